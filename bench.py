@@ -64,7 +64,13 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--dist-chunks", type=int, default=2,
                     help="row chunks per rank of the dist leg's operand exchange (chunk c + 1 travels under the GEMM of chunk c)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the headline's timed steps, write what its last step computed (hv, hv_norm_2, nhash) as "
+                         "DIR/<name>.npy (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 _CTX = []  # the bench's hg.Context once it exists: barrier_sync completes its queued sketch step (hg_ctx_sync) first
@@ -297,6 +303,32 @@ def cpu_baseline_dist(hv, n2, seconds, log):
                       "i16 dot per pair), OpenMP over rows on %d threads, %.2f s" % (rows, q_rows, cores, dt)}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: the most all ranks together write
+
+
+def dump_outputs(d, hv, n2, nh, rank, world):
+    """--dump-outputs DIR: what a caller of the headline step (hg_sketch_batch_dev_packed) receives from its last timed
+    step -- the HVs as float32 (i16 values, exact), the squared norms and hash counts as float64 (i32 values, exact).
+    More genomes than fit this rank's share of DUMP_BYTES: a fixed, seeded sample of them (the same for the same
+    arguments), whose genome indices go to hv_rows.npy.  With N > 1 ranks, rank r writes into DIR/rank<r>/."""
+    if world > 1:
+        d = os.path.join(d, "rank%d" % rank)
+    os.makedirs(d, exist_ok=True)
+    n = hv.shape[0]
+    per_genome = hv.shape[1] * 4 + 2 * 8 + 8  # hv row, norm and count, row index
+    limit = (DUMP_BYTES // world - 4 * 1024) // per_genome  # (1 KB for the header of each of the four files)
+    rows = None
+    if n > limit:
+        rows = np.sort(np.random.default_rng(0x48470D).choice(n, limit, replace=False))
+        sel = torch.from_numpy(rows).to(hv.device)
+        hv, n2, nh = hv[sel], n2[sel], nh[sel]
+        np.save(os.path.join(d, "hv_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "hv.npy"), hv.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(d, "hv_norm_2.npy"), n2.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(d, "nhash.npy"), nh.cpu().numpy().astype(np.float64))
+    return {"dir": d, "genomes": n if rows is None else int(rows.size), "of": n}
+
+
 def self_launch(a):
     """`python bench.py --gpus N` with N > 1 and no torch.distributed environment: start the N ranks as CHILD
     processes (torch.distributed.run, one per GPU, rendezvous on 127.0.0.1), let rank 0's JSON line through on the
@@ -415,6 +447,7 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
     tm = ctx.timings()
     ctx.enable_timing(False)
+    dumped = dump_outputs(a.dump_outputs, hv, n2, nh, rank, world) if a.dump_outputs else None
     kmer_ms, kmer_launches = tm["kmer"]
     kmer_avg_ms = kmer_ms / max(kmer_launches, 1)
     bytes_per_launch = N * (L_GENOME + 2 * HV_D)  # L + 2*D algorithmic bytes per genome
@@ -492,6 +525,8 @@ def main():
                            "config": {"workload": "the same %d genomes resident as ASCII (1 B per base, %.1f GB), "
                                                   "hg_sketch_batch_dev; sketches identical to the headline's" % (N, N * stride / 1e9)}},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
 
     # ---------------- the inputs real users have (never `value`) ----------------------------------------------------
     # Every timed leg above runs on clean, single-contig, iid-uniform genomes.  (a) `draft_assemblies`: the SAME N genomes

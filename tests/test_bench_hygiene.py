@@ -77,3 +77,31 @@ def test_draftify_makes_what_it_says():
         cs = np.concatenate([[0], np.cumsum(same)])
         run = cs[40_000:] - cs[:-40_000]  # matches in every window of 40 000 positions
         assert run.max() > 0.995 * 40_000
+
+
+def test_dump_outputs_exact_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the headline's arrays as float32 / float64 with their values unchanged; more genomes
+    than fit 64 MB: the same seeded sample on every call, named in hv_rows.npy, and never more than 64 MB in all"""
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "np", np)
+    monkeypatch.setattr(bench, "torch", torch)
+    g = torch.Generator().manual_seed(2)
+    for n, world in ((300, 1), (5000, 1), (3000, 2)):
+        hv = torch.randint(-2**15, 2**15, (n, 4096), dtype=torch.int16, generator=g)
+        n2 = torch.randint(0, 2**31 - 1, (n,), dtype=torch.int32, generator=g)
+        nh = torch.randint(0, 2**31 - 1, (n,), dtype=torch.int32, generator=g)
+        picks = []
+        for rep in range(2):
+            d = tmp_path / ("n%d_w%d_%d" % (n, world, rep))
+            info = bench.dump_outputs(str(d), hv, n2, nh, world - 1, world)
+            out = d / ("rank%d" % (world - 1)) if world > 1 else d
+            got = {f.name: np.load(f) for f in out.iterdir()}
+            assert (got["hv.npy"].dtype, got["hv_norm_2.npy"].dtype, got["nhash.npy"].dtype) == (np.float32, np.float64, np.float64)
+            rows = got["hv_rows.npy"].astype(np.int64) if "hv_rows.npy" in got else np.arange(n)
+            assert info["genomes"] == rows.size and info["of"] == n and (rows.size == n) == ("hv_rows.npy" not in got)
+            assert np.array_equal(got["hv.npy"], hv.numpy()[rows]) and np.array_equal(got["hv_norm_2.npy"], n2.numpy()[rows])
+            assert np.array_equal(got["nhash.npy"], nh.numpy()[rows])
+            assert sum(f.stat().st_size for f in out.iterdir()) * world <= 64 << 20
+            picks.append(rows)
+        assert np.array_equal(picks[0], picks[1])

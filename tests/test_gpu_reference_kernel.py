@@ -1,7 +1,11 @@
 """The reference's OWN kernel (src/cuda_kernel.cu built in place by hipcc into oracle/_ref/) run on
 the MI355X next to the oracle and the product: three-way agreement on the sampled hash sets.
 k <= 24 with the -O3 build of the reference source, k = 25..32 (the `default:` branch of its t1ha2_atonce: the
-prime_4 stage) with the -O0 build of the same source -- optimised builds of the reference kernel fault there."""
+prime_4 stage) with the -O0 build of the same source -- optimised builds of the reference kernel fault there.
+The reference kernel's hash set of every case is also stored (tests/golden/g3_ref_three_way.json: size and SHA-256 of
+the sorted set, tools/gen_golden_ref_gpu.py): the oracle and the product are held to it on every box, the live reference
+kernel joins where oracle/_ref/ was built."""
+import hashlib
 import os
 import subprocess
 import tempfile
@@ -9,7 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, golden
 
 pytestmark = pytest.mark.gpu
 REF = os.path.join(ROOT, "oracle", "_ref")
@@ -26,8 +30,21 @@ def run_ref(seq, k, scaled, seed=123, canonical=True, slots=0):
         return np.fromfile(fo, np.uint64)
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (needs /root/reference at build time)")
-@pytest.mark.parametrize("g,L,k,scaled,canon,slots", [
+def hash_set_digest(h):
+    """what g3_ref_three_way.json stores of a sorted hash set: its size and the SHA-256 of its little-endian u64 words"""
+    return {"n": int(h.size), "sha256": hashlib.sha256(np.ascontiguousarray(h, "<u8").tobytes()).hexdigest()}
+
+
+_STORED = []
+
+
+def stored_ref_set(name):
+    if not _STORED:
+        _STORED.append(golden("g3_ref_three_way.json"))
+    return _STORED[0][name]
+
+
+FIXED_CASES = [
     (11, 150_000, 21, 1500, True, 0),     # the reference's own launch parameters (8 slots/thread)
     (12, 150_000, 21, 1, True, 520),      # every k-mer
     (13, 80_000, 21, 20, False, 128),     # non-canonical mode (src/cuda_kernel.cu:312-314)
@@ -38,27 +55,20 @@ def run_ref(seq, k, scaled, seed=123, canonical=True, slots=0):
     (18, 60_000, 27, 5, False, 256),
     (19, 60_000, 31, 20, True, 128),
     (20, 60_000, 32, 1, True, 520),
-])
-def test_three_way_hash_sets(orc, g, L, k, scaled, canon, slots):
-    import hypergen_amd as hg
+]
+N_RANDOM = 60
+
+
+def fixed_case_input(orc, g, L):
     seq = orc.synth_genome(g, L).copy()
     rng = np.random.default_rng(g)
     seq[rng.choice(L, 30, replace=False) + 1] = ord("N")
     seq[1000:1500] = np.char.lower(seq[1000:1500].view("S1")).view(np.uint8)
-    ref = run_ref(seq, k, scaled, canonical=canon, slots=slots)
-    want = orc.kmer_hash_sample(seq, k, scaled, 123, canon)
-    with hg.Context(0) as ctx:
-        got = ctx.kmer_hash_sample(seq, k, scaled, 123, canon)
-    assert ref.size == want.size and (ref == want).all(), "reference kernel vs oracle"
-    assert got.size == want.size and (got == want).all(), "product vs oracle"
+    return seq
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref not built (needs /root/reference at build time)")
-@pytest.mark.parametrize("case", range(60))
-def test_three_way_random_cases(orc, case):
-    """Random k, sampling rate, seed, strand mode and contamination (N runs, lower case, IUPAC and other bytes, record
-    separators at random places), k = 1..32: the reference's own kernel, the oracle and the product must give the same hash set."""
-    import hypergen_amd as hg
+def random_case_input(orc, case):
+    """(seq, k, scaled, seed, canonical) of random case `case`"""
     rng = np.random.default_rng(31_000 + case)
     L = int(rng.integers(600, 40_000))
     k = int(rng.integers(1, 33))
@@ -74,18 +84,43 @@ def test_three_way_random_cases(orc, case):
         b = min(L + 1, a + int(rng.integers(1, 3000)))
         seq[a:b] = np.char.lower(seq[a:b].view("S1")).view(np.uint8)
     seq[rng.choice(L, int(rng.integers(0, 20)), replace=False) + 1] = ord("N")  # record separators / single N's
-    ref = run_ref(seq, k, scaled, seed=seed, canonical=canon, slots=520)
+    return seq, k, scaled, seed, canon
+
+
+@pytest.mark.parametrize("g,L,k,scaled,canon,slots", FIXED_CASES)
+def test_three_way_hash_sets(orc, g, L, k, scaled, canon, slots):
+    import hypergen_amd as hg
+    seq = fixed_case_input(orc, g, L)
+    want = orc.kmer_hash_sample(seq, k, scaled, 123, canon)
+    assert hash_set_digest(want) == stored_ref_set("fixed_g%d" % g), "stored reference kernel hash set vs oracle"
+    if HAVE_REF:
+        ref = run_ref(seq, k, scaled, canonical=canon, slots=slots)
+        assert ref.size == want.size and (ref == want).all(), "reference kernel vs oracle"
+    with hg.Context(0) as ctx:
+        got = ctx.kmer_hash_sample(seq, k, scaled, 123, canon)
+    assert got.size == want.size and (got == want).all(), "product vs oracle"
+
+
+@pytest.mark.parametrize("case", range(N_RANDOM))
+def test_three_way_random_cases(orc, case):
+    """Random k, sampling rate, seed, strand mode and contamination (N runs, lower case, IUPAC and other bytes, record
+    separators at random places), k = 1..32: the reference's own kernel, the oracle and the product must give the same hash set."""
+    import hypergen_amd as hg
+    seq, k, scaled, seed, canon = random_case_input(orc, case)
+    L = seq.size - 1
     want = orc.kmer_hash_sample(seq, k, scaled, seed, canon)
+    assert hash_set_digest(want) == stored_ref_set("random_%d" % case), ("stored reference kernel hash set vs oracle", k, scaled, canon, L)
     with hg.Context(0) as ctx:
         for form in ("ascii", "packed"):
             ctx.set_debug("kmer_input", form)
             got = ctx.kmer_hash_sample(seq, k, scaled, seed, canon)
             assert got.size == want.size and (got == want).all(), ("product vs oracle", form, k, scaled, canon, L)
-    assert ref.size == want.size and (ref == want).all(), ("reference kernel vs oracle", k, scaled, canon, L)
+    if HAVE_REF:
+        ref = run_ref(seq, k, scaled, seed=seed, canonical=canon, slots=520)
+        assert ref.size == want.size and (ref == want).all(), ("reference kernel vs oracle", k, scaled, canon, L)
 
 
 def _g2_cases():
-    from conftest import golden
     return golden("g2_ref_kernel.json")
 
 

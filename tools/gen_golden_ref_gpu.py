@@ -2,9 +2,9 @@
 """Run on the GPU box: produces golden hash sets with the REFERENCE's own kernel
 (src/cuda_kernel.cu compiled in place by hipcc -> oracle/_ref/) on seeded synthetic inputs.
 
-    gpurun -- python tools/gen_golden_ref_gpu.py        # writes gpurun_out/golden_ref/*.json
+    python tools/gen_golden_ref_gpu.py OUT_DIR        # writes OUT_DIR/*.json
 then copy the files into tests/golden/ (they are data: inputs are regenerated from the seed,
-the expected hash sets are stored as hex).
+the expected hash sets are stored as hex, or as size + SHA-256 for the three-way cases).
 """
 import json
 import os
@@ -17,7 +17,6 @@ import numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 REF = os.path.join(ROOT, "oracle", "_ref")
-OUT = os.path.join(ROOT, "gpurun_out", "golden_ref")
 
 
 def run_ref(seq, k, scaled, seed=123, canonical=True, slots=0):
@@ -33,7 +32,10 @@ def run_ref(seq, k, scaled, seed=123, canonical=True, slots=0):
 
 def main():
     from oracle import oracle as orc
-    os.makedirs(OUT, exist_ok=True)
+    if len(sys.argv) != 2:
+        raise SystemExit("usage: tools/gen_golden_ref_gpu.py OUT_DIR")
+    out = sys.argv[1]
+    os.makedirs(out, exist_ok=True)
     cases = []
     # (name, genome id, length, k, scaled, canonical, slots) -- slots=0: the reference's own 8
     for name, g, L, k, scaled, canon, slots in [
@@ -72,8 +74,31 @@ def main():
                       "subsampled": bool(ref.size > 4000),
                       "xor": "%016x" % int(np.bitwise_xor.reduce(ref) if ref.size else 0),
                       "sum": "%016x" % (int(ref.astype(object).sum()) % 2**64 if ref.size else 0)})
-    json.dump(cases, open(os.path.join(OUT, "g2_ref_kernel.json"), "w"), indent=1)
-    print("wrote", OUT)
+    json.dump(cases, open(os.path.join(out, "g2_ref_kernel.json"), "w"), indent=1)
+    three_way(orc, out)
+    print("wrote", out)
+
+
+def three_way(orc, out):
+    """g3_ref_three_way.json: the reference kernel's hash set of every case of tests/test_gpu_reference_kernel.py (the
+    cases and their inputs are taken from the test module), as size + SHA-256 of the sorted set"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_gpu_reference_kernel as t
+    sets, bad = {}, []
+    runs = []
+    for g, L, k, scaled, canon, slots in t.FIXED_CASES:
+        runs.append(("fixed_g%d" % g, t.fixed_case_input(orc, g, L), k, scaled, 123, canon, slots))
+    for case in range(t.N_RANDOM):
+        seq, k, scaled, seed, canon = t.random_case_input(orc, case)
+        runs.append(("random_%d" % case, seq, k, scaled, seed, canon, 520))
+    for name, seq, k, scaled, seed, canon, slots in runs:
+        ref = run_ref(seq, k, scaled, seed=seed, canonical=canon, slots=slots)
+        mine = orc.kmer_hash_sample(seq, k, scaled, seed, canon)
+        if not (ref.size == mine.size and (ref == mine).all()):
+            bad.append(name)
+        sets[name] = t.hash_set_digest(ref)
+    print("three-way cases: %d, reference kernel != oracle: %s" % (len(sets), bad or "none"))
+    json.dump(sets, open(os.path.join(out, "g3_ref_three_way.json"), "w"), indent=1, sort_keys=True)
 
 
 if __name__ == "__main__":
