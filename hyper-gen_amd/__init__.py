@@ -84,6 +84,7 @@ EXPORTS = [
     "hg_dist_ops_row_bytes", "hg_dist_ops_meta_bytes", "hg_dist_ops_padded_rows", "hg_dist_prep_ops_dev", "hg_dist_block_ops_dev",
     "hg_hv_packed_bytes_naive", "hg_hv_pack_naive", "hg_hv_unpack_naive", "hg_hv_payload_layout", "hg_hv_unpack_batch_dev",
     "hg_sketch_file_read_image", "hg_sketch_file_image", "hg_sketch_file_payload_offset",
+    "hg_cluster_init_dev", "hg_cluster_add_hits_dev", "hg_cluster_finish_dev", "hg_cluster_dev", "hg_cluster",
 ]
 
 
@@ -253,6 +254,11 @@ def lib():
         "hg_sketch_file_read_image": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
         "hg_sketch_file_image": (vp, [vp, C.POINTER(sz)]),
         "hg_sketch_file_payload_offset": (C.c_uint64, [vp, sz]),
+        "hg_cluster_init_dev": (C.c_int, [vp, vp, sz]),
+        "hg_cluster_add_hits_dev": (C.c_int, [vp, vp, sz, vp, sz, C.c_float]),
+        "hg_cluster_finish_dev": (C.c_int, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "hg_cluster_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, C.POINTER(sz)]),
+        "hg_cluster": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the ABI lost a symbol
@@ -555,6 +561,39 @@ class Context:
                                ksize, int(symmetric), C.c_float(ani_th), _ptr(d_out), cap, C.byref(n))
         self._ck(st, allow=(ERR_CAPACITY,))
         return n.value, st
+
+    # ---- single-linkage clustering (hg_cluster*) --------------------------------------------------
+    def cluster(self, hv, n2, ksize=21, ani_th=95.0):
+        """hg_cluster on host sketches: numpy (rep, cluster, n_clusters) -- rep[i] = smallest index of i's component,
+        cluster[i] = its dense id in order of rep"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        rep = np.zeros(n, np.uint32)
+        cl = np.zeros(n, np.uint32)
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th),
+                                  _ptr(rep), _ptr(cl), C.byref(nc)))
+        return rep, cl, nc.value
+
+    def cluster_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, ksize=21, ani_th=95.0):
+        """hg_cluster_dev on resident sketches (device pointers); returns the number of clusters"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep),
+                                      _ptr(d_cluster), C.byref(nc)))
+        return nc.value
+
+    def cluster_init_dev(self, d_rep, n):
+        self._ck(lib().hg_cluster_init_dev(self._h, _ptr(d_rep), n))
+
+    def cluster_add_hits_dev(self, d_rep, n, d_hits, n_hits, ani_th):
+        self._ck(lib().hg_cluster_add_hits_dev(self._h, _ptr(d_rep), n, _ptr(d_hits), n_hits, C.c_float(ani_th)))
+
+    def cluster_finish_dev(self, d_rep, n, d_cluster):
+        """returns the number of clusters; raises HgError(ERR_INVALID) if a hit since the init had an index >= n"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_finish_dev(self._h, _ptr(d_rep), n, _ptr(d_cluster), C.byref(nc)))
+        return nc.value
 
 
 def shard_range(n, shard, n_shards):

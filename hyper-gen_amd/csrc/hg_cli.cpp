@@ -75,10 +75,11 @@ struct Cli {
   bool canonical = true;
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
   float quant_scale = 1.0f, ani_th = 85.0f;
+  bool ani_th_given = false;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
 };
 
 Cli parse(int argc, char **argv) {
-  if (argc < 2) die("usage: hyper-gen <sketch|dist|search> [options]   (see --help)");
+  if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
   Cli c;
   c.mode = argv[1];
   if (c.mode == "--version" || c.mode == "-V") {
@@ -89,16 +90,19 @@ Cli parse(int argc, char **argv) {
     std::printf("HyperGen: Fast and memory-efficient genome sketching in hyperdimensional space (MI355X build)\n\n"
                 "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
                 "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
-                "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n\n"
+                "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
+                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0]\n\n"
                 "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
                 "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
                 "         -Q --quant_scale [1.0], -a --ani_th [85.0], -D --device [cpu]\n"
                 "extensions: -n --top_n [1] (search), --pack_layout avx2|naive [avx2] (sketch: the payload layout of\n"
                 "         reference hosts with / without AVX2; dist and search read both), --shards N (dist / search: N\n"
-                "         shards dealt round the visible GPUs; default one per GPU)\n");
+                "         shards dealt round the visible GPUs; default one per GPU), cluster (single-linkage clusters at\n"
+                "         -a --ani_th [95.0] on the first visible GPU: one line per sketch, file, cluster id, file of the\n"
+                "         cluster's first member)\n");
     std::exit(0);
   }
-  if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search") die("unknown subcommand '" + c.mode + "'");
+  if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
   if (c.mode != "sketch") c.method = "fracminhash";
   static const std::map<std::string, char> longs = {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
@@ -148,10 +152,10 @@ Cli parse(int argc, char **argv) {
       case 's': c.scaled = u(~0ull); break;
       case 'd': c.hv_d = u(~0ull); break;
       case 'Q': c.quant_scale = std::strtof(val.c_str(), nullptr); break;
-      case 'a': c.ani_th = std::strtof(val.c_str(), nullptr); break;
+      case 'a': c.ani_th = std::strtof(val.c_str(), nullptr), c.ani_th_given = true; break;
       case 'D': c.device = val; break;
       case 'n': c.top_n = (unsigned)u(1u << 20); break;  // search only (extension: the reference's search is a stub)
-      case 'G': c.shards = (unsigned)u(64); break;  // dist / search only (testing aid: the several-GPU path on fewer GPUs)
+      case 'G': c.shards = (unsigned)u(64); break;  // dist / search only (cluster rejects it) (testing aid: the several-GPU path on fewer GPUs)
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -768,6 +772,68 @@ int run_search(const Cli &c) {
   return 0;
 }
 
+
+// `cluster` (an extension: the reference has no such subcommand): single-linkage clusters of the sketches of one file at an
+// ANI threshold, computed where the hits are (hg_cluster_dev: the symmetric comparison in row blocks, each block's hits
+// unioned on the device).  One line per sketch record, in file order: "<file_str>\t<cluster id>\t<file_str of the
+// cluster's first member>\n" -- ids count the clusters in the order of their first members.
+int run_cluster(const Cli &c) {
+  if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
+  if (c.shards) die("--shards is not supported by cluster: it runs on the first visible GPU");
+  const float th = c.ani_th_given ? c.ani_th : 95.0f;
+  const auto t0 = std::chrono::steady_clock::now();
+  Loaded L;
+  hg_multi *multi = nullptr;
+  std::thread opener([&] { multi = open_all_devices(1); });  // (the HIP runtime comes up while the file is read)
+  load(c.path, L);
+  opener.join();
+  DevSet D;
+  to_devices(multi, L, D);
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "Clustering %zu genomes at ANI threshold %.1f..", L.n, th);
+  logline("INFO", buf);
+  double tp = now_s();
+  hg_ctx *ctx = hg_multi_ctx(multi, 0);
+  void *d_rep = nullptr, *d_cl = nullptr;
+  ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_rep), "alloc");
+  ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_cl), "alloc");
+  size_t n_cl = 0;
+  ck(ctx, hg_cluster_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
+                         static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
+  std::vector<uint32_t> rep(L.n), cl(L.n);
+  ck(ctx, hg_copy_d2h(ctx, rep.data(), d_rep, L.n * sizeof(uint32_t)), "download");
+  ck(ctx, hg_copy_d2h(ctx, cl.data(), d_cl, L.n * sizeof(uint32_t)), "download");
+  (void)hg_dev_free(ctx, d_rep), (void)hg_dev_free(ctx, d_cl);
+  release(multi, D);
+  debugf("clusters on the host in %.1f ms", (now_s() - tp) * 1e3);
+  std::vector<uint32_t> size(n_cl, 0);
+  for (size_t i = 0; i < L.n; ++i) {
+    if (cl[i] >= n_cl || rep[i] > i) die("inconsistent cluster result");
+    ++size[cl[i]];
+  }
+  size_t singletons = 0;
+  for (uint32_t s : size) singletons += s == 1;
+  std::string o;
+  for (size_t i = 0; i < L.n; ++i) {
+    o += hg_sketch_file_get(L.f, i)->file_str;
+    o += '\t';
+    o += std::to_string(cl[i]);
+    o += '\t';
+    o += hg_sketch_file_get(L.f, rep[i])->file_str;
+    o += '\n';
+  }
+  FILE *f = std::fopen(c.out.c_str(), "wb");
+  if (!f || std::fwrite(o.data(), 1, o.size(), f) != o.size() || std::fclose(f) != 0) die("Dump cluster file failed!");
+  std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %.1f to file %s", L.n, n_cl,
+                singletons, th, c.out.c_str());
+  logline("INFO", buf);
+  std::snprintf(buf, sizeof buf, "Clustered %zu files took %.3fs", L.n,
+                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  logline("INFO", buf);
+  hg_sketch_file_free(L.f);
+  hg_multi_destroy(multi);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -776,5 +842,6 @@ int main(int argc, char **argv) {
   // 10 000 x 10 000 dist -- but those handlers are also where rocprofv3 and other tools write what they collected)
   if (c.mode == "sketch") return run_sketch(c);
   if (c.mode == "dist") return run_dist(c);
+  if (c.mode == "cluster") return run_cluster(c);
   return run_search(c);
 }

@@ -11,6 +11,7 @@
 // call of a process -- which is the only call `hyper-gen dist` makes).
 #include <cstring>
 
+#include "hg_block_scan.h"
 #include "hg_internal.h"
 
 namespace {
@@ -93,28 +94,6 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(const K *__restrict__ k
   }
   __syncthreads();
   counts[(size_t)threadIdx.x * n_blocks + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// block-wide exclusive scan of one value per thread (256 threads); returns the block total through *total
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *s_wave /* 4 words */, uint32_t *total) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t up = __shfl_up(inc, o);
-    if (lane >= (uint32_t)o) inc += up;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < 4; ++w) {
-    const uint32_t t = s_wave[w];
-    before += w < wave ? t : 0u, all += t;
-  }
-  __syncthreads();  // (s_wave may be reused by the caller's next round)
-  *total = all;
-  return before + inc - v;
 }
 
 __global__ __launch_bounds__(256) void radix_scan_kernel(uint32_t *__restrict__ counts, uint32_t n_blocks, uint32_t *__restrict__ totals) {

@@ -96,6 +96,9 @@ struct hg_ctx {
   uint32_t i8_sig_r = 0, i8_sig_q = 0, i8_sig_d = 0;
   uint32_t i8_skip = 0;         // calls left that skip the i8 attempt after it was vetoed
   Buf w_sorthits; // keys / permutations / scratch of the device-side hit ordering
+  Buf w_clu_res;  // clustering: 16 result words ([0] cluster count, [1] error word of the hook kernel), never regrown
+  Buf w_clu;      // clustering: per-tile root counts of the dense-id scan
+  Buf w_clu_hits; // hg_cluster_dev: scratch hit list of one row block
   // optional per-kernel timing (hg_ctx_enable_timing)
   bool timing = false;
   struct TimedLaunch {
@@ -135,6 +138,7 @@ struct hg_ctx {
   // development / test hooks (hg_ctx_set_debug); never read from the environment
   std::string dbg_dist_tile, dbg_dist_path, dbg_ham_path, dbg_dist_order, dbg_kmer_input, dbg_hostfed, dbg_sketch_path;
   int dbg_sort_buckets = 0;
+  uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the scratch list of hg_cluster_dev starts with (0: its own size)
   uint64_t dbg_pair_limit = 0;  // test hook "pair_limit": pairs one kernel launch of a comparison may enumerate (0: 2^32 - 1, the hit counter's reach)
   // pinned host scratch
   void *h_pin = nullptr;

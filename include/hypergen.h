@@ -82,6 +82,8 @@ int hg_device_count(void);
  *       "sort_test_buckets" = "<n>"   (bucket count of the large-set sort; 0 = automatic)
  *       "pair_limit" = "<n>"          (pairs one launch of a thresholded comparison / search may enumerate before the call is
  *                                      split into blocks of reference rows; 0 = 2^32 - 1, the reach of the hit counter)
+ *       "cluster_hit_cap" = "<n>"     (hits the scratch list of hg_cluster_dev starts with -- small forces its grow path;
+ *                                      0 = the ctx's own size)
  * Nothing in the library reads environment variables. */
 hg_status hg_ctx_set_debug(hg_ctx *ctx, const char *key, const char *value);
 
@@ -325,6 +327,37 @@ hg_status hg_sort_ani_hits_staged(hg_ctx *ctx, hg_ani_hit *hits, size_t n, size_
  * d_counts[q] = number of valid entries (<= k).  Device pointers; stream-ordered. */
 hg_status hg_topk_per_query_dev(hg_ctx *ctx, const hg_ani_hit *d_hits, size_t n, size_t Q, uint32_t k,
                                 hg_ani_hit *d_out, uint32_t *d_counts);
+
+/* `cluster` (no reference counterpart; its users cluster dump_ani_file's TSV, src/utils.rs:262-285, in another tool):
+ * single-linkage clustering at an ANI threshold.  The graph has an edge {i, j} for every pair i < j with ani >= ani_th
+ * (the ANI of hg_dist_dev, the side of the threshold exactly as there).  For every sketch i:
+ *   rep[i]     = the smallest index of i's connected component (i itself without edges);
+ *   cluster[i] = the component's dense id: 0, 1, ... in increasing order of rep (the file order of the clusters' first members);
+ *   *n_clusters = the number of components.
+ * The result depends on the graph alone -- not on scheduling, blocks, hit order or how many calls delivered the hits.
+ * d_rep / d_cluster: n uint32 of device memory, n < 2^32 (hg_cluster_dev / hg_cluster: n < 2^31).
+ * Step by step, on a hit list the caller has (e.g. of hg_dist_dev at a low threshold, clustered at several higher ones
+ * without another GEMM; or of several hg_dist_block_dev calls / GPUs):
+ *   hg_cluster_init_dev     : d_rep[i] = i.  Stream-ordered.
+ *   hg_cluster_add_hits_dev : unions the hits with ani >= ani_th (self-pairs ignored) into d_rep; any number of calls,
+ *                             stream-ordered.  A hit with an index >= n is skipped and remembered.
+ *   hg_cluster_finish_dev   : d_rep[i] = the component minimum, d_cluster, *n_clusters; final when it returns (like
+ *                             hg_dist_dev once its count is back).  HG_ERR_INVALID if a hit given since the init had an
+ *                             index >= n.
+ * That error word is kept by the ctx: one step-by-step clustering at a time per ctx. */
+hg_status hg_cluster_init_dev(hg_ctx *ctx, uint32_t *d_rep, size_t n);
+hg_status hg_cluster_add_hits_dev(hg_ctx *ctx, uint32_t *d_rep, size_t n, const hg_ani_hit *d_hits, size_t n_hits,
+                                  float ani_th);
+hg_status hg_cluster_finish_dev(hg_ctx *ctx, uint32_t *d_rep, size_t n, uint32_t *d_cluster, size_t *n_clusters);
+/* The whole job on resident sketches (d_hv: n x hv_d int16, d_norm2: n): init, the symmetric comparison in blocks of rows
+ * [r0, r0 + rows) x columns [r0, n) into a scratch hit list the ctx owns, each block unioned before the next one runs
+ * (the hits of the whole matrix are never held at once -- past 66 000 sketches their count can pass 2^32), finish.  The
+ * scratch list grows to a block's hit count when it overflows, and the block runs again (debug key "cluster_hit_cap"
+ * sets the size it starts with).  hg_cluster: host arrays in and out, staged through the ctx. */
+hg_status hg_cluster_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                         float ani_th, uint32_t *d_rep, uint32_t *d_cluster, size_t *n_clusters);
+hg_status hg_cluster(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                     float ani_th, uint32_t *rep, uint32_t *cluster, size_t *n_clusters);
 
 /* ---- sketch compression (host side; src/hd.rs:114-232) -------------------------------- */
 uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d);
