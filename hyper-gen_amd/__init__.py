@@ -23,6 +23,7 @@ CLI_PATH = os.path.join(_HERE, "hyper-gen")
 
 LAYOUT_SCALAR, LAYOUT_AVX2 = 0, 1
 GATHER_PEER, GATHER_RCCL = 0, 1
+ANI_MASH, ANI_CONTAINMENT, ANI_MAX_CONTAINMENT = 0, 1, 2  # hg_ctx_set_ani_metric
 NORM_ACGT, NORM_U2T = 0, 1
 (OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_IO,
  ERR_INEXACT) = range(9)
@@ -85,6 +86,7 @@ EXPORTS = [
     "hg_hv_packed_bytes_naive", "hg_hv_pack_naive", "hg_hv_unpack_naive", "hg_hv_payload_layout", "hg_hv_unpack_batch_dev",
     "hg_sketch_file_read_image", "hg_sketch_file_image", "hg_sketch_file_payload_offset",
     "hg_cluster_init_dev", "hg_cluster_add_hits_dev", "hg_cluster_finish_dev", "hg_cluster_dev", "hg_cluster",
+    "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
 ]
 
 
@@ -212,6 +214,9 @@ def lib():
         "hg_sketch_stream_close": (None, [vp]),
         "hg_sketch_stream_stats": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double)]),
         "hg_ctx_last_dist_path": (C.c_int, [vp]),
+        "hg_ctx_set_ani_metric": (C.c_int, [vp, C.c_int]),
+        "hg_ctx_ani_metric": (C.c_int, [vp]),
+        "hg_multi_set_ani_metric": (C.c_int, [vp, C.c_int]),
         "hg_ctx_last_hamming_path": (C.c_int, [vp]),
         "hg_sort_ani_hits_dev": (C.c_int, [vp, vp, sz, sz]),
         "hg_sort_ani_hits_staged": (C.c_int, [vp, vp, sz, sz]),
@@ -540,6 +545,14 @@ class Context:
         """0 = f16 MFMA, 1 = i8 MFMA, 2 = integer VALU (all exact), -1 = no thresholded dist call yet."""
         return int(lib().hg_ctx_last_dist_path(self._h))
 
+    def set_ani_metric(self, metric):
+        """ANI_MASH (default), ANI_CONTAINMENT (dot / the query's norm: directional) or ANI_MAX_CONTAINMENT (dot / the
+        smaller norm) for this ctx's later dist / cluster calls (hg_ctx_set_ani_metric)."""
+        self._ck(lib().hg_ctx_set_ani_metric(self._h, metric))
+
+    def ani_metric(self):
+        return int(lib().hg_ctx_ani_metric(self._h))
+
     def last_hamming_path(self):
         """0 = xor + popcount kernel, 1 = +-1 byte GEMM on the matrix pipe (same integers), -1 = none yet."""
         return int(lib().hg_ctx_last_hamming_path(self._h))
@@ -638,6 +651,10 @@ class Multi:
     def set_gather(self, mode):
         """GATHER_PEER (direct hipMemcpyPeerAsync pulls) or GATHER_RCCL (ncclAllGather / grouped ncclBroadcast)."""
         self._ck(lib().hg_multi_set_gather(self._h, mode))
+
+    def set_ani_metric(self, metric):
+        """hg_multi_set_ani_metric: the ANI metric of every shard's ctx (see Context.set_ani_metric)."""
+        self._ck(lib().hg_multi_set_ani_metric(self._h, metric))
 
     def gather_mode(self):
         return lib().hg_multi_gather_mode(self._h)

@@ -137,6 +137,16 @@ extern "C" hg_status hg_ctx_reset_stream(hg_ctx *c) {
 
 extern "C" int hg_ctx_last_dist_path(const hg_ctx *c) { return c ? c->last_dist_path : -1; }
 
+extern "C" hg_status hg_ctx_set_ani_metric(hg_ctx *c, int metric) {
+  if (!c) return HG_ERR_INVALID;
+  if (metric != HG_ANI_MASH && metric != HG_ANI_CONTAINMENT && metric != HG_ANI_MAX_CONTAINMENT)
+    return hg_fail(c, HG_ERR_INVALID, "unknown ANI metric " + std::to_string(metric));
+  c->ani_metric = metric;
+  return HG_OK;
+}
+
+extern "C" int hg_ctx_ani_metric(const hg_ctx *c) { return c ? c->ani_metric : HG_ANI_MASH; }
+
 extern "C" hg_status hg_ctx_set_debug(hg_ctx *c, const char *key, const char *value) {
   if (!c || !key) return HG_ERR_INVALID;
   const std::string k = key, v = value ? value : "";

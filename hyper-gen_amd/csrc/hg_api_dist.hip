@@ -24,7 +24,10 @@
 // dist
 // ---------------------------------------------------------------------------------------------
 namespace {
-hg_status check_dist(hg_ctx *c, size_t R, size_t Q, uint32_t hv_d, uint32_t ksize) {
+// (the ctx's ANI metric, hg_ctx_set_ani_metric, is read here: every dist entry point checks its arguments through this)
+hg_status check_dist(hg_ctx *c, size_t R, size_t Q, uint32_t hv_d, uint32_t ksize, int symmetric = 0) {
+  if (symmetric && c->ani_metric == HG_ANI_CONTAINMENT)
+    return hg_fail(c, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
   if (R > 0x7FFFFFFFull || Q > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "R, Q must be < 2^31");
   if (hv_d == 0 || hv_d > 65536) return hg_fail(c, HG_ERR_UNSUPPORTED, "hv_d must be in 1..65536");
   if (ksize == 0) return hg_fail(c, HG_ERR_INVALID, "ksize must be >= 1");
@@ -45,6 +48,7 @@ extern "C" hg_status hg_dist_full_dev(hg_ctx *c, const int16_t *d_ref_hv, const 
   a.ref_hv = d_ref_hv, a.ref_n2 = d_ref_norm2, a.qry_hv = d_qry_hv, a.qry_n2 = d_qry_norm2;
   a.R = (uint32_t)R, a.Q = (uint32_t)Q, a.hv_d = hv_d, a.ksize = ksize;
   a.ani_out = d_ani_out;
+  a.ani_metric = c->ani_metric;
   return hg_run_dist(c, a);
 }
 
@@ -97,7 +101,7 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   if (!c) return HG_ERR_INVALID;
   if (!n_out) return hg_fail(c, HG_ERR_INVALID, "n_out == NULL");
   *n_out = 0;
-  hg_status s = check_dist(c, R, Q, hv_d, ksize);
+  hg_status s = check_dist(c, R, Q, hv_d, ksize, symmetric);
   if (s != HG_OK) return s;
   if (ref_off + R > 0x7FFFFFFFull || qry_off + Q > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "global indices must be < 2^31");
   if (R == 0 || Q == 0) return HG_OK;
@@ -115,7 +119,7 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   a.R = (uint32_t)R, a.Q = (uint32_t)Q, a.hv_d = hv_d, a.ksize = ksize;
   a.hits = d_out, a.hit_count = d_count;
   a.hit_cap = cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap;
-  a.ani_th = ani_th, a.symmetric = symmetric;
+  a.ani_th = ani_th, a.symmetric = symmetric, a.ani_metric = c->ani_metric;
   a.ref_off = (uint32_t)ref_off, a.qry_off = (uint32_t)qry_off;
   int spec_cover = -1;
   if ((s = hg_run_dist(c, a, d_count + 1, &spec_cover)) != HG_OK) return s;
@@ -211,7 +215,7 @@ static hg_status dist_block_ops_once(hg_ctx *c, const uint8_t *d_ref_ops, const 
   if (!c) return HG_ERR_INVALID;
   if (!n_out) return hg_fail(c, HG_ERR_INVALID, "n_out == NULL");
   *n_out = 0;
-  hg_status s = check_dist(c, R, Q, hv_d, ksize);
+  hg_status s = check_dist(c, R, Q, hv_d, ksize, symmetric);
   if (s != HG_OK) return s;
   if (ref_off + R > 0x7FFFFFFFull || qry_off + Q > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "global indices must be < 2^31");
   if (R == 0 || Q == 0) return HG_OK;
@@ -228,7 +232,7 @@ static hg_status dist_block_ops_once(hg_ctx *c, const uint8_t *d_ref_ops, const 
   a.R = (uint32_t)R, a.Q = (uint32_t)Q, a.hv_d = hv_d, a.ksize = ksize;
   a.hits = d_out, a.hit_count = d_count;
   a.hit_cap = cap > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cap;
-  a.ani_th = ani_th, a.symmetric = symmetric;
+  a.ani_th = ani_th, a.symmetric = symmetric, a.ani_metric = c->ani_metric;
   a.ref_off = (uint32_t)ref_off, a.qry_off = (uint32_t)qry_off;
   a.ref_ops = d_ref_ops, a.ref_meta = d_ref_meta, a.ref_flags = d_flags, a.n_flags = (uint32_t)n_flags, a.ref_index = d_ref_index;
   int spec = -1;
@@ -302,7 +306,7 @@ extern "C" hg_status hg_dist(hg_ctx *c, const int16_t *ref_hv, const int32_t *re
   if (!c) return HG_ERR_INVALID;
   if (!n_out) return hg_fail(c, HG_ERR_INVALID, "n_out == NULL");
   *n_out = 0;
-  hg_status s = check_dist(c, R, Q, hv_d, ksize);
+  hg_status s = check_dist(c, R, Q, hv_d, ksize, symmetric);
   if (s != HG_OK) return s;
   if (R == 0 || Q == 0) return HG_OK;
   if (!ref_hv || !ref_norm2 || !qry_hv || !qry_norm2 || (cap && !out)) return hg_fail(c, HG_ERR_INVALID, "NULL argument");

@@ -76,6 +76,7 @@ struct Cli {
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
   float quant_scale = 1.0f, ani_th = 85.0f;
   bool ani_th_given = false;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
+  int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
 };
 
 Cli parse(int argc, char **argv) {
@@ -99,7 +100,11 @@ Cli parse(int argc, char **argv) {
                 "         reference hosts with / without AVX2; dist and search read both), --shards N (dist / search: N\n"
                 "         shards dealt round the visible GPUs; default one per GPU), cluster (single-linkage clusters at\n"
                 "         -a --ani_th [95.0] on the first visible GPU: one line per sketch, file, cluster id, file of the\n"
-                "         cluster's first member)\n");
+                "         cluster's first member), --ani_metric mash|containment|max_containment [mash] (dist / search /\n"
+                "         cluster: containment = the share of the query's hashes found in the reference -- the identity of a\n"
+                "         fragment, a partial MAG or a draft with a larger genome; max_containment = the same against the\n"
+                "         smaller of the two; dist on one file with containment writes every ordered pair i != j; cluster\n"
+                "         takes mash or max_containment)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -107,7 +112,7 @@ Cli parse(int argc, char **argv) {
   static const std::map<std::string, char> longs = {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
-      {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}};
+      {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -155,7 +160,13 @@ Cli parse(int argc, char **argv) {
       case 'a': c.ani_th = std::strtof(val.c_str(), nullptr), c.ani_th_given = true; break;
       case 'D': c.device = val; break;
       case 'n': c.top_n = (unsigned)u(1u << 20); break;  // search only (extension: the reference's search is a stub)
-      case 'G': c.shards = (unsigned)u(64); break;  // dist / search only (cluster rejects it) (testing aid: the several-GPU path on fewer GPUs)
+      case 'G': c.shards = (unsigned)u(64); break;
+      case '\x01':  // (long form only)
+        if (val == "mash") c.ani_metric = HG_ANI_MASH;
+        else if (val == "containment") c.ani_metric = HG_ANI_CONTAINMENT;
+        else if (val == "max_containment") c.ani_metric = HG_ANI_MAX_CONTAINMENT;
+        else die("invalid value '" + val + "' for '--ani_metric' (mash | containment | max_containment)");
+        break;  // dist / search only (cluster rejects it) (testing aid: the several-GPU path on fewer GPUs)
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -551,12 +562,15 @@ int run_dist(const Cli &c) {
     die("the following required arguments were not provided: --path_r --path_q --out");
   const auto t0 = std::chrono::steady_clock::now();
   const bool sym = c.path_r == c.path_q;  // src/dist.rs:13
+  // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
+  const bool sym_full = sym && c.ani_metric == HG_ANI_CONTAINMENT;
   Loaded R, Qs;
   double tp = now_s();
   hg_multi *multi = nullptr;
   std::thread opener([&] {  // the HIP runtime comes up (~0.2 s) while the sketch files are read and decompressed
     const double td = now_s();
     multi = open_all_devices(c.shards);
+    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
     debugf("devices opened in %.1f ms", (now_s() - td) * 1e3);
   });
   {  // two files are read and parsed side by side
@@ -577,11 +591,18 @@ int run_dist(const Cli &c) {
   debugf("payloads uploaded and decompressed on the device(s) in %.1f ms", (now_s() - tp) * 1e3);
   logline("INFO", "Computing ANI..");
   tp = now_s();
-  const size_t total = sym ? R.n * (Q.n - 1) / 2 : R.n * Q.n;
+  const size_t total = sym_full ? R.n * (R.n - 1) : (sym ? R.n * (Q.n - 1) / 2 : R.n * Q.n);
   HitBuf hits;
   // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
   // sort of up to 10^6..10^8 triples on one host core)
-  const size_t found = all_hits(multi, R, dR, sym ? nullptr : &Qs, sym ? nullptr : &dQ, c.ani_th, true, hits);
+  size_t found = sym_full ? all_hits(multi, R, dR, &R, &dR, c.ani_th, true, hits)
+                         : all_hits(multi, R, dR, sym ? nullptr : &Qs, sym ? nullptr : &dQ, c.ani_th, true, hits);
+  if (sym_full) {  // (the pairs i = j are not written: the order of the rest stays)
+    size_t w = 0;
+    for (size_t i = 0; i < found; ++i)
+      if (hits.p[i].ref_idx != hits.p[i].qry_idx) hits.p[w++] = hits.p[i];
+    found = w;
+  }
   release(multi, dR), release(multi, dQ);
   debugf("ANI matrix (%zu hits), ordered, on the host in %.1f ms", found, (now_s() - tp) * 1e3);
   tp = now_s();
@@ -678,6 +699,7 @@ int run_search(const Cli &c) {
   std::thread opener([&] {  // the HIP runtime comes up while the files are read
     const double td = now_s();
     multi = open_all_devices(c.shards);
+    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
     debugf("devices opened in %.1f ms", (now_s() - td) * 1e3);
   });
   {  // the two files are read and parsed side by side
@@ -780,11 +802,15 @@ int run_search(const Cli &c) {
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.shards) die("--shards is not supported by cluster: it runs on the first visible GPU");
+  if (c.ani_metric == HG_ANI_CONTAINMENT) die("--ani_metric containment is not supported by cluster: it is directional (mash | max_containment)");
   const float th = c.ani_th_given ? c.ani_th : 95.0f;
   const auto t0 = std::chrono::steady_clock::now();
   Loaded L;
   hg_multi *multi = nullptr;
-  std::thread opener([&] { multi = open_all_devices(1); });  // (the HIP runtime comes up while the file is read)
+  std::thread opener([&] {  // (the HIP runtime comes up while the file is read)
+    multi = open_all_devices(1);
+    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
+  });
   load(c.path, L);
   opener.join();
   DevSet D;

@@ -232,6 +232,8 @@ extern "C" hg_status hg_cluster_dev(hg_ctx *c, const int16_t *d_hv, const int32_
   if (!n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_clusters == NULL");
   *n_clusters = 0;
   if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^31");
+  if (c->ani_metric == HG_ANI_CONTAINMENT)  // (the graph is undirected: HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT)
+    return hg_fail(c, HG_ERR_INVALID, "clustering needs a symmetric ANI metric: HG_ANI_CONTAINMENT is directional");
   if (n && (!d_hv || !d_norm2 || !d_rep || !d_cluster)) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
   hg_status s = hg_cluster_init_dev(c, d_rep, n);
@@ -269,6 +271,8 @@ extern "C" hg_status hg_cluster(hg_ctx *c, const int16_t *hv, const int32_t *nor
   if (!n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_clusters == NULL");
   *n_clusters = 0;
   if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^31");
+  if (c->ani_metric == HG_ANI_CONTAINMENT)  // (the graph is undirected: HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT)
+    return hg_fail(c, HG_ERR_INVALID, "clustering needs a symmetric ANI metric: HG_ANI_CONTAINMENT is directional");
   if (n == 0) return HG_OK;
   if (!hv || !norm2 || !rep || !cluster) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);

@@ -30,4 +30,23 @@ __device__ __forceinline__ float ani_from_dot(int32_t dot, int32_t nr, int32_t n
   return ani * 100.0f;
 }
 
+// ---- the containment metrics (hg_ctx_set_ani_metric; include/hypergen.h) ---------------------------------------------------
+// x = dot / nq (HG_ANI_CONTAINMENT: the share of the query's hashes found in the reference) or dot / min(nr, nq)
+// (HG_ANI_MAX_CONTAINMENT), then exactly the tail of ani_from_dot: 1 + ln(x) / k, NaN -> 0, clamp to [0, 1], x 100, all of it
+// f32 in this order (dot <= 0 -> 0; den = 0 -> NaN -> 0 or +inf -> 100; dot > den -> 100).  With equal norms
+// 2J / (1 + J) = dot / n, so both reduce to the Mash-style value up to rounding.  `contain`: HG_ANI_CONTAINMENT.
+__device__ __forceinline__ float ani_from_dot_containment(bool contain, int32_t dot, int32_t nr, int32_t nq, float kf) {
+  const int32_t den = contain ? nq : (nr < nq ? nr : nq);
+  const float x = (float)dot / (float)den;
+  float ani = 1.0f + hg_logf(x) / kf;
+  if (ani != ani) return 0.0f;
+  ani = fminf(ani, 1.0f);
+  ani = fmaxf(ani, 0.0f);
+  return ani * 100.0f;
+}
+// any metric (a uniform value: the integer and streaming kernels, hg_ani_from_dots_dev)
+__device__ __forceinline__ float ani_from_dot_metric(int metric, int32_t dot, int32_t nr, int32_t nq, float kf) {
+  return metric == HG_ANI_MASH ? ani_from_dot(dot, nr, nq, kf) : ani_from_dot_containment(metric == HG_ANI_CONTAINMENT, dot, nr, nq, kf);
+}
+
 }  // namespace

@@ -45,7 +45,7 @@ __device__ __forceinline__ void dist_load_tile_words(const GemmArgs &g, uint32_t
   }
 }
 
-template <bool BIG, bool GLDS, int NT, bool I8, bool HAM, bool CEN>
+template <bool BIG, bool GLDS, int NT, bool I8, bool HAM, bool CEN, bool CTM = false>
 __device__ __forceinline__ void dist_stage_tile_words(const GemmArgs &g, _Float16 *sAB, uint32_t row0, uint32_t col0,
                                                       const DistTileWords<BIG, NT> &w_) {
   using TC = TileCfg<BIG, NT>;
@@ -100,7 +100,18 @@ __device__ __forceinline__ void dist_stage_tile_words(const GemmArgs &g, _Float1
       }
       // (finite sentinels, so that `d - ur - tq` is never NaN: "out of range" outweighs "norm outside the safe range")
       if (HAM) s_ur[t] = !in ? 1e30f : (is_r ? 0.f : (float)g.ham_thr);  // G >= ham_thr, exact while D <= 2^24
-      else {
+      else if constexpr (CTM) {
+        // The containment metrics: dot >= c' * nq (HG_ANI_CONTAINMENT) or dot >= c' * min(nr, nq) (HG_ANI_MAX_CONTAINMENT) --
+        // not of the form ur(row) + tq(column) --, as `d >= ur + tq + min(ar, aq)`: ur / tq carry the slacks (and pre_b),
+        // ar / aq the scaled c' * norm.  Containment makes the row's ar +1e30, so that the min is the column's.  A norm
+        // outside [0, 2^29] gives -1e20 in both words (phase 1 decides), a row / column past R / Q keeps its +1e30 in ur / tq:
+        // every sum stays finite (|each word| <= 1e30).
+        const bool bad = nv < 0 || nv > NORM_SAFE;
+        const float thr = fminf(fmaxf(((is_r ? 0.f : g.pre_b) - slack) * p0_scale, -1e20f), 1e20f);
+        const float a = fminf(fmaxf(g.pre_c * (float)nv * p0_scale, -1e20f), 1e20f);
+        s_ur[t] = !in ? 1e30f : (bad ? -1e20f : thr);
+        s_ar[t] = !in ? 0.f : (bad ? -1e20f : ((is_r && g.metric == HG_ANI_CONTAINMENT) ? 1e30f : a));
+      } else {
         // (clamped: pre_b is -inf when every pair passes -- ani_th <= 0 -- and +inf when none can; left infinite, a
         // column threshold of -inf would cancel the "out of range" of a row: inf - inf, and with it the only thing
         // that keeps the rows past R out of the lane-mask path's lists)
@@ -114,7 +125,7 @@ __device__ __forceinline__ void dist_stage_tile_words(const GemmArgs &g, _Float1
 }
 
 // The epilogue of one tile (see the comments inside; returns when the tile's hits are in the global list).
-template <bool CHUNKED, bool FULL, bool BIG, bool GLDS, int NT, bool I8, bool HAM, bool FP4, bool CEN>
+template <bool CHUNKED, bool FULL, bool BIG, bool GLDS, int NT, bool I8, bool HAM, bool FP4, bool CEN, bool CTM = false>
 __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, uint32_t row0, uint32_t col0,
                                               dist_acc_t<I8, FP4> (&acc)[TileCfg<BIG, NT>::WTM][NT],
                                               int32_t (&iacc)[CHUNKED ? TileCfg<BIG, NT>::WTM : 1][CHUNKED ? NT : 1][4]) {
@@ -246,7 +257,9 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
       for (int u = 0; u < U; ++u) {
         if (k0 + (uint32_t)u * NW_ >= nb) break;  // wave-uniform: the group is not full
         const uint32_t li = key[u] >> 16, lj = key[u] & 0xffffu;
-        const float ani = HG_EXP(128) ? (float)val[u] * 1e-9f + 99.f : ani_from_dot(val[u], s_nr[li], s_nq[lj], g.kf);
+        float ani;
+        if constexpr (CTM) ani = ani_from_dot_containment(g.metric == HG_ANI_CONTAINMENT, val[u], s_nr[li], s_nq[lj], g.kf);
+        else ani = HG_EXP(128) ? (float)val[u] * 1e-9f + 99.f : ani_from_dot(val[u], s_nr[li], s_nq[lj], g.kf);
         if constexpr (FULL) {
           if (g.ani_out && valid[u]) g.ani_out[(size_t)(row0 + li) * g.Q + (col0 + lj)] = ani;
         }
@@ -351,13 +364,15 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
   // fetched here, the four row thresholds of a slab with one 16-byte read per slab (all 4 * WTM of them kept in
   // registers from the top push the i8 kernels into scratch).
   int32_t nqv[NT];
-  float tq[NT];
+  float tq[NT], aq[CTM ? NT : 1];
 #pragma unroll
   for (int n = 0; n < NT; ++n) {
     nqv[n] = s_nq[wn * (NT * 16) + n * 16 + fr];
     tq[n] = s_tq[wn * (NT * 16) + n * 16 + fr];
+    if constexpr (CTM) aq[n] = s_aq[wn * (NT * 16) + n * 16 + fr];
   }
   const float4v *s_ur4 = reinterpret_cast<const float4v *>(s_ur + wm * (WTM * 16) + fq * 4);  // slab m: s_ur4[4 m]
+  [[maybe_unused]] const float4v *s_ar4 = reinterpret_cast<const float4v *>(s_ar + wm * (WTM * 16) + fq * 4);  // (CTM)
   HG_TSTAMP(3)
   // Two ways through the accumulators (in-kernel stamps, DESIGN.md 4.3: with one branch per element and the row words
   // read slab by slab the sweep took 20 000 cycles in a tile without a single candidate and 25 000 more in a tile with
@@ -393,6 +408,8 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
         constexpr int m = decltype(mc)::value;
         uint32_t np = 0;
         const float4v ur4 = s_ur4[4 * m];
+        [[maybe_unused]] float4v ar4;
+        if constexpr (CTM) ar4 = s_ar4[4 * m];
         dist_static_for(std::make_integer_sequence<int, 4>{}, [&](auto rc) {
           constexpr int r = decltype(rc)::value;
           dist_static_for(std::make_integer_sequence<int, NT>{}, [&](auto nc) {
@@ -407,7 +424,8 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
               asm("v_cvt_f32_i32_e32 %0, %1" : "=v"(di) : "v"(iacc[CHUNKED ? m : 0][CHUNKED ? n : 0][r]));
               d += di;
             }
-            const float margin = (d - ur4[r]) - tq[n];  // (finite sentinels: never NaN)
+            float margin = (d - ur4[r]) - tq[n];  // (finite sentinels: never NaN)
+            if constexpr (CTM) margin -= fminf(ar4[r], aq[n]);
             np = __builtin_amdgcn_alignbit(np, __float_as_uint(margin), 31);  // (np << 1) | sign: element e = r * NT + n at bit 4 NT - 1 - e
           });
         });
@@ -556,6 +574,8 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
   dist_static_for(std::make_integer_sequence<int, WTM>{}, [&](auto mc) {
     constexpr int m = decltype(mc)::value;
     const float4v ur4 = s_ur4[4 * m];
+    [[maybe_unused]] float4v ar4;
+    if constexpr (CTM) ar4 = s_ar4[4 * m];
     auto passes = [&](auto rc, auto nc) __attribute__((always_inline)) -> bool {
       constexpr int r = decltype(rc)::value, n = decltype(nc)::value;
       if constexpr (FULL) return true;
@@ -563,7 +583,8 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
       else {
         float d = (float)acc[m][n][r];
         if (CHUNKED) d += (float)iacc[CHUNKED ? m : 0][CHUNKED ? n : 0][r];
-        return d >= ur4[r] + tq[n];
+        if constexpr (CTM) return (d - ur4[r]) - tq[n] - fminf(ar4[r], aq[n]) >= 0.f;
+        else return d >= ur4[r] + tq[n];
       }
     };
     unsigned long long slab = FULL ? ~0ull : 0ull;
@@ -585,7 +606,7 @@ __device__ __forceinline__ void dist_epilogue(const GemmArgs &g, _Float16 *sAB, 
           int32_t dot = (int32_t)acc[m][n][r];
           if (CHUNKED) dot = (int32_t)((uint32_t)dot + (uint32_t)iacc[CHUNKED ? m : 0][CHUNKED ? n : 0][r]);
           bool live = pass && iok && j < g.Q && !(g.symmetric && i + g.ref_off >= j + g.qry_off);
-          if (!FULL && !I8 && !CEN) {  // (centred operands: the list carries the raw G, phase 2 forms the exact dot product)
+          if (!FULL && !I8 && !CEN && !CTM) {  // (centred operands: the list carries the raw G, phase 2 forms the exact dot product)
             const int32_t den = (int32_t)((uint32_t)s_nr[li] + (uint32_t)nqv[n] - (uint32_t)dot);
             live = live && (den <= 0 || (float)dot >= g.j_lo * (float)den);
           }

@@ -51,9 +51,11 @@ constexpr size_t dist_lds_main_bytes() {
   const size_t lists = (size_t)(TC::THREADS / 64) * CAND_CAP * 8;
   return stages > lists ? stages : lists;
 }
-template <bool BIG, int NT, bool GLDS>
+// CTM (the containment metrics): one more float per row and column behind the rest, the pre-filter's c' * norm (see
+// dist_stage_tile_words).  The 256 x 320 tile then takes 163 776 B of the CU's 163 840.
+template <bool BIG, int NT, bool GLDS, bool CTM = false>
 constexpr size_t dist_lds_bytes() {
-  return dist_lds_main_bytes<BIG, NT, GLDS>() + (size_t)6 * (TileCfg<BIG, NT>::BM + TileCfg<BIG, NT>::BN) * 4 + 192;
+  return dist_lds_main_bytes<BIG, NT, GLDS>() + (size_t)(CTM ? 7 : 6) * (TileCfg<BIG, NT>::BM + TileCfg<BIG, NT>::BN) * 4 + 192;
 }
 
 struct GemmArgs {
@@ -96,6 +98,8 @@ struct GemmArgs {
   const uint32_t *tile_tab;        // slot -> tile (tm | tn << 16, ~0u: no tile) built by the host (dist_tile_table); nullptr:
                                    // the workgroup derives its tile from blockIdx as described at the top of the kernel
   int32_t ham_thr;                 // HAM: candidates are G >= ham_thr
+  int metric;                      // CTM instantiations: HG_ANI_CONTAINMENT or HG_ANI_MAX_CONTAINMENT (pre_c is then c' of
+                                   // dot >= c' * nq or dot >= c' * min(nr, nq), see ctm_lower_bound)
 };
 
 // development builds only (-DHG_DIST_EXPERIMENT=<bits>, results are wrong): timing with parts of the kernel
@@ -149,7 +153,7 @@ template <bool I8, bool FP4>
 using dist_acc_t = typename std::conditional<I8 && !FP4, int4v, float4v>::type;
 
 // The tile's row / column words live behind the operand stages (dist_lds_bytes): norms, i8 info / slot / first-entry
-// words, the phase-0 thresholds and the epilogue's counters.  Declares the pointers (needs BIG, NT, GLDS, BM, BN, THREADS
+// words, the phase-0 thresholds, the epilogue's counters and (CTM kernels only) the rows' / columns' c' * norm.  Declares the pointers (needs BIG, NT, GLDS, BM, BN, THREADS
 // and sAB in scope): written by dist_stage_tile_words at kernel entry, read by the epilogue.
 #define HG_DIST_TILE_WORDS                                                                                                             \
   int32_t *s_nr = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(sAB) + dist_lds_main_bytes<BIG, NT, GLDS>()), *s_nq = s_nr + BM; \
@@ -159,6 +163,8 @@ using dist_acc_t = typename std::conditional<I8 && !FP4, int4v, float4v>::type;
   float *s_ur = reinterpret_cast<float *>(s_fq + BN), *s_tq = s_ur + BM; \
   uint32_t *s_er = reinterpret_cast<uint32_t *>(s_tq + BN), *s_eq = s_er + BM; \
   uint32_t *s_cnt = s_eq + BN; \
-  uint32_t *s_tot = s_cnt + 2 * (THREADS / 64) + 4, *s_fill = s_tot + THREADS / 64;
+  uint32_t *s_tot = s_cnt + 2 * (THREADS / 64) + 4, *s_fill = s_tot + THREADS / 64; \
+  float *s_ar = reinterpret_cast<float *>(reinterpret_cast<char *>(sAB) + dist_lds_bytes<BIG, NT, GLDS>()), *s_aq = s_ar + BM; \
+  (void)s_ar, (void)s_aq;
 
 }  // namespace

@@ -62,10 +62,12 @@ namespace {
 // epilogue recovers dot = 4 G - 2 e_q S_r - 2 e_r S_q + D e_r e_q from the row / column info words like the i8 path,
 // without clamped entries.  Sketches too large for byte operands (beyond ~6 000 hashes) take this kernel instead of the
 // windowed one with its i32 side accumulators and 256 x 192 tiles.
-template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool HAM = false, bool FP4 = false,
-          bool CEN = false>
-__global__ __launch_bounds__((TileCfg<BIG, 4>::THREADS)) void dist_mfma_kernel(GemmArgs g) {
+// CTM: the containment metrics (g.metric: HG_ANI_CONTAINMENT or HG_ANI_MAX_CONTAINMENT) -- the pre-filter's extra word per row
+// and column and phase 2's formula (hg_dist_epilogue.h); dist_mfma_ctm_kernel below.  The Mash-style kernel is CTM = false.
+template <bool CHUNKED, bool FULL, bool BIG, bool GLDS, int NT, bool I8, bool HAM, bool FP4, bool CEN, bool CTM>
+__device__ __forceinline__ void dist_mfma_tile(GemmArgs &g) {
   using TC = TileCfg<BIG, NT>;
+  static_assert(!CTM || !HAM, "the Hamming search has no ANI metric");
   static_assert(!CEN || (!I8 && GLDS && !CHUNKED && !FULL), "centred f16 operands: thresholded whole-K LDS-DMA geometries");
   static_assert(!I8 || (GLDS && !CHUNKED && !FULL), "the i8 operand path exists for the thresholded LDS-DMA geometries");
   static_assert(!HAM || I8, "the Hamming epilogue rides on the i8 operand path");
@@ -158,8 +160,119 @@ __global__ __launch_bounds__((TileCfg<BIG, 4>::THREADS)) void dist_mfma_kernel(G
   DistTileWords<BIG, NT> words;
   dist_load_tile_words<BIG, NT, I8, HAM, CEN>(g, row0, col0, words);
   dist_main_loop<CHUNKED, BIG, GLDS, NT, I8, FP4>(g, sAB, row0, col0, acc, iacc,
-                                                  [&]() { dist_stage_tile_words<BIG, GLDS, NT, I8, HAM, CEN>(g, sAB, row0, col0, words); });
-  dist_epilogue<CHUNKED, FULL, BIG, GLDS, NT, I8, HAM, FP4, CEN>(g, sAB, row0, col0, acc, iacc);
+                                                  [&]() { dist_stage_tile_words<BIG, GLDS, NT, I8, HAM, CEN, CTM>(g, sAB, row0, col0, words); });
+  dist_epilogue<CHUNKED, FULL, BIG, GLDS, NT, I8, HAM, FP4, CEN, CTM>(g, sAB, row0, col0, acc, iacc);
+}
+
+// The Mash-style kernel: the same body with CTM = false, written out in the kernel itself.  (A kernel that only calls
+// dist_mfma_tile compiles to different code -- other register choices and block layout in most of the 15 instantiations --,
+// and these instantiations keep exactly the code they had before the containment metrics.)
+template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool HAM = false, bool FP4 = false,
+          bool CEN = false>
+__global__ __launch_bounds__((TileCfg<BIG, 4>::THREADS)) void dist_mfma_kernel(GemmArgs g) {
+  constexpr bool CTM = false;
+  using TC = TileCfg<BIG, NT>;
+  static_assert(!CTM || !HAM, "the Hamming search has no ANI metric");
+  static_assert(!CEN || (!I8 && GLDS && !CHUNKED && !FULL), "centred f16 operands: thresholded whole-K LDS-DMA geometries");
+  static_assert(!I8 || (GLDS && !CHUNKED && !FULL), "the i8 operand path exists for the thresholded LDS-DMA geometries");
+  static_assert(!HAM || I8, "the Hamming epilogue rides on the i8 operand path");
+  static_assert(!FP4 || HAM, "e2m1 operands exist for the Hamming search only");
+  HG_TSTAMP(0)
+#ifdef HG_DIST_STAMPS
+  if (threadIdx.x == 0 && blockIdx.x < 2048)
+    g_dist_tile_all[blockIdx.x][3] = 0, g_dist_tile_all[blockIdx.x][1] = 0, g_dist_tile_all[blockIdx.x][2] = 0,
+    g_dist_tile_all[blockIdx.x][5] = 0, g_dist_tile_all[blockIdx.x][6] = 0, g_dist_tile_all[blockIdx.x][7] = 0,
+    g_dist_tile_all[blockIdx.x][8] = 0, g_dist_tile_all[blockIdx.x][9] = 0, g_dist_tile_all[blockIdx.x][10] = 0,
+    g_dist_tile_all[blockIdx.x][11] = 0, g_dist_tile_all[blockIdx.x][12] = 0, g_dist_tile_all[blockIdx.x][13] = 0,
+    g_dist_tile_all[blockIdx.x][4] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) |  // hwreg(HW_REG_XCC_ID, 0, 4)
+                                     ((unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)) << 8);  // HW_REG_HW_ID
+#endif
+  if (g.veto && (CEN ? g.veto[0] == 1u : g.veto[0] != 0u)) return;  // uniform: a kernel queued before this one did the work (1: the i8 one, 2: the centred f16 one)
+  if (I8 && !HAM) {
+    const bool ok = i8_attempt_valid(g.i8ctrl, g.ent_cap);
+    if (blockIdx.x == 0 && threadIdx.x == 0) g.i8verdict[0] = ok ? 1u : 0u, g.i8verdict[1] = g.Kp / BK;
+    if (!ok) return;
+  }
+  if (g.verdict) {  // uniform
+    const uint32_t code = g.verdict[0];
+    if (code < g.v_lo || code > g.v_hi) return;
+    if (CHUNKED && g.chunk_from_verdict) g.chunk_steps = g.verdict[1];
+  }
+  static_assert(!GLDS || BIG, "LDS-DMA variant exists for the 256 x 256 geometry only");
+  constexpr int BM = TC::BM, BN = TC::BN, WTM = TC::WTM;
+  extern __shared__ __attribute__((aligned(16))) _Float16 sAB[];
+
+  // XCD-aware tile order (MI355X guide T1): workgroups b and b + 8 run on the same XCD and share its 4 MiB L2, so every
+  // XCD gets a contiguous run of tiles (bijective remap) and walks 8 x 8 super-tiles inside it: the 32 workgroups resident
+  // on an XCD cover 4 x 8 tiles -- 4 A row-blocks and 8 B row-blocks through that L2 instead of 32 different B blocks
+  // (measured in round 1: 7.0 GB of L2 misses per 10k x 10k launch with plain row-major order) --, and the next 4 x 8
+  // tiles reuse the same 8 B blocks.  (Round 3 tried 4 x 8 super-tiles dealt round-robin to the XCDs, to spread the
+  // expensive diagonal tiles of a self-comparison evenly: the same time on i8 operands, but the L2 hit rate fell from
+  // 68 % to 64 %, and from 63 % to 49 % on f16 operands -- without the shared B blocks between consecutive groups.  The
+  // diagonal is dealt with below.)
+  // A database compared with itself in file order has its hits on the diagonal, and a tile with 20 000 candidates spends
+  // twice as long in its epilogue as in its K loop: with five tiles per CU the launch ends when the last such tile does.
+  // The host may therefore put the tiles that straddle the diagonal in front (g.diag_first workgroup slots, two per tile
+  // row, a multiple of 8 so that the XCD of the remaining workgroups is unchanged): longest jobs first.
+  uint32_t tm, tn;
+  if (g.tile_tab) {
+    // the host's table: exactly the tiles that have work, every XCD the same number of them (+-1) in the order described
+    // above, the diagonal ones in front.  Slots that return at once -- the super-tile grid's padding, the diagonal tiles'
+    // places in the walk, the lower triangle of a symmetric comparison -- made some CUs run six tiles and others four
+    // where five each were due: the hardware deals workgroup i to XCD i % 8 whatever it turns out to do.
+    const uint32_t t = g.tile_tab[blockIdx.x];
+    if (t == ~0u) return;
+    tm = t & 0xFFFFu, tn = t >> 16;
+  } else if (blockIdx.x < g.diag_first) {
+    // slot s: tile row s % (diag_first / 2), its first (s < diag_first / 2) or second diagonal tile -- diag_first / 2 is a
+    // multiple of 8, so the rows' first tiles, the dense ones, go round the XCDs (with two adjacent slots per row they
+    // all fell to the even XCDs: 223 k against 126 k candidates per XCD)
+    const uint32_t half = g.diag_first >> 1, second = blockIdx.x >= half ? 1u : 0u;
+    tm = blockIdx.x - second * half;
+    if (tm >= g.tiles_m) return;
+    const uint32_t tn0 = tm * BM / BN, tn1 = (tm * BM + BM - 1) / BN;
+    tn = second ? tn1 : tn0;
+    if ((second && tn1 == tn0) || tn >= g.tiles_n) return;
+  } else {
+    const uint32_t b = blockIdx.x - g.diag_first, nwg = gridDim.x - g.diag_first;
+    const uint32_t q = nwg / 8, r = nwg % 8, xcd = b % 8;
+    const uint32_t bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
+    const uint32_t sup_n = (g.tiles_n + ST - 1) / ST;
+    const uint32_t sup = bid / (ST * ST), within = bid % (ST * ST);
+    tm = (sup / sup_n) * ST + within / ST, tn = (sup % sup_n) * ST + within % ST;
+    if (tm >= g.tiles_m || tn >= g.tiles_n) return;  // padding of the super-tile grid
+    if (g.diag_first && (tn == tm * BM / BN || tn == (tm * BM + BM - 1) / BN)) return;  // ran in front
+  }
+  const uint32_t row0 = tm * BM, col0 = tn * BN;
+  if (g.symmetric && row0 + g.ref_off >= col0 + g.qry_off + BN) return;  // tile entirely on/below the diagonal
+
+  dist_acc_t<I8, FP4> acc[WTM][NT];
+  int32_t iacc[CHUNKED ? WTM : 1][CHUNKED ? NT : 1][4];
+#pragma unroll
+  for (int m = 0; m < WTM; ++m)
+#pragma unroll
+    for (int n = 0; n < NT; ++n) acc[m][n] = dist_acc_t<I8, FP4>{};
+  if (CHUNKED) {
+#pragma unroll
+    for (int m = 0; m < WTM; ++m)
+#pragma unroll
+      for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) iacc[CHUNKED ? m : 0][CHUNKED ? n : 0][r] = 0;
+  }
+  // the three parts (hg_dist_epilogue.h, hg_dist_mainloop.h): the tile's row / column words are requested first, the main
+  // loop publishes them with its first operand stage, the epilogue turns the accumulators into hits
+  DistTileWords<BIG, NT> words;
+  dist_load_tile_words<BIG, NT, I8, HAM, CEN>(g, row0, col0, words);
+  dist_main_loop<CHUNKED, BIG, GLDS, NT, I8, FP4>(g, sAB, row0, col0, acc, iacc,
+                                                  [&]() { dist_stage_tile_words<BIG, GLDS, NT, I8, HAM, CEN, CTM>(g, sAB, row0, col0, words); });
+  dist_epilogue<CHUNKED, FULL, BIG, GLDS, NT, I8, HAM, FP4, CEN, CTM>(g, sAB, row0, col0, acc, iacc);
+}
+
+// the same tiles under HG_ANI_CONTAINMENT / HG_ANI_MAX_CONTAINMENT (one instantiation serves both: g.metric is uniform)
+template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool CEN = false>
+__global__ __launch_bounds__((TileCfg<BIG, 4>::THREADS)) void dist_mfma_ctm_kernel(GemmArgs g) {
+  dist_mfma_tile<CHUNKED, FULL, BIG, GLDS, NT, I8, false, false, CEN, true>(g);
 }
 
 // ---- always-exact integer fallback -------------------------------------------------------------------
@@ -189,7 +302,7 @@ __global__ __launch_bounds__(FB_T *FB_T) void dist_int_kernel(const int16_t *__r
   const uint32_t i = i0 + ty, j = j0 + tx;
   if (i >= a.R || j >= a.Q) return;
   if (a.symmetric && i + a.ref_off >= j + a.qry_off) return;
-  const float ani = ani_from_dot((int32_t)acc, a.ref_n2[i], a.qry_n2[j], kf);
+  const float ani = ani_from_dot_metric(a.ani_metric, (int32_t)acc, a.ref_n2[i], a.qry_n2[j], kf);
   if (a.ani_out) a.ani_out[(size_t)i * a.Q + j] = ani;
   if (a.hit_count && ani >= a.ani_th) {
     const uint32_t idx = atomicAdd(a.hit_count, 1u);
@@ -274,7 +387,9 @@ __global__ __launch_bounds__(SK_T) void dist_skinny_kernel(const int16_t *__rest
     const uint32_t sq = lane & 31u, row = row0 + (lane >> 5);  // this lane's small row and large row
     const uint32_t i = SWAP ? sq : row, j = SWAP ? row : sq;   // (reference row, query column) of its pair
     if (sq < n_sml && (lane < 32 || two) && !(a.symmetric && i + a.ref_off >= j + a.qry_off)) {
-      ani = SWAP ? ani_from_dot(mine, sml_n2[sq], big_n2[row], kf) : ani_from_dot(mine, big_n2[row], sml_n2[sq], kf);
+      // (reference norm first either way: under HG_ANI_CONTAINMENT the denominator is the QUERY's norm, whichever side is small)
+      ani = SWAP ? ani_from_dot_metric(a.ani_metric, mine, sml_n2[sq], big_n2[row], kf)
+                 : ani_from_dot_metric(a.ani_metric, mine, big_n2[row], sml_n2[sq], kf);
       hit = ani >= a.ani_th;
     }
     const unsigned long long bal = __ballot(hit);
@@ -300,6 +415,13 @@ static std::string dist_kernel_name() {
          std::to_string(NT) + ", " + b(I8) + ", " + b(HAM) + ", " + b(FP4) + ", " + b(CEN) + ">";
 }
 #define HG_DIST_K(...) &dist_mfma_kernel<__VA_ARGS__>, dist_kernel_name<__VA_ARGS__>()
+template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool CEN = false>
+static std::string dist_ctm_kernel_name() {
+  auto b = [](bool x) { return x ? "true" : "false"; };
+  return std::string("dist_mfma_ctm_kernel<") + b(CHUNKED) + ", " + b(FULL) + ", " + b(BIG) + ", " + b(GLDS) + ", " +
+         std::to_string(NT) + ", " + b(I8) + ", " + b(CEN) + ">";
+}
+#define HG_DIST_CTM_K(...) &dist_mfma_ctm_kernel<__VA_ARGS__>, dist_ctm_kernel_name<__VA_ARGS__>()
 
 // ---- bit-packed Hamming search on the matrix pipe ---------------------------------------------------------------
 // bits -> +-1 bytes (bit 1 -> +1, bit 0 -> -1), one lane per 32-bit word: per nibble the four bits are spread to the
@@ -441,6 +563,30 @@ static float jaccard_lower_bound(float ani_th, uint32_t ksize) {
   return (float)(j * (1.0 - 1e-4));
 }
 
+// The containment metrics: ANI >= th  <=>  x >= exp(k*(th/100-1)), x = dot / nq or dot / min(nr, nq); with the same margin.
+static float ctm_lower_bound(float ani_th, uint32_t ksize) {
+  if (!(ani_th > 0.0f)) return -INFINITY;
+  if (ani_th > 100.0f) return INFINITY;
+  return (float)(std::exp((double)ksize * ((double)ani_th / 100.0 - 1.0)) * (1.0 - 1e-4));
+}
+// phase 0's pre_c / pre_b (and the slab path's j_lo) for the ctx's metric: dot < pre_c * (nr + nq) + pre_b rejects a pair under
+// HG_ANI_MASH; under the containment metrics pre_c is c' of dot < c' * nq (or * min(nr, nq)), pre_b the same +-inf / 0
+static void dist_prefilter(GemmArgs &g, const hg_dist_args &a) {
+  g.metric = a.ani_metric;
+  if (a.ani_metric != HG_ANI_MASH) {
+    const float cl = ctm_lower_bound(a.ani_th, a.ksize);
+    g.j_lo = cl;
+    if (cl == -INFINITY) g.pre_c = 0.f, g.pre_b = -INFINITY;
+    else if (cl == INFINITY) g.pre_c = 0.f, g.pre_b = INFINITY;
+    else g.pre_c = cl, g.pre_b = 0.f;
+    return;
+  }
+  g.j_lo = jaccard_lower_bound(a.ani_th, a.ksize);
+  if (g.j_lo == -INFINITY) g.pre_c = 0.f, g.pre_b = -INFINITY;       // everything goes on to phase 1
+  else if (g.j_lo == INFINITY) g.pre_c = 0.f, g.pre_b = INFINITY;    // ANI <= 100 < ani_th: nothing does
+  else g.pre_c = (float)((double)g.j_lo / (1.0 + (double)g.j_lo) * (1.0 - 1e-5)), g.pre_b = 0.f;
+}
+
 hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int *speculated) {
   if (speculated) *speculated = -1;
   const uint32_t Kp = (a.hv_d + BK - 1) / BK * BK;
@@ -564,10 +710,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     g.chunk_steps = ~0u, g.kf = (float)a.ksize;
     g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap, g.ani_th = a.ani_th;
     g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
-    g.j_lo = jaccard_lower_bound(a.ani_th, a.ksize);
-    if (g.j_lo == -INFINITY) g.pre_c = 0.f, g.pre_b = -INFINITY;
-    else if (g.j_lo == INFINITY) g.pre_c = 0.f, g.pre_b = INFINITY;
-    else g.pre_c = (float)((double)g.j_lo / (1.0 + (double)g.j_lo) * (1.0 - 1e-5)), g.pre_b = 0.f;
+    dist_prefilter(g, a);
     g.info_r = info_r, g.info_q = info_q, g.slot_r = slot_r, g.slot_q = slot_q, g.ents = list;
     g.first_r = first_r, g.first_q = first_q, g.ent_cap = ent_cap, g.i8verdict = ctrl + 4;
     g.raw_q = a.qry_hv, g.ref_index = a.ref_index, g.i8ctrl = ctrl, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
@@ -578,10 +721,27 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
       if (r5 * 9 < r4 * 8) nt = 5;  // (256 x 320 costs 1.25 x 0.9 of 256 x 256, see hg_run_hamming_mfma)
       if (c->dbg_dist_tile == "big") nt = 4;
       else if (c->dbg_dist_tile == "wide") nt = 5;
+      if (a.ani_metric != HG_ANI_MASH) nt = 4;  // (see the launch below)
     }
     g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
     // (the same matrix on both sides at the same global offset: hits cluster on the diagonal -- those tiles first)
     const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
+    const bool ctm = a.ani_metric != HG_ANI_MASH;
+    if (ctm) {
+      // (the containment metrics: the CTM epilogue on 256 x 256 tiles only -- with the second pre-filter word the
+      // 256 x 320 byte-operand kernel would spill, as its Mash-style sibling already does: 10 VGPRs, 44 B of scratch)
+      const size_t lds = dist_lds_bytes<true, 4, true, true>();
+      const void *fp = reinterpret_cast<const void *>(&dist_mfma_ctm_kernel<false, false, true, true, 4, true>);
+      if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
+        HG_HIP(c, hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        c->lds_attr_done.push_back(fp);
+      }
+      hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
+      c->last_kernel_i8 = dist_ctm_kernel_name<false, false, true, true, 4, true>();
+      hipLaunchKernelGGL((dist_mfma_ctm_kernel<false, false, true, true, 4, true>), dim3(n_tiles), dim3(TileCfg<true, 4>::THREADS), lds,
+                         c->stream, g);
+      HG_HIP(c, hipGetLastError());
+    } else {
     const size_t lds = nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>();
     const void *fp = nt == 5 ? reinterpret_cast<const void *>(&dist_mfma_kernel<false, false, true, true, 5, true>)
                              : reinterpret_cast<const void *>(&dist_mfma_kernel<false, false, true, true, 4, true>);
@@ -599,6 +759,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
         hipLaunchKernelGGL((dist_mfma_kernel<false, false, true, true, 4, true>), dim3(n_tiles), dim3(TileCfg<true, 4>::THREADS), lds,
                            c->stream, g);
       HG_HIP(c, hipGetLastError());
+    }
     }
     veto = ctrl + 4;
     if (ops_given) {  // (nothing to fall back on: the caller reads the verdict)
@@ -662,10 +823,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     g.chunk_steps = ~0u, g.kf = (float)a.ksize;
     g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap, g.ani_th = a.ani_th;
     g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
-    g.j_lo = jaccard_lower_bound(a.ani_th, a.ksize);
-    if (g.j_lo == -INFINITY) g.pre_c = 0.f, g.pre_b = -INFINITY;
-    else if (g.j_lo == INFINITY) g.pre_c = 0.f, g.pre_b = INFINITY;
-    else g.pre_c = (float)((double)g.j_lo / (1.0 + (double)g.j_lo) * (1.0 - 1e-5)), g.pre_b = 0.f;
+    dist_prefilter(g, a);
     g.info_r = info_r, g.info_q = info_q, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
     g.verdict = cverdict, g.v_lo = 0, g.v_hi = 0, g.veto = mark;
     int nt = 4;
@@ -678,7 +836,9 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     }
     g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
     const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
-    const size_t lds = nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>();
+    const bool ctm = a.ani_metric != HG_ANI_MASH;
+    const size_t lds = ctm ? (nt == 5 ? dist_lds_bytes<true, 5, true, true>() : dist_lds_bytes<true, 4, true, true>())
+                           : (nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>());
     auto launch_cen = [&](auto kern, const std::string &name, int threads) -> hipError_t {
       const void *fp = reinterpret_cast<const void *>(kern);
       if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
@@ -692,8 +852,12 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     };
     {
       hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
-      HG_HIP(c, nt == 5 ? launch_cen(HG_DIST_K(false, false, true, true, 5, false, false, false, true), TileCfg<true, 5>::THREADS)
-                        : launch_cen(HG_DIST_K(false, false, true, true, 4, false, false, false, true), TileCfg<true, 4>::THREADS));
+      if (ctm)
+        HG_HIP(c, nt == 5 ? launch_cen(HG_DIST_CTM_K(false, false, true, true, 5, false, true), TileCfg<true, 5>::THREADS)
+                          : launch_cen(HG_DIST_CTM_K(false, false, true, true, 4, false, true), TileCfg<true, 4>::THREADS));
+      else
+        HG_HIP(c, nt == 5 ? launch_cen(HG_DIST_K(false, false, true, true, 5, false, false, false, true), TileCfg<true, 5>::THREADS)
+                          : launch_cen(HG_DIST_K(false, false, true, true, 4, false, false, false, true), TileCfg<true, 4>::THREADS));
     }
     veto = mark;
     // the previous call on exactly these operands ran on centred operands: the raw-value chain is not queued again
@@ -818,10 +982,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
   g.ani_th = a.ani_th, g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
   g.verdict = guard, g.v_lo = v_lo, g.v_hi = v_hi, g.chunk_from_verdict = from_verdict ? 1u : 0u;
   g.veto = veto;
-  g.j_lo = jaccard_lower_bound(a.ani_th, a.ksize);
-  if (g.j_lo == -INFINITY) g.pre_c = 0.f, g.pre_b = -INFINITY;       // everything goes on to phase 1
-  else if (g.j_lo == INFINITY) g.pre_c = 0.f, g.pre_b = INFINITY;    // ANI <= 100 < ani_th: nothing does
-  else g.pre_c = (float)((double)g.j_lo / (1.0 + (double)g.j_lo) * (1.0 - 1e-5)), g.pre_b = 0.f;
+  dist_prefilter(g, a);
   const bool whole_k = (64u << best_c) >= Kp;  // one window covers K: no i32 side accumulators
   const bool full = a.ani_out != nullptr;
   // big tiles when the problem fills the chip with them (Rp, Qp are multiples of 128: the last big
@@ -867,7 +1028,20 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
   // (two operand stages or the epilogue's candidate lists, + the tile's row / column words: dist_lds_bytes)
   const size_t lds_small = dist_lds_bytes<false, 4, false>(), lds_dma = dist_lds_bytes<true, 4, true>();
   const size_t lds_wide = dist_lds_bytes<true, 5, true>(), lds_chunked = dist_lds_bytes<true, NT_CHUNKED, true>();
-  static_assert(dist_lds_bytes<true, 5, true>() <= 160 * 1024, "the widest tile fits the CU's LDS");
+  static_assert(dist_lds_bytes<true, 5, true, true>() <= 160 * 1024, "the widest tile fits the CU's LDS");
+  if (a.ani_metric != HG_ANI_MASH) {  // the containment metrics: the same choice of tiles, the CTM epilogue (hg_dist_epilogue.h)
+    const size_t cs = dist_lds_bytes<false, 4, false, true>(), cd = dist_lds_bytes<true, 4, true, true>();
+    const size_t cw = dist_lds_bytes<true, 5, true, true>(), cc = dist_lds_bytes<true, NT_CHUNKED, true, true>();
+    if (big_chunked) le = launch(HG_DIST_CTM_K(true, false, true, true, NT_CHUNKED), TileCfg<true, NT_CHUNKED>::THREADS, cc);
+    else if (big && nt == 5) le = launch(HG_DIST_CTM_K(false, false, true, true, 5), TileCfg<true, 5>::THREADS, cw);
+    else if (big) le = launch(HG_DIST_CTM_K(false, false, true, true), TileCfg<true>::THREADS, cd);
+    else if (whole_k && full) le = launch(HG_DIST_CTM_K(false, true, false), TileCfg<false>::THREADS, cs);
+    else if (whole_k) le = launch(HG_DIST_CTM_K(false, false, false), TileCfg<false>::THREADS, cs);
+    else if (full) le = launch(HG_DIST_CTM_K(true, true, false), TileCfg<false>::THREADS, cs);
+    else le = launch(HG_DIST_CTM_K(true, false, false), TileCfg<false>::THREADS, cs);
+    HG_HIP(c, le);
+    return HG_OK;
+  }
   if (big_chunked) le = launch(HG_DIST_K(true, false, true, true, NT_CHUNKED), TileCfg<true, NT_CHUNKED>::THREADS, lds_chunked);
   else if (big && nt == 5) le = launch(HG_DIST_K(false, false, true, true, 5), TileCfg<true, 5>::THREADS, lds_wide);
   else if (big) le = launch(HG_DIST_K(false, false, true, true), TileCfg<true>::THREADS, lds_dma);
@@ -950,9 +1124,9 @@ __global__ void logf_kernel(const float *__restrict__ x, uint32_t first_bits, si
   if (i < n) out[i] = hg_logf(x ? x[i] : __uint_as_float(first_bits + (uint32_t)i));
 }
 __global__ void ani_from_dots_kernel(const int32_t *__restrict__ dot, const int32_t *__restrict__ nr, const int32_t *__restrict__ nq,
-                                     size_t n, float kf, float *__restrict__ out) {
+                                     size_t n, float kf, int metric, float *__restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = ani_from_dot(dot[i], nr[i], nq[i], kf);
+  if (i < n) out[i] = ani_from_dot_metric(metric, dot[i], nr[i], nq[i], kf);
 }
 }  // namespace
 
@@ -973,7 +1147,7 @@ extern "C" hg_status hg_ani_from_dots_dev(hg_ctx *c, const int32_t *d_dot, const
   if (!d_dot || !d_norm2_r || !d_norm2_q || !d_ani || ksize == 0 || n > ((size_t)1 << 32)) return hg_fail(c, HG_ERR_INVALID, "hg_ani_from_dots_dev: bad argument");
   HG_ENTER(c);
   hipLaunchKernelGGL(ani_from_dots_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_dot, d_norm2_r, d_norm2_q, n,
-                     (float)ksize, d_ani);
+                     (float)ksize, c->ani_metric, d_ani);
   HG_HIP(c, hipGetLastError());
   return HG_OK;
 }

@@ -91,6 +91,7 @@ struct hg_ctx {
   int last_ham_path = -1;       // last Hamming search: 0 xor + popcount kernel, 1 +-1 byte GEMM (i8), 2 +-1.0 e2m1 GEMM (FP4)
   std::string last_kernel[HG_T_COUNT];  // name of the last kernel launched per timing class (hg_ctx_last_kernel)
   std::string last_kernel_i8;           // ... of the last i8 operand attempt (it is the DIST kernel when the attempt was valid)
+  int ani_metric = HG_ANI_MASH;  // hg_ctx_set_ani_metric: read by every dist / cluster entry point when it is called
   int last_dist_path = -1;      // operand path of the last thresholded dist call: 0 f16 MFMA (raw values), 1 i8 MFMA, 2 integer VALU, 3 f16 MFMA on centred counts
   const void *i8_sig_ref = nullptr, *i8_sig_qry = nullptr;  // operands of the last call that took the i8 path
   uint32_t i8_sig_r = 0, i8_sig_q = 0, i8_sig_d = 0;
@@ -312,6 +313,7 @@ struct hg_dist_args {
   uint32_t hit_cap;
   float ani_th;
   int symmetric;
+  int ani_metric = HG_ANI_MASH;       // HG_ANI_*: the formula of phase 2 and the form of the pre-filter
   uint32_t ref_off = 0, qry_off = 0;  // global indices of row 0 / column 0 when the call is a block of a larger matrix
   // the reference side as prepared byte operands (hg_dist_prep_ops_dev on the GPUs that own the rows, gathered by the caller):
   // ref_hv is unused then.  ref_ops: hg_dist_ops_padded_rows(R) rows of hg_dist_ops_row_bytes(hv_d); ref_meta: R records of

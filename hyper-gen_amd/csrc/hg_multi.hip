@@ -221,6 +221,14 @@ extern "C" const char *hg_multi_peer_report(const hg_multi *m) { return m ? m->p
 extern "C" const char *hg_multi_gather_report(const hg_multi *m) { return m ? m->gather_report.c_str() : ""; }
 extern "C" int hg_multi_gather_mode(const hg_multi *m) { return m ? m->gather : -1; }
 
+extern "C" hg_status hg_multi_set_ani_metric(hg_multi *m, int metric) {
+  if (!m) return HG_ERR_INVALID;
+  if (metric != HG_ANI_MASH && metric != HG_ANI_CONTAINMENT && metric != HG_ANI_MAX_CONTAINMENT)
+    return mfail(m, HG_ERR_INVALID, "unknown ANI metric " + std::to_string(metric));
+  for (hg_ctx *c : m->ctx) c->ani_metric = metric;  // (host-side state: no device involved)
+  return HG_OK;
+}
+
 extern "C" hg_status hg_multi_set_gather(hg_multi *m, int mode) {
   if (!m) return HG_ERR_INVALID;
   if (mode == HG_GATHER_PEER) {
@@ -614,6 +622,8 @@ extern "C" hg_status hg_dist_multi_dev(hg_multi *m, const int16_t *const *d_ref_
   *n_out = 0;
   if (!d_ref_hv || !d_ref_norm2 || !ref_rows || (cap && !out)) return mfail(m, HG_ERR_INVALID, "NULL argument");
   if (d_qry_hv && (!d_qry_norm2 || !qry_rows)) return mfail(m, HG_ERR_INVALID, "query shards need norms and row counts");
+  if (symmetric && !m->ctx.empty() && m->ctx[0]->ani_metric == HG_ANI_CONTAINMENT)
+    return mfail(m, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
   const int ns = (int)m->ctx.size();
   for (int s = 0; s < ns; ++s) {  // the shards' operands may be the outputs of a sketch step still queued on their ctx
     if (hipSetDevice(m->dev[s]) != hipSuccess) return mfail(m, HG_ERR_HIP, "hipSetDevice");
@@ -650,6 +660,8 @@ extern "C" hg_status hg_dist_multi(hg_multi *m, const int16_t *ref_hv, const int
   if (R == 0 || Q == 0) return HG_OK;
   if (!ref_hv || !ref_norm2 || !qry_hv || !qry_norm2 || (cap && !out)) return mfail(m, HG_ERR_INVALID, "NULL argument");
   if (hv_d == 0) return mfail(m, HG_ERR_INVALID, "hv_d == 0");
+  if (symmetric && !m->ctx.empty() && m->ctx[0]->ani_metric == HG_ANI_CONTAINMENT)
+    return mfail(m, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
   const int ns = (int)m->ctx.size();
   const bool same = ref_hv == qry_hv && ref_norm2 == qry_norm2 && R == Q;
   const size_t row_bytes = (size_t)hv_d * sizeof(int16_t);

@@ -241,6 +241,27 @@ hg_status hg_logf_dev(hg_ctx *ctx, const float *d_x, uint32_t first_bits, size_t
 hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t *d_norm2_r, const int32_t *d_norm2_q,
                                size_t n, uint32_t ksize, float *d_ani);
 
+/* ANI metric of a ctx (no reference counterpart; the reference computes HG_ANI_MASH only, src/dist.rs:153-160).  With
+ * J = dot / (nr + nq - dot) and k = ksize, every metric is ani = 1 + ln(x) / k -> NaN to 0, clamped to [0, 1], x 100, f32
+ * arithmetic in this order and the device's logf bit for bit, where x is
+ *   HG_ANI_MASH            : 2 / (1 / J + 1)        (the default; symmetric)
+ *   HG_ANI_CONTAINMENT     : dot / nq               (the share of the QUERY's hashes found in the reference; directional)
+ *   HG_ANI_MAX_CONTAINMENT : dot / min(nr, nq)      (i32 min of the norms as passed; symmetric)
+ * Containment estimates the identity of a fragment (a partial MAG, a plasmid, a draft) with a larger genome, where J --
+ * and with it the Mash-style value -- falls with the difference in size.  With equal norms all three agree up to rounding.
+ * dot <= 0 gives 0, a zero denominator 0 (dot = 0) or 100 (dot > 0), dot > denominator 100.
+ * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
+ * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
+ * (hg_multi_set_ani_metric sets every shard's ctx), hg_cluster{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev}
+ * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev (it takes hits), hg_dist_prep_ops_dev, the
+ * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
+#define HG_ANI_MASH 0
+#define HG_ANI_CONTAINMENT 1
+#define HG_ANI_MAX_CONTAINMENT 2
+hg_status hg_ctx_set_ani_metric(hg_ctx *ctx, int metric);
+int hg_ctx_ani_metric(const hg_ctx *ctx);
+
 /* one reported pair: what dump_ani_file prints per line (src/utils.rs:275-285) */
 typedef struct {
   uint32_t ref_idx;
@@ -597,6 +618,8 @@ const char *hg_multi_peer_report(const hg_multi *m);
  * Both give the same gathered matrix, hence the same hits.  hg_multi_gather_report: how the last exchange ran. */
 enum { HG_GATHER_PEER = 0, HG_GATHER_RCCL = 1 };
 hg_status hg_multi_set_gather(hg_multi *m, int mode);
+/* hg_ctx_set_ani_metric on every shard's ctx (see there): the metric of hg_dist_multi{,_dev} */
+hg_status hg_multi_set_ani_metric(hg_multi *m, int metric);
 int hg_multi_gather_mode(const hg_multi *m);
 const char *hg_multi_gather_report(const hg_multi *m);
 /* contiguous block [*lo, *hi) of n units owned by `shard` of n_shards; sizes differ by at most one */
