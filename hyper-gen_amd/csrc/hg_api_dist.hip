@@ -70,27 +70,12 @@ extern "C" hg_status hg_dist_block_dev(hg_ctx *c, const int16_t *d_ref_hv, const
                                        hg_ani_hit *d_out, size_t cap, size_t *n_out) {
   // The kernels count hits in 32 bits.  A comparison of more than 2^32 - 1 pairs (66 000 x 66 000 and up) could report more
   // hits than that with a low threshold, so it runs as blocks of reference rows with fewer pairs each -- global indices, the
-  // i < j rule and the hit list are those of the one call; the counts add up in 64 bits, and once the caller's buffer is full
-  // the remaining blocks only count (the contract: *n_out = all hits found, HG_ERR_CAPACITY if they did not fit).
-  const uint64_t pair_limit = (c && c->dbg_pair_limit) ? c->dbg_pair_limit : 0xFFFFFFFFull;  // ("pair_limit": test hook)
-  if (c && n_out && Q && (uint64_t)R * (uint64_t)Q > pair_limit && R <= 0x7FFFFFFFull && Q <= 0x7FFFFFFFull) {
-    const size_t rows_per = std::max<size_t>(1, (size_t)(pair_limit / (uint64_t)Q));
-    size_t total = 0;
-    bool full = false;
-    *n_out = 0;
-    for (size_t r0 = 0; r0 < R; r0 += rows_per) {
-      const size_t rows = std::min(rows_per, R - r0), room = total < cap ? cap - total : 0;
-      size_t got = 0;
-      const hg_status bs = dist_block_once(c, d_ref_hv + r0 * (size_t)hv_d, d_ref_norm2 + r0, rows, ref_off + r0, d_qry_hv, d_qry_norm2, Q,
-                                           qry_off, hv_d, ksize, symmetric, ani_th, d_out ? d_out + std::min(total, cap) : nullptr, room, &got);
-      if (bs == HG_ERR_CAPACITY) full = true;
-      else if (bs != HG_OK) return bs;
-      total += got;
-    }
-    *n_out = total;
-    if (full || total > cap) return hg_fail(c, HG_ERR_CAPACITY, "hit buffer too small");
-    return HG_OK;
-  }
+  // i < j rule and the hit list are those of the one call (hg_run_blocks: the contract of *n_out and HG_ERR_CAPACITY).
+  if (c && n_out && Q && (uint64_t)R * (uint64_t)Q > hg_pair_limit(c) && R <= 0x7FFFFFFFull && Q <= 0x7FFFFFFFull)
+    return hg_run_blocks(c, R, Q, d_out, cap, n_out, [&](size_t r0, size_t rows, hg_ani_hit *out, size_t room, size_t *got) {
+      return dist_block_once(c, d_ref_hv + r0 * (size_t)hv_d, d_ref_norm2 + r0, rows, ref_off + r0, d_qry_hv, d_qry_norm2, Q, qry_off,
+                             hv_d, ksize, symmetric, ani_th, out, room, got);
+    });
   return dist_block_once(c, d_ref_hv, d_ref_norm2, R, ref_off, d_qry_hv, d_qry_norm2, Q, qry_off, hv_d, ksize, symmetric, ani_th, d_out,
                          cap, n_out);
 }
@@ -107,12 +92,11 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   if (R == 0 || Q == 0) return HG_OK;
   if (!d_ref_hv || !d_ref_norm2 || !d_qry_hv || !d_qry_norm2 || (cap && !d_out)) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
-  if ((s = hg_ensure(c, c->w_misc, 64)) != HG_OK) return s;
-  // [0] hit counter, [1] exactness verdict, [2] its window length, [4..12] control words of the i8 operand attempt
-  auto *d_count = static_cast<uint32_t *>(c->w_misc.p);
+  if ((s = hg_ensure(c, c->w_misc, HG_RES_WORDS * sizeof(uint32_t))) != HG_OK) return s;
+  auto *d_count = static_cast<uint32_t *>(c->w_misc.p);  // the result block (HG_RES_*)
   // (zeroed by the previous call on its way out, behind its read-back: one command less in front of the kernels;
   // the first call, and one after a call that failed half way, does it here)
-  if (c->misc_zeroed != d_count) HG_HIP(c, hipMemsetAsync(d_count, 0, 16 * sizeof(uint32_t), c->stream));
+  if (c->misc_zeroed != d_count) HG_HIP(c, hipMemsetAsync(d_count, 0, HG_RES_WORDS * sizeof(uint32_t), c->stream));
   c->misc_zeroed = nullptr;
   hg_dist_args a{};
   a.ref_hv = d_ref_hv, a.ref_n2 = d_ref_norm2, a.qry_hv = d_qry_hv, a.qry_n2 = d_qry_norm2;
@@ -122,21 +106,22 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   a.ani_th = ani_th, a.symmetric = symmetric, a.ani_metric = c->ani_metric;
   a.ref_off = (uint32_t)ref_off, a.qry_off = (uint32_t)qry_off;
   int spec_cover = -1;
-  if ((s = hg_run_dist(c, a, d_count + 1, &spec_cover)) != HG_OK) return s;
+  if ((s = hg_run_dist(c, a, d_count, &spec_cover)) != HG_OK) return s;
   const uint32_t *h_res = nullptr;
   // (the publishing kernel clears the control words behind the copy: they are ready for a second pass, or for the next call)
-  if ((s = hg_publish_words(c, d_count, 16, &h_res, 16)) != HG_OK) return s;
+  if ((s = hg_publish_words(c, d_count, HG_RES_WORDS, &h_res, HG_RES_WORDS)) != HG_OK) return s;
   c->misc_zeroed = d_count;
-  const bool i8_tried = h_res[9] != 0;  // the i8 prepass wrote its K-step count
-  if (i8_tried && h_res[8] != 1u) c->i8_skip = 16;  // vetoed on the device: f16 ran; do not probe again for a while
-  if (h_res[8] == 1u) {
+  const uint32_t mark = h_res[HG_RES_MARK];
+  const bool i8_tried = h_res[HG_RES_I8_KSTEPS] != 0;  // the i8 kernel wrote its K-step count
+  if (i8_tried && mark != 1u) c->i8_skip = 16;  // vetoed on the device: f16 ran; do not probe again for a while
+  if (mark == 1u) {
     c->last_dist_path = 1;
     c->last_kernel[HG_T_DIST] = c->last_kernel_i8;
     c->i8_sig_ref = d_ref_hv, c->i8_sig_qry = d_qry_hv, c->i8_sig_r = (uint32_t)R, c->i8_sig_q = (uint32_t)Q, c->i8_sig_d = hv_d;
   } else {
     c->i8_sig_ref = c->i8_sig_qry = nullptr;
   }
-  if (h_res[8] == 2u) {  // the centred f16 kernel did the work
+  if (mark == 2u) {  // the centred f16 kernel did the work
     c->last_dist_path = 3;
     c->last_kernel[HG_T_DIST] = c->last_kernel_cen;
     c->cen_sig_ref = d_ref_hv, c->cen_sig_qry = d_qry_hv, c->cen_sig_r = (uint32_t)R, c->cen_sig_q = (uint32_t)Q, c->cen_sig_d = hv_d;
@@ -145,13 +130,13 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   }
   // no guarded launch applied (or the raw f16 chain was not queued behind a trusted i8 / centred attempt that failed after
   // all): statistics-driven schedule
-  if (h_res[8] == 0u && (spec_cover == -2 || (spec_cover >= 0 && (int)h_res[1] > spec_cover))) {
+  if (mark == 0u && (spec_cover == -2 || (spec_cover >= 0 && (int)h_res[HG_RES_VERDICT] > spec_cover))) {
     c->misc_zeroed = nullptr;
     if ((s = hg_run_dist(c, a)) != HG_OK) return s;
-    if ((s = hg_publish_words(c, d_count, 16, &h_res, 16)) != HG_OK) return s;
+    if ((s = hg_publish_words(c, d_count, HG_RES_WORDS, &h_res, HG_RES_WORDS)) != HG_OK) return s;
     c->misc_zeroed = d_count;
   }
-  const uint32_t found = h_res[0];
+  const uint32_t found = h_res[HG_RES_COUNT];
   *n_out = found;
   if (found > cap) return hg_fail(c, HG_ERR_CAPACITY, "hit buffer too small");
   return HG_OK;
@@ -183,27 +168,13 @@ extern "C" hg_status hg_dist_block_ops_dev(hg_ctx *c, const uint8_t *d_ref_ops, 
                                            size_t qry_off, uint32_t hv_d, uint32_t ksize, int symmetric, float ani_th,
                                            hg_ani_hit *d_out, size_t cap, size_t *n_out) {
   // (32-bit hit counter, see hg_dist_block_dev; here the prepared reference block stays whole -- its padding rows belong to
-  // it -- and the QUERY rows go in blocks)
-  const uint64_t pair_limit = (c && c->dbg_pair_limit) ? c->dbg_pair_limit : 0xFFFFFFFFull;
-  if (c && n_out && R && (uint64_t)R * (uint64_t)Q > pair_limit && R <= 0x7FFFFFFFull && Q <= 0x7FFFFFFFull) {
-    const size_t cols_per = std::max<size_t>(1, (size_t)(pair_limit / (uint64_t)R));
-    size_t total = 0;
-    bool full = false;
-    *n_out = 0;
-    for (size_t q0 = 0; q0 < Q; q0 += cols_per) {
-      const size_t cols = std::min(cols_per, Q - q0), room = total < cap ? cap - total : 0;
-      size_t got = 0;
-      const hg_status bs = dist_block_ops_once(c, d_ref_ops, d_ref_meta, d_ref_norm2, R, ref_off, d_ref_index, d_flags, n_flags,
-                                               d_qry_hv + q0 * (size_t)hv_d, d_qry_norm2 + q0, cols, qry_off + q0, hv_d, ksize, symmetric, ani_th,
-                                               d_out ? d_out + std::min(total, cap) : nullptr, room, &got);
-      if (bs == HG_ERR_CAPACITY) full = true;
-      else if (bs != HG_OK) return bs;  // (HG_ERR_INEXACT included: the caller falls back for the whole call)
-      total += got;
-    }
-    *n_out = total;
-    if (full || total > cap) return hg_fail(c, HG_ERR_CAPACITY, "hit buffer too small");
-    return HG_OK;
-  }
+  // it -- and the QUERY rows go in blocks.  HG_ERR_INEXACT of a block ends the loop: the caller falls back for the whole call)
+  if (c && n_out && R && (uint64_t)R * (uint64_t)Q > hg_pair_limit(c) && R <= 0x7FFFFFFFull && Q <= 0x7FFFFFFFull)
+    return hg_run_blocks(c, Q, R, d_out, cap, n_out, [&](size_t q0, size_t cols, hg_ani_hit *out, size_t room, size_t *got) {
+      return dist_block_ops_once(c, d_ref_ops, d_ref_meta, d_ref_norm2, R, ref_off, d_ref_index, d_flags, n_flags,
+                                 d_qry_hv + q0 * (size_t)hv_d, d_qry_norm2 + q0, cols, qry_off + q0, hv_d, ksize, symmetric, ani_th,
+                                 out, room, got);
+    });
   return dist_block_ops_once(c, d_ref_ops, d_ref_meta, d_ref_norm2, R, ref_off, d_ref_index, d_flags, n_flags, d_qry_hv, d_qry_norm2, Q,
                              qry_off, hv_d, ksize, symmetric, ani_th, d_out, cap, n_out);
 }
@@ -223,9 +194,9 @@ static hg_status dist_block_ops_once(hg_ctx *c, const uint8_t *d_ref_ops, const 
     return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   if (d_ref_index && symmetric) return hg_fail(c, HG_ERR_UNSUPPORTED, "symmetric needs contiguous reference indices (no d_ref_index)");
   HG_ENTER(c);
-  if ((s = hg_ensure(c, c->w_misc, 64)) != HG_OK) return s;
+  if ((s = hg_ensure(c, c->w_misc, HG_RES_WORDS * sizeof(uint32_t))) != HG_OK) return s;
   auto *d_count = static_cast<uint32_t *>(c->w_misc.p);
-  if (c->misc_zeroed != d_count) HG_HIP(c, hipMemsetAsync(d_count, 0, 16 * sizeof(uint32_t), c->stream));
+  if (c->misc_zeroed != d_count) HG_HIP(c, hipMemsetAsync(d_count, 0, HG_RES_WORDS * sizeof(uint32_t), c->stream));
   c->misc_zeroed = nullptr;
   hg_dist_args a{};
   a.ref_n2 = d_ref_norm2, a.qry_hv = d_qry_hv, a.qry_n2 = d_qry_norm2;
@@ -236,12 +207,12 @@ static hg_status dist_block_ops_once(hg_ctx *c, const uint8_t *d_ref_ops, const 
   a.ref_off = (uint32_t)ref_off, a.qry_off = (uint32_t)qry_off;
   a.ref_ops = d_ref_ops, a.ref_meta = d_ref_meta, a.ref_flags = d_flags, a.n_flags = (uint32_t)n_flags, a.ref_index = d_ref_index;
   int spec = -1;
-  if ((s = hg_run_dist(c, a, d_count + 1, &spec)) != HG_OK) return s;
+  if ((s = hg_run_dist(c, a, d_count, &spec)) != HG_OK) return s;
   const uint32_t *h_res = nullptr;
-  if ((s = hg_publish_words(c, d_count, 16, &h_res, 16)) != HG_OK) return s;
+  if ((s = hg_publish_words(c, d_count, HG_RES_WORDS, &h_res, HG_RES_WORDS)) != HG_OK) return s;
   c->misc_zeroed = d_count;
-  const bool valid = h_res[8] == 1u;
-  const uint32_t found = h_res[0];
+  const bool valid = h_res[HG_RES_MARK] == 1u;
+  const uint32_t found = h_res[HG_RES_COUNT];
   c->i8_sig_ref = c->i8_sig_qry = nullptr;
   if (!valid) {
     // an owner's rows, or this call's query rows, do not fit the byte-operand scheme (mixed parity, a residual beyond a

@@ -405,23 +405,60 @@ __global__ __launch_bounds__(SK_T) void dist_skinny_kernel(const int16_t *__rest
 
 }  // namespace
 
-// the instantiation's name as a profiler prints it (hg_ctx_last_kernel: bench.py matches it against the kernel names in
-// the committed rocprofv3 summaries before it quotes their counters)
-template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool HAM = false, bool FP4 = false,
-          bool CEN = false>
-static std::string dist_kernel_name() {
-  auto b = [](bool x) { return x ? "true" : "false"; };
-  return std::string("dist_mfma_kernel<") + b(CHUNKED) + ", " + b(FULL) + ", " + b(BIG) + ", " + b(GLDS) + ", " +
-         std::to_string(NT) + ", " + b(I8) + ", " + b(HAM) + ", " + b(FP4) + ", " + b(CEN) + ">";
+// ---- host side: the tile kernels as the launch sites queue them ------------------------------------------------------
+// One instantiation, its name as a profiler prints it (hg_ctx_last_kernel: bench.py matches it against the kernel names in
+// the committed rocprofv3 summaries before it quotes their counters), its threads and its dynamic LDS (two operand stages or
+// the epilogue's candidate lists, + the tile's row / column words: dist_lds_bytes).
+struct TileKernel {
+  void (*fn)(GemmArgs);
+  std::string name;
+  int threads;
+  size_t lds;
+};
+// CTM: the geometry's dist_mfma_ctm_kernel (the containment metrics), else its dist_mfma_kernel.  Only the kernels a launch
+// site names are instantiated.
+template <bool CTM, bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool HAM = false,
+          bool FP4 = false, bool CEN = false>
+static TileKernel tile_kernel() {
+  static_assert(!CTM || (!HAM && !FP4), "the Hamming search has no ANI metric");
+  auto b = [](bool x) { return std::string(x ? "true, " : "false, "); };
+  const std::string name = std::string(CTM ? "dist_mfma_ctm_kernel<" : "dist_mfma_kernel<") + b(CHUNKED) + b(FULL) + b(BIG) + b(GLDS) +
+                           std::to_string(NT) + ", " + b(I8) + (CTM ? "" : b(HAM) + b(FP4)) + (CEN ? "true>" : "false>");
+  void (*fn)(GemmArgs);
+  if constexpr (CTM) fn = &dist_mfma_ctm_kernel<CHUNKED, FULL, BIG, GLDS, NT, I8, CEN>;
+  else fn = &dist_mfma_kernel<CHUNKED, FULL, BIG, GLDS, NT, I8, HAM, FP4, CEN>;
+  return {fn, name, TileCfg<BIG, NT>::THREADS, dist_lds_bytes<BIG, NT, GLDS, CTM>()};
 }
-#define HG_DIST_K(...) &dist_mfma_kernel<__VA_ARGS__>, dist_kernel_name<__VA_ARGS__>()
-template <bool CHUNKED, bool FULL, bool BIG, bool GLDS = false, int NT = 4, bool I8 = false, bool CEN = false>
-static std::string dist_ctm_kernel_name() {
-  auto b = [](bool x) { return x ? "true" : "false"; };
-  return std::string("dist_mfma_ctm_kernel<") + b(CHUNKED) + ", " + b(FULL) + ", " + b(BIG) + ", " + b(GLDS) + ", " +
-         std::to_string(NT) + ", " + b(I8) + ", " + b(CEN) + ">";
+// pick(std::integral_constant<bool, CTM>) for the call's metric: one ladder names a geometry's Mash-style and containment kernel
+template <class Pick>
+static TileKernel by_metric(const hg_dist_args &a, Pick pick) {
+  return a.ani_metric != HG_ANI_MASH ? pick(std::true_type{}) : pick(std::false_type{});
 }
-#define HG_DIST_CTM_K(...) &dist_mfma_ctm_kernel<__VA_ARGS__>, dist_ctm_kernel_name<__VA_ARGS__>()
+
+// Queue a tile kernel on n_tiles workgroups: its dynamic-LDS limit is raised the first time the context launches it, and its
+// name goes to *slot (nullptr: nowhere).
+static hipError_t launch_tiles(hg_ctx *c, const TileKernel &k, uint32_t n_tiles, const GemmArgs &g, std::string *slot) {
+  const void *fp = reinterpret_cast<const void *>(k.fn);
+  if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
+    const hipError_t e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k.lds);
+    if (e != hipSuccess) return e;
+    c->lds_attr_done.push_back(fp);
+  }
+  if (slot) *slot = k.name;
+  hipLaunchKernelGGL(k.fn, dim3(n_tiles), dim3(k.threads), k.lds, c->stream, g);
+  return hipGetLastError();
+}
+
+// 16-column MFMA tiles per wave of a 256-row tile: 5 (256 x 320) when the tile grid then needs fewer rounds over the CUs, a
+// round of 320-wide tiles priced at num / den of a 256-wide one; else 4.  The test hook dist_tile (hg_ctx_set_debug) forces
+// "big" (4) or "wide" (5).
+static int tile_nt(const hg_ctx *c, uint32_t R, uint32_t Q, uint64_t num, uint64_t den) {
+  if (c->dbg_dist_tile == "big") return 4;
+  if (c->dbg_dist_tile == "wide") return 5;
+  const uint64_t tm = (R + 255) / 256, ncu = (uint64_t)std::max(c->n_cu, 1);
+  const uint64_t r4 = (tm * ((Q + 255) / 256) + ncu - 1) / ncu, r5 = (tm * ((Q + 319) / 320) + ncu - 1) / ncu;
+  return r5 * num < r4 * den ? 5 : 4;
+}
 
 // ---- bit-packed Hamming search on the matrix pipe ---------------------------------------------------------------
 // bits -> +-1 bytes (bit 1 -> +1, bit 0 -> -1), one lane per 32-bit word: per nibble the four bits are spread to the
@@ -480,8 +517,7 @@ hg_status hg_run_hamming_mfma(hg_ctx *c, const uint32_t *d_ref_bits, uint32_t R,
   if (!fp4 && hv_d % 128) return hg_fail(c, HG_ERR_INVALID, "byte operands need hv_d % 128 == 0");
   // row bytes: one per dim (bytes) or half of one (e2m1), padded to whole 128-byte K-steps, pitch + 128 B (see hg_run_dist)
   const uint32_t kbytes = fp4 ? (dims / 2 + 127) / 128 * 128 : hv_d, ldkb = kbytes + 128;
-  auto padded = [](uint32_t n) { return std::max({(n + 255) / 256 * 256, (n + 319) / 320 * 320, (n + 191) / 192 * 192}); };
-  const uint32_t Rp = padded(R), Qp = padded(Q);
+  const uint32_t Rp = (uint32_t)hg_dist_ops_padded_rows_impl(R), Qp = (uint32_t)hg_dist_ops_padded_rows_impl(Q);
   hg_status s;
   if ((s = hg_ensure(c, c->w_i8a, (size_t)Rp * ldkb)) != HG_OK) return s;
   if ((s = hg_ensure(c, c->w_i8b, (size_t)Qp * ldkb)) != HG_OK) return s;
@@ -518,37 +554,17 @@ hg_status hg_run_hamming_mfma(hg_ctx *c, const uint32_t *d_ref_bits, uint32_t R,
   g.ref_off = ref_off, g.qry_off = qry_off, g.hv_d = dims;
   // dist <= max  <=>  G = D - 2*dist >= D - 2*max  (max >= D: everything is a hit)
   g.ham_thr = max_dist >= dims ? -(int32_t)dims - 1 : (int32_t)dims - 2 * (int32_t)max_dist;
-  int nt = 4;
-  {
-    const uint64_t tm = (R + 255) / 256, ncu = (uint64_t)std::max(c->n_cu, 1);
-    const uint64_t r4 = (tm * ((Q + 255) / 256) + ncu - 1) / ncu, r5 = (tm * ((Q + 319) / 320) + ncu - 1) / ncu;
-    // a 256 x 320 tile is priced at 1.25 x 0.9 of a 256 x 256 one (13 % fewer fragment bytes per MFMA; 50 000 x 10 000 x
-    // 16384 on byte operands: 5.9 ms against 6.55 at equal padded area)
-    if (r5 * 9 < r4 * 8) nt = 5;
-    if (c->dbg_dist_tile == "big") nt = 4;
-    else if (c->dbg_dist_tile == "wide") nt = 5;
-  }
+  // a 256 x 320 tile is priced at 1.25 x 0.9 of a 256 x 256 one (13 % fewer fragment bytes per MFMA; 50 000 x 10 000 x
+  // 16384 on byte operands: 5.9 ms against 6.55 at equal padded area)
+  const int nt = tile_nt(c, R, Q, 9, 8);
   g.tiles_m = (R + 255) / 256, g.tiles_n = (Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
   const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, false);
-  const size_t lds = nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>();
-  auto launch = [&](auto kern, const std::string &name, int threads) -> hipError_t {
-    c->last_kernel[HG_T_DIST] = name;
-    const void *fp = reinterpret_cast<const void *>(kern);
-    if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
-      const hipError_t e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      c->lds_attr_done.push_back(fp);
-    }
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(threads), lds, c->stream, g);
-    return hipGetLastError();
-  };
+  const TileKernel k = fp4 ? (nt == 5 ? tile_kernel<false, false, false, true, true, 5, true, true, true>()
+                                      : tile_kernel<false, false, false, true, true, 4, true, true, true>())
+                           : (nt == 5 ? tile_kernel<false, false, false, true, true, 5, true, true>()
+                                      : tile_kernel<false, false, false, true, true, 4, true, true>());
   hg_timed tg(c, HG_T_DIST);
-  hipError_t le;
-  if (fp4 && nt == 5) le = launch(HG_DIST_K(false, false, true, true, 5, true, true, true), TileCfg<true, 5>::THREADS);
-  else if (fp4) le = launch(HG_DIST_K(false, false, true, true, 4, true, true, true), TileCfg<true, 4>::THREADS);
-  else if (nt == 5) le = launch(HG_DIST_K(false, false, true, true, 5, true, true), TileCfg<true, 5>::THREADS);
-  else le = launch(HG_DIST_K(false, false, true, true, 4, true, true), TileCfg<true, 4>::THREADS);
-  HG_HIP(c, le);
+  HG_HIP(c, launch_tiles(c, k, n_tiles, g, &c->last_kernel[HG_T_DIST]));
   return HG_OK;
 }
 
@@ -587,311 +603,216 @@ static void dist_prefilter(GemmArgs &g, const hg_dist_args &a) {
   else g.pre_c = (float)((double)g.j_lo / (1.0 + (double)g.j_lo) * (1.0 - 1e-5)), g.pre_b = 0.f;
 }
 
-hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int *speculated) {
-  if (speculated) *speculated = -1;
-  const uint32_t Kp = (a.hv_d + BK - 1) / BK * BK;
-  // Row pitch of the f16 copies: Kp + 64 elements (+128 B).  With a power-of-two pitch (8 KiB at
-  // D = 4096) every workgroup reads the same 128-byte column offset of 256 different rows at the same
-  // moment, i.e. one L2 / Infinity-Cache channel; the odd 128-byte skew spreads rows over channels.
-  const uint32_t ldk = Kp + 64;
-  // padded row counts cover every tile geometry: 128- and 256-row tiles, 320-wide tiles and the 192-wide tiles of
-  // the windowed (CHUNKED) big geometry -- the LDS-DMA reads whole tiles, rows past R / Q must exist and be zero
-  auto padded = [](uint32_t n) {
-    return std::max(std::max((n + 255) / 256 * 256, (n + 319) / 320 * 320), (n + 191) / 192 * 192);
-  };
-  const uint32_t Rp = padded(a.R), Qp = padded(a.Q);
-  // ops_given: the reference side arrives as byte operands + control records prepared where the rows live
-  // (hg_dist_prep_ops_dev on the owning GPUs, gathered by the caller): no reference prepass here, and no f16 fallback --
-  // there are no i16 reference rows to fall back on; a veto comes back to the caller as HG_ERR_INEXACT
-  const bool ops_given = a.ref_ops != nullptr;
-  const bool same = !ops_given && (a.ref_hv == a.qry_hv) && (a.R == a.Q);
+// the GemmArgs fields the i8, centred and raw-value launches set alike (ani_out: nullptr on the first two, which run
+// thresholded calls only); each path sets its own behind them
+static GemmArgs dist_gemm_args(const hg_dist_args &a, const void *A, const void *B, uint32_t Kp, uint32_t ldk) {
+  GemmArgs g{};
+  g.A = static_cast<const _Float16 *>(A), g.B = static_cast<const _Float16 *>(B);
+  g.nr = a.ref_n2, g.nq = a.qry_n2, g.R = a.R, g.Q = a.Q, g.Kp = Kp, g.ldk = ldk;
+  g.chunk_steps = ~0u, g.kf = (float)a.ksize;
+  g.ani_out = a.ani_out, g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap, g.ani_th = a.ani_th;
+  g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
+  dist_prefilter(g, a);
+  return g;
+}
+
+// what the paths of one hg_run_dist call share
+struct DistOps {
+  uint32_t Kp, ldk;  // K padded to whole K-steps, the row pitch of the f16 copies (elements)
+  uint32_t Rp, Qp;   // rows of the operand copies
+  bool ops_given, same;
+  _Float16 *fa = nullptr, *fb = nullptr;  // the f16 copies (centred and raw-value paths)
+};
+
+// Zero the rows behind the last real one of the f16 copies (tiles hang over).  Neither prepass ever writes them, so the
+// raw-value chain behind the centred path and a repeat call on the same buffer and shape find them still zero.
+static hg_status zero_f16_pads(hg_ctx *c, const hg_dist_args &a, const DistOps &o) {
+  if (o.Rp > a.R && !(c->pad_a_ptr == o.fa && c->pad_a_rows == a.R && c->pad_a_ldk == o.ldk)) {
+    HG_HIP(c, hipMemsetAsync(o.fa + (size_t)a.R * o.ldk, 0, (size_t)(o.Rp - a.R) * o.ldk * 2, c->stream));
+    c->pad_a_ptr = o.fa, c->pad_a_rows = a.R, c->pad_a_ldk = o.ldk;
+  }
+  if (!o.same && o.Qp > a.Q && !(c->pad_b_ptr == o.fb && c->pad_b_rows == a.Q && c->pad_b_ldk == o.ldk)) {
+    HG_HIP(c, hipMemsetAsync(o.fb + (size_t)a.Q * o.ldk, 0, (size_t)(o.Qp - a.Q) * o.ldk * 2, c->stream));
+    c->pad_b_ptr = o.fb, c->pad_b_rows = a.Q, c->pad_b_ldk = o.ldk;
+  }
+  return HG_OK;
+}
+
+// ---- a handful of rows on one side: the streaming kernel (no operand prepass, no tiles) ---------------------------------
+// (*queued = false: the call does not qualify, nothing was queued)
+static hg_status dist_skinny(hg_ctx *c, const hg_dist_args &a, bool *queued) {
+  const bool q_small = a.Q <= a.R;
+  const uint32_t n_sml = q_small ? a.Q : a.R, n_big = q_small ? a.R : a.Q;
+  const size_t lds = (size_t)n_sml * a.hv_d * sizeof(int16_t);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(a.ref_hv) | reinterpret_cast<uintptr_t>(a.qry_hv)) & 15) == 0;
+  // (a count-only call -- no hit buffer, capacity 0: the trailing blocks of a comparison whose buffer is full -- streams too:
+  // the kernel writes a hit only below hit_cap)
+  *queued = !a.ref_ops && !a.ani_out && (a.hits || a.hit_cap == 0) && a.hit_count && n_sml >= 1 && n_sml <= SK_MAX &&
+            a.hv_d % 8 == 0 && aligned && lds <= 128 * 1024 && c->dbg_dist_path.empty() && c->dbg_dist_tile.empty();
+  if (!*queued) return HG_OK;
+  static std::atomic<uint64_t> done{0};
+  int dev = 0;
+  HG_HIP(c, hipGetDevice(&dev));
+  if (dev >= 0 && dev < 64 && !((done.load() >> dev) & 1)) {
+    HG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_skinny_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    HG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_skinny_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    done.fetch_or(1ull << dev);
+  }
+  const float kf = (float)a.ksize;
+  const uint32_t rows_per_wg = 2 * (SK_T / 64);
+  const uint32_t grid = std::min<uint32_t>((n_big + rows_per_wg - 1) / rows_per_wg, 256u * 8u);
+  hg_timed tm(c, HG_T_DIST);
+  c->last_dist_path = 2;  // exact integer dot products
+  c->last_kernel[HG_T_DIST] = q_small ? "dist_skinny_kernel<false>" : "dist_skinny_kernel<true>";
+  if (q_small)
+    hipLaunchKernelGGL(dist_skinny_kernel<false>, dim3(grid), dim3(SK_T), lds, c->stream, a.ref_hv, a.ref_n2, n_big, a.qry_hv, a.qry_n2, n_sml, a, kf);
+  else
+    hipLaunchKernelGGL(dist_skinny_kernel<true>, dim3(grid), dim3(SK_T), lds, c->stream, a.qry_hv, a.qry_n2, n_big, a.ref_hv, a.ref_n2, n_sml, a, kf);
+  HG_HIP(c, hipGetLastError());
+  return HG_OK;
+}
+
+// ---- i8 operand attempt: the prepass and the GEMM, which writes its verdict to HG_RES_MARK of the result block ----------
+static hg_status dist_i8(hg_ctx *c, const hg_dist_args &a, const DistOps &o, uint32_t *d_res) {
   hg_status s;
-  // ---- a handful of rows on one side: the streaming kernel (no operand prepass, no tiles)
+  const bool same = o.same, ops_given = o.ops_given;
+  const uint32_t kp8 = (a.hv_d + 127) / 128 * 128, ldk8 = kp8 + 128;
+  if (!ops_given && (s = hg_ensure(c, c->w_i8a, (size_t)o.Rp * ldk8)) != HG_OK) return s;
+  if (!same && (s = hg_ensure(c, c->w_i8b, (size_t)o.Qp * ldk8)) != HG_OK) return s;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // misc block: info, slot and first-entry words per row / column, the list of clamped entries: I8_ROW_SLOTS per row.
+  // (Where the path stops paying is the per-candidate corrections and the wider pre-filter slack, not the list:
+  // 10 000 x 10 000, 1.29 M hits, GEMM + prepass -- 3 333 hashes 0.40 + 0.03 ms (f16 operands 0.66 + 0.05), 4 500:
+  // 0.42 + 0.04 (0.77 + 0.04), 5 500: 0.50 + 0.04 (0.77 + 0.04), 6 000: 0.57 + 0.04 (0.75 + 0.05); beyond ~6 300
+  // hashes some row of 10 000 overflows its slots and the call runs on f16 operands.)
+  const uint32_t ent_cap = (uint32_t)(((uint64_t)a.R + (same ? 0 : a.Q)) * I8_ROW_SLOTS);
+  const size_t o_iq = al((size_t)a.R * 4), o_sr = o_iq + al((size_t)a.Q * 4), o_sq = o_sr + al((size_t)a.R * 4);
+  const size_t o_fr = o_sq + al((size_t)a.Q * 4), o_fq = o_fr + al((size_t)a.R * 4), o_list = o_fq + al((size_t)a.Q * 4);
+  if ((s = hg_ensure(c, c->w_i8misc, o_list + al((size_t)ent_cap * sizeof(I8Outlier)) + 256)) != HG_OK) return s;
+  // (prepared operands: the caller's buffer holds hg_dist_ops_padded_rows(R) rows; the rows behind R are zeroed below)
+  auto *a8 = ops_given ? reinterpret_cast<int8_t *>(const_cast<uint8_t *>(a.ref_ops)) : static_cast<int8_t *>(c->w_i8a.p);
+  auto *b8 = same ? a8 : static_cast<int8_t *>(c->w_i8b.p);
+  auto *mb = static_cast<uint8_t *>(c->w_i8misc.p);
+  auto *info_r = reinterpret_cast<int32_t *>(mb), *info_q = same ? info_r : reinterpret_cast<int32_t *>(mb + o_iq);
+  auto *slot_r = reinterpret_cast<int32_t *>(mb + o_sr), *slot_q = same ? slot_r : reinterpret_cast<int32_t *>(mb + o_sq);
+  auto *first_r = reinterpret_cast<uint32_t *>(mb + o_fr), *first_q = same ? first_r : reinterpret_cast<uint32_t *>(mb + o_fq);
+  auto *list = reinterpret_cast<I8Outlier *>(mb + o_list);
+  uint32_t *ctrl = d_res + HG_RES_I8_CTRL;  // (zeroed by the caller, read back with the hit count)
+  // The rows behind R / Q (the LDS-DMA reads whole tiles) must be zero.  The context's own operand copies keep them from
+  // call to call -- the prepass writes rows below R only --, so a repeat of the same geometry needs no memset (one or two
+  // 1 MB commands in front of the prepass of every call otherwise); a caller's buffer (prepared operands) is zeroed always.
+  auto pad_rows = [&](int side, int8_t *base, uint32_t n, uint32_t np, bool own) -> hipError_t {
+    hg_ctx::I8Pad &k = c->i8_pad[side];
+    if (own && k.ptr == base && k.rows == n && k.padded == np && k.pitch == ldk8) return hipSuccess;
+    k.ptr = nullptr;
+    if (np > n) {
+      const hipError_t e = hipMemsetAsync(base + (size_t)n * ldk8, 0, (size_t)(np - n) * ldk8, c->stream);
+      if (e != hipSuccess) return e;
+    }
+    if (own) k.ptr = base, k.rows = n, k.padded = np, k.pitch = ldk8;
+    return hipSuccess;
+  };
+  HG_HIP(c, pad_rows(0, a8, a.R, o.Rp, !ops_given));
+  if (!same) HG_HIP(c, pad_rows(1, b8, a.Q, o.Qp, true));
   {
-    const bool q_small = a.Q <= a.R;
-    const uint32_t n_sml = q_small ? a.Q : a.R, n_big = q_small ? a.R : a.Q;
-    const size_t lds = (size_t)n_sml * a.hv_d * sizeof(int16_t);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(a.ref_hv) | reinterpret_cast<uintptr_t>(a.qry_hv)) & 15) == 0;
-    // (a count-only call -- no hit buffer, capacity 0: the trailing blocks of a comparison whose buffer is full -- streams too:
-    // the kernel writes a hit only below hit_cap)
-    if (!ops_given && !a.ani_out && (a.hits || a.hit_cap == 0) && a.hit_count && n_sml >= 1 && n_sml <= SK_MAX && a.hv_d % 8 == 0 && aligned &&
-        lds <= 128 * 1024 && c->dbg_dist_path.empty() && c->dbg_dist_tile.empty()) {
-      static std::atomic<uint64_t> done{0};
-      int dev = 0;
-      HG_HIP(c, hipGetDevice(&dev));
-      if (dev >= 0 && dev < 64 && !((done.load() >> dev) & 1)) {
-        HG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_skinny_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        HG_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&dist_skinny_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        done.fetch_or(1ull << dev);
-      }
-      const float kf = (float)a.ksize;
-      const uint32_t rows_per_wg = 2 * (SK_T / 64);
-      const uint32_t grid = std::min<uint32_t>((n_big + rows_per_wg - 1) / rows_per_wg, 256u * 8u);
-      hg_timed tm(c, HG_T_DIST);
-      c->last_dist_path = 2;  // exact integer dot products
-      c->last_kernel[HG_T_DIST] = q_small ? "dist_skinny_kernel<false>" : "dist_skinny_kernel<true>";
-      if (q_small)
-        hipLaunchKernelGGL(dist_skinny_kernel<false>, dim3(grid), dim3(SK_T), lds, c->stream, a.ref_hv, a.ref_n2, n_big, a.qry_hv, a.qry_n2, n_sml, a, kf);
-      else
-        hipLaunchKernelGGL(dist_skinny_kernel<true>, dim3(grid), dim3(SK_T), lds, c->stream, a.qry_hv, a.qry_n2, n_big, a.ref_hv, a.ref_n2, n_sml, a, kf);
+    hg_timed tmp(c, HG_T_DIST_PREP);
+    if (ops_given)
+      hipLaunchKernelGGL(unpack_meta_kernel, dim3((a.R * I8_ROW_SLOTS + 255) / 256), dim3(256), 0, c->stream,
+                         static_cast<const I8RowMeta *>(a.ref_meta), a.R, info_r, slot_r, first_r, list, a.ref_flags, a.n_flags, ctrl);
+    else
+      hipLaunchKernelGGL(prep_i8_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, kp8, ldk8, a8,
+                         info_r, slot_r, first_r, list, 0u, ctrl, 0u, static_cast<I8RowMeta *>(nullptr));
+    HG_HIP(c, hipGetLastError());
+    if (!same) {
+      hipLaunchKernelGGL(prep_i8_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, c->stream, a.qry_hv, a.Q, a.hv_d, kp8, ldk8, b8,
+                         info_q, slot_q, first_q, list, a.R * I8_ROW_SLOTS, ctrl, 1u, static_cast<I8RowMeta *>(nullptr));
       HG_HIP(c, hipGetLastError());
-      return HG_OK;
     }
   }
-  // ---- i8 operand attempt (thresholded, large problems): queued first; every f16 kernel below carries its verdict
-  // word as a veto and returns at once when the i8 kernels did the work.  After a failed attempt the next few calls
-  // go straight to f16 (large sketches never qualify; probing them every time would cost ~50 us per call).
-  const uint32_t *veto = nullptr;
-  const bool i8_possible = d_verdict && !a.ani_out && a.hits && a.hv_d <= 8192 && a.hv_d % 8 == 0 &&
-                           ((uint64_t)a.R + a.Q) * I8_ROW_SLOTS < ((uint64_t)1 << 31);  // (32-bit entry indices)
-  if (ops_given && !i8_possible) return hg_fail(c, HG_ERR_UNSUPPORTED, "prepared operands: thresholded calls with hv_d <= 8192, hv_d % 8 == 0 only");
-  const bool want_i8 = ops_given || (c->dbg_dist_path != "f16" && i8_possible &&
-                                     ((uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256 || c->dbg_dist_path == "i8") &&
-                                     (c->i8_skip == 0 || c->dbg_dist_path == "i8"));
-  if (!want_i8 && c->i8_skip) --c->i8_skip;
-  if (want_i8) {
-    const uint32_t kp8 = (a.hv_d + 127) / 128 * 128, ldk8 = kp8 + 128;
-    if (!ops_given && (s = hg_ensure(c, c->w_i8a, (size_t)Rp * ldk8)) != HG_OK) return s;
-    if (!same && (s = hg_ensure(c, c->w_i8b, (size_t)Qp * ldk8)) != HG_OK) return s;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // misc block: info, slot and first-entry words per row / column, the list of clamped entries: I8_ROW_SLOTS per row.
-    // (Where the path stops paying is the per-candidate corrections and the wider pre-filter slack, not the list:
-    // 10 000 x 10 000, 1.29 M hits, GEMM + prepass -- 3 333 hashes 0.40 + 0.03 ms (f16 operands 0.66 + 0.05), 4 500:
-    // 0.42 + 0.04 (0.77 + 0.04), 5 500: 0.50 + 0.04 (0.77 + 0.04), 6 000: 0.57 + 0.04 (0.75 + 0.05); beyond ~6 300
-    // hashes some row of 10 000 overflows its slots and the call runs on f16 operands.)
-    const uint32_t ent_cap = (uint32_t)(((uint64_t)a.R + (same ? 0 : a.Q)) * I8_ROW_SLOTS);
-    const size_t o_iq = al((size_t)a.R * 4), o_sr = o_iq + al((size_t)a.Q * 4), o_sq = o_sr + al((size_t)a.R * 4);
-    const size_t o_fr = o_sq + al((size_t)a.Q * 4), o_fq = o_fr + al((size_t)a.R * 4), o_list = o_fq + al((size_t)a.Q * 4);
-    if ((s = hg_ensure(c, c->w_i8misc, o_list + al((size_t)ent_cap * sizeof(I8Outlier)) + 256)) != HG_OK) return s;
-    // (prepared operands: the caller's buffer holds hg_dist_ops_padded_rows(R) rows; the rows behind R are zeroed below)
-    auto *a8 = ops_given ? reinterpret_cast<int8_t *>(const_cast<uint8_t *>(a.ref_ops)) : static_cast<int8_t *>(c->w_i8a.p);
-    auto *b8 = same ? a8 : static_cast<int8_t *>(c->w_i8b.p);
-    auto *mb = static_cast<uint8_t *>(c->w_i8misc.p);
-    auto *info_r = reinterpret_cast<int32_t *>(mb), *info_q = same ? info_r : reinterpret_cast<int32_t *>(mb + o_iq);
-    auto *slot_r = reinterpret_cast<int32_t *>(mb + o_sr), *slot_q = same ? slot_r : reinterpret_cast<int32_t *>(mb + o_sq);
-    auto *first_r = reinterpret_cast<uint32_t *>(mb + o_fr), *first_q = same ? first_r : reinterpret_cast<uint32_t *>(mb + o_fq);
-    auto *list = reinterpret_cast<I8Outlier *>(mb + o_list);
-    uint32_t *ctrl = d_verdict + 3;  // words 4.. of the caller's result block (zeroed by the caller, read back with the hit count)
-    // The rows behind R / Q (the LDS-DMA reads whole tiles) must be zero.  The context's own operand copies keep them from
-    // call to call -- the prepass writes rows below R only --, so a repeat of the same geometry needs no memset (one or two
-    // 1 MB commands in front of the prepass of every call otherwise); a caller's buffer (prepared operands) is zeroed always.
-    auto pad_rows = [&](int side, int8_t *base, uint32_t n, uint32_t np, bool own) -> hipError_t {
-      hg_ctx::I8Pad &k = c->i8_pad[side];
-      if (own && k.ptr == base && k.rows == n && k.padded == np && k.pitch == ldk8) return hipSuccess;
-      k.ptr = nullptr;
-      if (np > n) {
-        const hipError_t e = hipMemsetAsync(base + (size_t)n * ldk8, 0, (size_t)(np - n) * ldk8, c->stream);
-        if (e != hipSuccess) return e;
-      }
-      if (own) k.ptr = base, k.rows = n, k.padded = np, k.pitch = ldk8;
-      return hipSuccess;
-    };
-    HG_HIP(c, pad_rows(0, a8, a.R, Rp, !ops_given));
-    if (!same) HG_HIP(c, pad_rows(1, b8, a.Q, Qp, true));
-    {
-      hg_timed tmp(c, HG_T_DIST_PREP);
-      if (ops_given)
-        hipLaunchKernelGGL(unpack_meta_kernel, dim3((a.R * I8_ROW_SLOTS + 255) / 256), dim3(256), 0, c->stream,
-                           static_cast<const I8RowMeta *>(a.ref_meta), a.R, info_r, slot_r, first_r, list, a.ref_flags, a.n_flags, ctrl);
-      else
-        hipLaunchKernelGGL(prep_i8_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, kp8, ldk8, a8,
-                           info_r, slot_r, first_r, list, 0u, ctrl, 0u, static_cast<I8RowMeta *>(nullptr));
-      HG_HIP(c, hipGetLastError());
-      if (!same) {
-        hipLaunchKernelGGL(prep_i8_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, c->stream, a.qry_hv, a.Q, a.hv_d, kp8, ldk8, b8,
-                           info_q, slot_q, first_q, list, a.R * I8_ROW_SLOTS, ctrl, 1u, static_cast<I8RowMeta *>(nullptr));
-        HG_HIP(c, hipGetLastError());
-      }
+  // (K and pitch in two-byte units, like the f16 operands: a K-step is 128 bytes either way)
+  GemmArgs g = dist_gemm_args(a, a8, b8, kp8 / 2, ldk8 / 2);
+  g.info_r = info_r, g.info_q = info_q, g.slot_r = slot_r, g.slot_q = slot_q, g.ents = list;
+  g.first_r = first_r, g.first_q = first_q, g.ent_cap = ent_cap, g.i8verdict = d_res + HG_RES_MARK;
+  g.raw_q = a.qry_hv, g.ref_index = a.ref_index, g.i8ctrl = ctrl, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
+  // (256 x 320 costs 1.25 x 0.9 of 256 x 256, see hg_run_hamming_mfma.  The containment metrics: 256 x 256 tiles only --
+  // with the second pre-filter word the 256 x 320 byte-operand kernel would spill, as its Mash-style sibling already does:
+  // 10 VGPRs, 44 B of scratch)
+  const int nt = a.ani_metric != HG_ANI_MASH ? 4 : tile_nt(c, a.R, a.Q, 9, 8);
+  g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
+  // (the same matrix on both sides at the same global offset: hits cluster on the diagonal -- those tiles first)
+  const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
+  const TileKernel k = by_metric(a, [&](auto ctm) {
+    if constexpr (!decltype(ctm)::value) {
+      if (nt == 5) return tile_kernel<false, false, false, true, true, 5, true>();
     }
-    GemmArgs g{};
-    g.A = reinterpret_cast<const _Float16 *>(a8), g.B = reinterpret_cast<const _Float16 *>(b8);
-    g.nr = a.ref_n2, g.nq = a.qry_n2, g.R = a.R, g.Q = a.Q;
-    g.Kp = kp8 / 2, g.ldk = ldk8 / 2;  // in two-byte units, like the f16 operands (a K-step is 128 bytes either way)
-    g.chunk_steps = ~0u, g.kf = (float)a.ksize;
-    g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap, g.ani_th = a.ani_th;
-    g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
-    dist_prefilter(g, a);
-    g.info_r = info_r, g.info_q = info_q, g.slot_r = slot_r, g.slot_q = slot_q, g.ents = list;
-    g.first_r = first_r, g.first_q = first_q, g.ent_cap = ent_cap, g.i8verdict = ctrl + 4;
-    g.raw_q = a.qry_hv, g.ref_index = a.ref_index, g.i8ctrl = ctrl, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
-    int nt = 4;
-    {
-      const uint64_t tm = (a.R + 255) / 256, ncu = (uint64_t)std::max(c->n_cu, 1);
-      const uint64_t r4 = (tm * ((a.Q + 255) / 256) + ncu - 1) / ncu, r5 = (tm * ((a.Q + 319) / 320) + ncu - 1) / ncu;
-      if (r5 * 9 < r4 * 8) nt = 5;  // (256 x 320 costs 1.25 x 0.9 of 256 x 256, see hg_run_hamming_mfma)
-      if (c->dbg_dist_tile == "big") nt = 4;
-      else if (c->dbg_dist_tile == "wide") nt = 5;
-      if (a.ani_metric != HG_ANI_MASH) nt = 4;  // (see the launch below)
-    }
-    g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
-    // (the same matrix on both sides at the same global offset: hits cluster on the diagonal -- those tiles first)
-    const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
-    const bool ctm = a.ani_metric != HG_ANI_MASH;
-    if (ctm) {
-      // (the containment metrics: the CTM epilogue on 256 x 256 tiles only -- with the second pre-filter word the
-      // 256 x 320 byte-operand kernel would spill, as its Mash-style sibling already does: 10 VGPRs, 44 B of scratch)
-      const size_t lds = dist_lds_bytes<true, 4, true, true>();
-      const void *fp = reinterpret_cast<const void *>(&dist_mfma_ctm_kernel<false, false, true, true, 4, true>);
-      if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
-        HG_HIP(c, hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        c->lds_attr_done.push_back(fp);
-      }
-      hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
-      c->last_kernel_i8 = dist_ctm_kernel_name<false, false, true, true, 4, true>();
-      hipLaunchKernelGGL((dist_mfma_ctm_kernel<false, false, true, true, 4, true>), dim3(n_tiles), dim3(TileCfg<true, 4>::THREADS), lds,
-                         c->stream, g);
-      HG_HIP(c, hipGetLastError());
-    } else {
-    const size_t lds = nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>();
-    const void *fp = nt == 5 ? reinterpret_cast<const void *>(&dist_mfma_kernel<false, false, true, true, 5, true>)
-                             : reinterpret_cast<const void *>(&dist_mfma_kernel<false, false, true, true, 4, true>);
-    if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
-      HG_HIP(c, hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      c->lds_attr_done.push_back(fp);
-    }
-    {
-      hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
-      c->last_kernel_i8 = nt == 5 ? dist_kernel_name<false, false, true, true, 5, true>() : dist_kernel_name<false, false, true, true, 4, true>();
-      if (nt == 5)
-        hipLaunchKernelGGL((dist_mfma_kernel<false, false, true, true, 5, true>), dim3(n_tiles), dim3(TileCfg<true, 5>::THREADS), lds,
-                           c->stream, g);
-      else
-        hipLaunchKernelGGL((dist_mfma_kernel<false, false, true, true, 4, true>), dim3(n_tiles), dim3(TileCfg<true, 4>::THREADS), lds,
-                           c->stream, g);
+    return tile_kernel<decltype(ctm)::value, false, false, true, true, 4, true>();
+  });
+  hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
+  HG_HIP(c, launch_tiles(c, k, n_tiles, g, &c->last_kernel_i8));
+  return HG_OK;
+}
+
+// ---- centred f16 operands: the counts c = (x + e) >> 1 as f16 are exact in ONE f32 window up to ~16 000 hashes per sketch
+// at D = 4096 (the raw values: ~4 000), so these sketches take the whole-K kernel (256 x 256 / 320 tiles, no i32 side
+// accumulators) instead of the windowed one.  `mark` (HG_RES_MARK, the i8 verdict word) says who did the work.
+static hg_status dist_cen(hg_ctx *c, const hg_dist_args &a, const DistOps &o, uint32_t *mark) {
+  hg_status s;
+  const bool same = o.same;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_iq = al((size_t)a.R * 4), o_sl = o_iq + al((size_t)a.Q * 4), o_fl = o_sl + 2 * PREP_SLOTS * sizeof(unsigned long long);
+  if ((s = hg_ensure(c, c->w_cen, o_fl + 256)) != HG_OK) return s;
+  auto *cb = static_cast<uint8_t *>(c->w_cen.p);
+  auto *info_r = reinterpret_cast<int32_t *>(cb), *info_q = same ? info_r : reinterpret_cast<int32_t *>(cb + o_iq);
+  auto *sl_r = reinterpret_cast<unsigned long long *>(cb + o_sl), *sl_q = same ? sl_r : sl_r + PREP_SLOTS;
+  auto *fail = reinterpret_cast<uint32_t *>(cb + o_fl), *cverdict = fail + 4;
+  HG_HIP(c, hipMemsetAsync(sl_r, 0, 2 * PREP_SLOTS * sizeof(unsigned long long) + 64, c->stream));
+  if ((s = zero_f16_pads(c, a, o)) != HG_OK) return s;
+  {
+    hg_timed tm(c, HG_T_DIST_PREP);
+    hipLaunchKernelGGL(prep_cen_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, o.Kp, o.ldk, o.fa, info_r,
+                       sl_r, fail, mark);
+    HG_HIP(c, hipGetLastError());
+    if (!same) {
+      hipLaunchKernelGGL(prep_cen_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, c->stream, a.qry_hv, a.Q, a.hv_d, o.Kp, o.ldk, o.fb, info_q,
+                         sl_q, fail, mark);
       HG_HIP(c, hipGetLastError());
     }
-    }
-    veto = ctrl + 4;
-    if (ops_given) {  // (nothing to fall back on: the caller reads the verdict)
-      if (speculated) *speculated = -3;
-      return HG_OK;
-    }
-    // The previous call on exactly these operands took the i8 path: the f16 fallback chain (five launches that would
-    // all return at once) is not queued again.  Should the verdict come back negative after all, the caller reruns
-    // the statistics-driven f16 schedule (*speculated == -2).
-    if (c->i8_sig_ref == a.ref_hv && c->i8_sig_qry == a.qry_hv && c->i8_sig_r == a.R && c->i8_sig_q == a.Q && c->i8_sig_d == a.hv_d) {
-      if (speculated) *speculated = -2;
-      return HG_OK;
-    }
+    hipLaunchKernelGGL(decide_cen_kernel, dim3(1), dim3(256), 0, c->stream, sl_r, sl_q, fail, cverdict, mark);
+    HG_HIP(c, hipGetLastError());
   }
-  if ((s = hg_ensure(c, c->w_f16a, (size_t)Rp * ldk * 2)) != HG_OK) return s;
-  if (!same && (s = hg_ensure(c, c->w_f16b, (size_t)Qp * ldk * 2)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_stats, 256 + 2 * PREP_SLOT_VALS * PREP_SLOTS * sizeof(unsigned long long))) != HG_OK) return s;
-  auto *fa = static_cast<_Float16 *>(c->w_f16a.p);
-  auto *fb = same ? fa : static_cast<_Float16 *>(c->w_f16b.p);
-  // ---- centred f16 operands (thresholded, large problems; sketches that byte operands cannot hold): the counts
-  // c = (x + e) >> 1 as f16 are exact in ONE f32 window up to ~16 000 hashes per sketch at D = 4096 (the raw values: ~4 000),
-  // so these sketches take the whole-K kernel (256 x 256 / 320 tiles, no i32 side accumulators) instead of the windowed one.
-  // Queued behind the i8 attempt and in front of the raw-value chain; `mark` (the i8 verdict word) says who did the work.
-  const bool want_cen = d_verdict && !a.ani_out && a.hits && a.hv_d % 8 == 0 && c->dbg_dist_path != "f16" &&
-                        ((uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256 || c->dbg_dist_path == "cen");
-  if (want_cen) {
-    uint32_t *mark = d_verdict + 7;  // = ctrl[4], the i8 attempt's verdict word (zero when no attempt was queued)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_iq = al((size_t)a.R * 4), o_sl = o_iq + al((size_t)a.Q * 4), o_fl = o_sl + 2 * PREP_SLOTS * sizeof(unsigned long long);
-    if ((s = hg_ensure(c, c->w_cen, o_fl + 256)) != HG_OK) return s;
-    auto *cb = static_cast<uint8_t *>(c->w_cen.p);
-    auto *info_r = reinterpret_cast<int32_t *>(cb), *info_q = same ? info_r : reinterpret_cast<int32_t *>(cb + o_iq);
-    auto *sl_r = reinterpret_cast<unsigned long long *>(cb + o_sl), *sl_q = same ? sl_r : sl_r + PREP_SLOTS;
-    auto *fail = reinterpret_cast<uint32_t *>(cb + o_fl), *cverdict = fail + 4;
-    HG_HIP(c, hipMemsetAsync(sl_r, 0, 2 * PREP_SLOTS * sizeof(unsigned long long) + 64, c->stream));
-    // (zero rows behind the last real one: neither prepass ever writes them, so the raw-value chain below and a repeat
-    // call on the same buffer and shape find them still zero)
-    if (Rp > a.R && !(c->pad_a_ptr == fa && c->pad_a_rows == a.R && c->pad_a_ldk == ldk)) {
-      HG_HIP(c, hipMemsetAsync(fa + (size_t)a.R * ldk, 0, (size_t)(Rp - a.R) * ldk * 2, c->stream));
-      c->pad_a_ptr = fa, c->pad_a_rows = a.R, c->pad_a_ldk = ldk;
-    }
-    if (!same && Qp > a.Q && !(c->pad_b_ptr == fb && c->pad_b_rows == a.Q && c->pad_b_ldk == ldk)) {
-      HG_HIP(c, hipMemsetAsync(fb + (size_t)a.Q * ldk, 0, (size_t)(Qp - a.Q) * ldk * 2, c->stream));
-      c->pad_b_ptr = fb, c->pad_b_rows = a.Q, c->pad_b_ldk = ldk;
-    }
-    {
-      hg_timed tm(c, HG_T_DIST_PREP);
-      hipLaunchKernelGGL(prep_cen_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, Kp, ldk, fa, info_r,
-                         sl_r, fail, mark);
-      HG_HIP(c, hipGetLastError());
-      if (!same) {
-        hipLaunchKernelGGL(prep_cen_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, c->stream, a.qry_hv, a.Q, a.hv_d, Kp, ldk, fb, info_q,
-                           sl_q, fail, mark);
-        HG_HIP(c, hipGetLastError());
-      }
-      hipLaunchKernelGGL(decide_cen_kernel, dim3(1), dim3(256), 0, c->stream, sl_r, sl_q, fail, cverdict, mark);
-      HG_HIP(c, hipGetLastError());
-    }
-    GemmArgs g{};
-    g.A = fa, g.B = fb, g.nr = a.ref_n2, g.nq = a.qry_n2, g.R = a.R, g.Q = a.Q, g.Kp = Kp, g.ldk = ldk;
-    g.chunk_steps = ~0u, g.kf = (float)a.ksize;
-    g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap, g.ani_th = a.ani_th;
-    g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
-    dist_prefilter(g, a);
-    g.info_r = info_r, g.info_q = info_q, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
-    g.verdict = cverdict, g.v_lo = 0, g.v_hi = 0, g.veto = mark;
-    int nt = 4;
-    {
-      const uint64_t tm = (a.R + 255) / 256, ncu = (uint64_t)std::max(c->n_cu, 1);
-      const uint64_t r4 = (tm * ((a.Q + 255) / 256) + ncu - 1) / ncu, r5 = (tm * ((a.Q + 319) / 320) + ncu - 1) / ncu;
-      if (r5 * 5 < r4 * 4) nt = 5;
-      if (c->dbg_dist_tile == "big") nt = 4;
-      else if (c->dbg_dist_tile == "wide") nt = 5;
-    }
-    g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
-    const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
-    const bool ctm = a.ani_metric != HG_ANI_MASH;
-    const size_t lds = ctm ? (nt == 5 ? dist_lds_bytes<true, 5, true, true>() : dist_lds_bytes<true, 4, true, true>())
-                           : (nt == 5 ? dist_lds_bytes<true, 5, true>() : dist_lds_bytes<true, 4, true>());
-    auto launch_cen = [&](auto kern, const std::string &name, int threads) -> hipError_t {
-      const void *fp = reinterpret_cast<const void *>(kern);
-      if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
-        const hipError_t e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        c->lds_attr_done.push_back(fp);
-      }
-      c->last_kernel_cen = name;
-      hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(threads), lds, c->stream, g);
-      return hipGetLastError();
-    };
-    {
-      hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
-      if (ctm)
-        HG_HIP(c, nt == 5 ? launch_cen(HG_DIST_CTM_K(false, false, true, true, 5, false, true), TileCfg<true, 5>::THREADS)
-                          : launch_cen(HG_DIST_CTM_K(false, false, true, true, 4, false, true), TileCfg<true, 4>::THREADS));
-      else
-        HG_HIP(c, nt == 5 ? launch_cen(HG_DIST_K(false, false, true, true, 5, false, false, false, true), TileCfg<true, 5>::THREADS)
-                          : launch_cen(HG_DIST_K(false, false, true, true, 4, false, false, false, true), TileCfg<true, 4>::THREADS));
-    }
-    veto = mark;
-    // the previous call on exactly these operands ran on centred operands: the raw-value chain is not queued again
-    if (c->cen_sig_ref == a.ref_hv && c->cen_sig_qry == a.qry_hv && c->cen_sig_r == a.R && c->cen_sig_q == a.Q && c->cen_sig_d == a.hv_d) {
-      if (speculated) *speculated = -2;
-      return HG_OK;
-    }
-  }
+  GemmArgs g = dist_gemm_args(a, o.fa, o.fb, o.Kp, o.ldk);
+  g.info_r = info_r, g.info_q = info_q, g.hv_d = a.hv_d, g.same_set = same ? 1u : 0u;
+  g.verdict = cverdict, g.v_lo = 0, g.v_hi = 0, g.veto = mark;
+  const int nt = tile_nt(c, a.R, a.Q, 5, 4);
+  g.tiles_m = (a.R + 255) / 256, g.tiles_n = (a.Q + (uint32_t)nt * 64 - 1) / ((uint32_t)nt * 64);
+  const uint32_t n_tiles = dist_tile_table(c, g, 256, (uint32_t)nt * 64, same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
+  const TileKernel k = by_metric(a, [&](auto ctm) {
+    return nt == 5 ? tile_kernel<decltype(ctm)::value, false, false, true, true, 5, false, false, false, true>()
+                   : tile_kernel<decltype(ctm)::value, false, false, true, true, 4, false, false, false, true>();
+  });
+  hg_timed tmg(c, HG_T_DIST, HG_T_DIST_PREP);
+  HG_HIP(c, launch_tiles(c, k, n_tiles, g, &c->last_kernel_cen));
+  return HG_OK;
+}
+
+// ---- the raw-value chain: f16 copies of the values themselves, their exact accumulation window measured by a prepass ----
+struct RawWindows {
+  int c_whole = -1;  // first candidate window that covers all of K (windows are 64 << c dims; beyond the table: none does)
+  int best_c = -1;   // the window the GEMM runs with; -1: values too large for the f16 path (the integer kernel)
+  bool spec = false, spec_win = false;  // speculative schedule; its prepass measured the 2 048- / 1 024-dim windows too
+};
+static hg_status raw_prepass(hg_ctx *c, const hg_dist_args &a, const DistOps &o, uint32_t *d_verdict, const uint32_t *veto,
+                             RawWindows &w) {
+  const bool same = o.same;
+  const uint32_t Kp = o.Kp, ldk = o.ldk;
   auto *st = static_cast<unsigned long long *>(c->w_stats.p);
-  // zero rows behind the last real one (tiles hang over); the prepass never writes them, so a repeat call
-  // on the same buffer and shape finds them still zero
-  if (Rp > a.R && !(c->pad_a_ptr == fa && c->pad_a_rows == a.R && c->pad_a_ldk == ldk)) {
-    HG_HIP(c, hipMemsetAsync(fa + (size_t)a.R * ldk, 0, (size_t)(Rp - a.R) * ldk * 2, c->stream));
-    c->pad_a_ptr = fa, c->pad_a_rows = a.R, c->pad_a_ldk = ldk;
-  }
-  if (!same && Qp > a.Q && !(c->pad_b_ptr == fb && c->pad_b_rows == a.Q && c->pad_b_ldk == ldk)) {
-    HG_HIP(c, hipMemsetAsync(fb + (size_t)a.Q * ldk, 0, (size_t)(Qp - a.Q) * ldk * 2, c->stream));
-    c->pad_b_ptr = fb, c->pad_b_rows = a.Q, c->pad_b_ldk = ldk;
-  }
   const size_t plds = (size_t)(2 * (Kp / 64) + 16 + N_CHUNK_CAND) * sizeof(unsigned long long);  // tree + maxima
-  // first candidate window that covers all of K (windows are 64 << c dims; beyond the table: none does)
-  int c_whole = -1;
-  for (int cnd = 0; cnd < N_CHUNK_CAND; ++cnd)
-    if ((64u << cnd) >= Kp) {
-      c_whole = cnd;
-      break;
-    }
+  for (int cnd = 0; cnd < N_CHUNK_CAND && w.c_whole < 0; ++cnd)
+    if ((64u << cnd) >= Kp) w.c_whole = cnd;
   unsigned long long h[2 * (1 + N_CHUNK_CAND)];
   const unsigned long long *hr = h, *hq = same ? h : h + 1 + N_CHUNK_CAND;
-  int best_c = -1;
-  bool fast_done = false, spec = false, spec_win = false;
-  (void)hr, (void)hq;
-  int spec_cover = -1;  // speculative schedule: highest verdict code with a guarded launch queued
-  if (c_whole >= 0) {  // fast prepass: max |x|, the whole-row bound and (win) the 2 048- / 1 024-dim window bounds
+  bool fast_done = false;
+  if (w.c_whole >= 0) {  // fast prepass: max |x|, the whole-row bound and (win) the 2 048- / 1 024-dim window bounds
     const size_t slot_bytes = PREP_SLOT_VALS * PREP_SLOTS * sizeof(unsigned long long);
     auto *sl = reinterpret_cast<unsigned long long *>(reinterpret_cast<uint8_t *>(st) + 256);
     auto *slq = same ? sl : sl + PREP_SLOT_VALS * PREP_SLOTS;
@@ -899,11 +820,11 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     HG_HIP(c, hipMemsetAsync(sl, 0, 2 * slot_bytes, c->stream));
     {
       hg_timed tm(c, HG_T_DIST_PREP);
-      hipLaunchKernelGGL(prep_fast_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, Kp, ldk, fa, sl, win, veto);
+      hipLaunchKernelGGL(prep_fast_kernel, dim3((a.R + 3) / 4), dim3(256), 0, c->stream, a.ref_hv, a.R, a.hv_d, Kp, ldk, o.fa, sl, win, veto);
       HG_HIP(c, hipGetLastError());
       if (!same) {
         hipLaunchKernelGGL(prep_fast_kernel, dim3((a.Q + 3) / 4), dim3(256), 0, c->stream, a.qry_hv, a.Q, a.hv_d, Kp, ldk,
-                           fb, slq, win, veto);
+                           o.fb, slq, win, veto);
         HG_HIP(c, hipGetLastError());
       }
     }
@@ -912,7 +833,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
       // it; the caller reads it back together with its hit count (no host round trip in between)
       hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(256), 0, c->stream, sl, slq, d_verdict, veto);
       HG_HIP(c, hipGetLastError());
-      best_c = c_whole, fast_done = true, spec = true, spec_win = win != 0;
+      w.best_c = w.c_whole, fast_done = true, w.spec = true, w.spec_win = win != 0;
     } else {
       hg_status ps = hg_ensure_pinned(c, 2 * slot_bytes);
       if (ps != HG_OK) return ps;
@@ -928,20 +849,20 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
       auto safe = [](unsigned long long x, unsigned long long y) {
         return x != ~0ull && y != ~0ull && (unsigned __int128)x * y <= ((unsigned __int128)1 << 48);
       };
-      if (r4[0] > 2048 || q4[0] > 2048) fast_done = true;  // no f16 path at all: integer kernel below
-      else if (safe(r4[1], q4[1])) best_c = c_whole, fast_done = true;
-      else if (safe(r4[2], q4[2])) best_c = 5, fast_done = true;  // windows of 2 048 dims (64 << 5)
-      else if (safe(r4[3], q4[3])) best_c = 4, fast_done = true;  // windows of 1 024 dims
+      if (r4[0] > 2048 || q4[0] > 2048) fast_done = true;  // no f16 path at all: integer kernel
+      else if (safe(r4[1], q4[1])) w.best_c = w.c_whole, fast_done = true;
+      else if (safe(r4[2], q4[2])) w.best_c = 5, fast_done = true;  // windows of 2 048 dims (64 << 5)
+      else if (safe(r4[3], q4[3])) w.best_c = 4, fast_done = true;  // windows of 1 024 dims
     }
   }
   if (!fast_done) {  // every candidate window (also rewrites the f16 copies: same values)
     HG_HIP(c, hipMemsetAsync(st, 0, 2 * (1 + N_CHUNK_CAND) * sizeof(unsigned long long), c->stream));
     {
       hg_timed tm(c, HG_T_DIST_PREP);
-      hipLaunchKernelGGL(prep_kernel, dim3(a.R), dim3(256), plds, c->stream, a.ref_hv, a.R, a.hv_d, Kp, ldk, fa, st);
+      hipLaunchKernelGGL(prep_kernel, dim3(a.R), dim3(256), plds, c->stream, a.ref_hv, a.R, a.hv_d, Kp, ldk, o.fa, st);
       HG_HIP(c, hipGetLastError());
       if (!same) {
-        hipLaunchKernelGGL(prep_kernel, dim3(a.Q), dim3(256), plds, c->stream, a.qry_hv, a.Q, a.hv_d, Kp, ldk, fb,
+        hipLaunchKernelGGL(prep_kernel, dim3(a.Q), dim3(256), plds, c->stream, a.qry_hv, a.Q, a.hv_d, Kp, ldk, o.fb,
                            st + 1 + N_CHUNK_CAND);
         HG_HIP(c, hipGetLastError());
       }
@@ -949,117 +870,143 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
     HG_HIP(c, hipMemcpyAsync(h, st, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HG_HIP(c, hipStreamSynchronize(c->stream));
     // largest accumulation window whose guaranteed bound sum|r||q| <= sqrt(SR*SQ) stays <= 2^24
-    if (hr[0] <= 2048 && hq[0] <= 2048) {
-      for (int cnd = N_CHUNK_CAND - 1; cnd >= 0; --cnd) {
-        const unsigned __int128 prod = (unsigned __int128)hr[1 + cnd] * hq[1 + cnd];
-        if (prod <= ((unsigned __int128)1 << 48)) {
-          best_c = cnd;
-          break;
-        }
-      }
-    }
+    if (hr[0] <= 2048 && hq[0] <= 2048)
+      for (int cnd = N_CHUNK_CAND - 1; cnd >= 0 && w.best_c < 0; --cnd)
+        if ((unsigned __int128)hr[1 + cnd] * hq[1 + cnd] <= ((unsigned __int128)1 << 48)) w.best_c = cnd;
   }
-  const float kf = (float)a.ksize;
-  hg_timed tm(c, HG_T_DIST);
-  c->last_dist_path = best_c < 0 ? 2 : 0;  // (a valid i8 attempt overrides this after the caller's read-back)
-  if (best_c < 0) {  // values too large for the f16 path: exact integer kernel
-    dim3 grid((a.Q + FB_T - 1) / FB_T, (a.R + FB_T - 1) / FB_T);
-    c->last_kernel[HG_T_DIST] = "dist_int_kernel";
-    hipLaunchKernelGGL(dist_int_kernel, grid, dim3(FB_T * FB_T), 0, c->stream, a.ref_hv, a.qry_hv, a, kf);
-    HG_HIP(c, hipGetLastError());
-    return HG_OK;
-  }
-  // one GEMM launch for accumulation windows of 64 << bc dims; guard != nullptr: runs only if
-  // v_lo <= guard[0] <= v_hi, and (from_verdict) takes its window length from guard[1]
-  auto gemm = [&](int bc, const uint32_t *guard, uint32_t v_lo, uint32_t v_hi, bool from_verdict) -> hg_status {
-  const int best_c = bc;
-  GemmArgs g{};
-  g.A = fa, g.B = fb, g.nr = a.ref_n2, g.nq = a.qry_n2;
-  g.R = a.R, g.Q = a.Q, g.Kp = Kp, g.ldk = ldk;
-  g.chunk_steps = (64u << best_c) / BK;
-  g.kf = kf;
-  g.ani_out = a.ani_out, g.hits = a.hits, g.hit_count = a.hit_count, g.hit_cap = a.hit_cap;
-  g.ani_th = a.ani_th, g.symmetric = a.symmetric, g.ref_off = a.ref_off, g.qry_off = a.qry_off;
+  return HG_OK;
+}
+
+// One GEMM launch of the raw-value chain for accumulation windows of 64 << bc dims; guard != nullptr: runs only if
+// v_lo <= guard[0] <= v_hi, and (from_verdict) takes its window length from guard[1]
+static hg_status raw_gemm(hg_ctx *c, const hg_dist_args &a, const DistOps &o, const uint32_t *veto, int bc, const uint32_t *guard,
+                          uint32_t v_lo, uint32_t v_hi, bool from_verdict) {
+  GemmArgs g = dist_gemm_args(a, o.fa, o.fb, o.Kp, o.ldk);
+  g.chunk_steps = (64u << bc) / BK;
   g.verdict = guard, g.v_lo = v_lo, g.v_hi = v_hi, g.chunk_from_verdict = from_verdict ? 1u : 0u;
   g.veto = veto;
-  dist_prefilter(g, a);
-  const bool whole_k = (64u << best_c) >= Kp;  // one window covers K: no i32 side accumulators
+  const bool whole_k = (64u << bc) >= o.Kp;  // one window covers K: no i32 side accumulators
   const bool full = a.ani_out != nullptr;
-  // big tiles when the problem fills the chip with them (Rp, Qp are multiples of 128: the last big
-  // tile may hang over by 128 rows, which the zero padding of the operand copies must cover)
-  bool big = !full && whole_k && (uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256;
-  int nt = 4;  // 16-column MFMA tiles per wave: 4 -> 256-wide tiles, 5 -> 320-wide
-  if (big) {   // the width that needs fewer rounds over the CUs (a round of 320-wide tiles costs 5/4)
-    const uint64_t tm = (a.R + 255) / 256, ncu = (uint64_t)std::max(c->n_cu, 1);
-    const uint64_t r4 = (tm * ((a.Q + 255) / 256) + ncu - 1) / ncu, r5 = (tm * ((a.Q + 319) / 320) + ncu - 1) / ncu;
-    if (r5 * 5 < r4 * 4) nt = 5;
-  }
-  if (const char *e = c->dbg_dist_tile.empty() ? nullptr : c->dbg_dist_tile.c_str()) {  // test hook (hg_ctx_set_debug): force a geometry
-    if (!std::strcmp(e, "big")) big = !full && whole_k, nt = 4;
-    else if (!std::strcmp(e, "wide")) big = !full && whole_k, nt = 5;
-    else if (!std::strcmp(e, "small")) big = false;
-  }
-  if (!big) nt = 4;
+  // big tiles when the problem fills the chip with them (Rp, Qp are multiples of 128: the last big tile may hang over by
+  // 128 rows, which the zero padding of the operand copies must cover); the test hook dist_tile (hg_ctx_set_debug) forces
+  // them ("big", "wide") or the 128 x 128 tiles ("small")
+  const std::string &hook = c->dbg_dist_tile;
+  const bool fills = hook == "big" || hook == "wide" || (hook != "small" && (uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256);
   // several exact f32 windows per row (sketches of more than ~4 000 hashes at D = 4096): the i32 side
   // accumulators double the accumulator registers, so the 256-row geometry narrows to 64 * NT_CHUNKED columns
   constexpr int NT_CHUNKED = 3;
-  bool big_chunked = !full && !whole_k && (uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256;
-  if (const char *e = c->dbg_dist_tile.empty() ? nullptr : c->dbg_dist_tile.c_str()) {
-    if (!std::strcmp(e, "small")) big_chunked = false;
-    else if (!std::strcmp(e, "big") || !std::strcmp(e, "wide")) big_chunked = !full && !whole_k;
-  }
-  if (big_chunked) big = true, nt = NT_CHUNKED;
+  const bool big_chunked = !full && !whole_k && fills, big = big_chunked || (!full && whole_k && fills);
+  // 16-column MFMA tiles per wave: 4 -> 256-wide tiles, 5 -> 320-wide (a round of 320-wide tiles costs 5/4)
+  const int nt = big_chunked ? NT_CHUNKED : big ? tile_nt(c, a.R, a.Q, 5, 4) : 4;
   const uint32_t bm = big ? 256 : 128, bn = big ? (uint32_t)nt * 64 : 128;
   g.tiles_m = (a.R + bm - 1) / bm, g.tiles_n = (a.Q + bn - 1) / bn;
   // (thresholded self-comparison: the tiles on the diagonal first, as on the i8 path)
-  const uint32_t n_tiles = dist_tile_table(c, g, bm, bn, !full && same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
-  auto launch = [&](auto kern, const std::string &name, int threads, size_t lds) -> hipError_t {
-    if (!guard || v_lo == 0) c->last_kernel[HG_T_DIST] = name;  // (a guarded second launch covers verdicts 1..2 only)
-    const void *fp = reinterpret_cast<const void *>(kern);
-    if (std::find(c->lds_attr_done.begin(), c->lds_attr_done.end(), fp) == c->lds_attr_done.end()) {
-      hipError_t e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      c->lds_attr_done.push_back(fp);
-    }
-    hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(threads), lds, c->stream, g);
-    return hipGetLastError();
-  };
-  hipError_t le;
-  // (two operand stages or the epilogue's candidate lists, + the tile's row / column words: dist_lds_bytes)
-  const size_t lds_small = dist_lds_bytes<false, 4, false>(), lds_dma = dist_lds_bytes<true, 4, true>();
-  const size_t lds_wide = dist_lds_bytes<true, 5, true>(), lds_chunked = dist_lds_bytes<true, NT_CHUNKED, true>();
+  const uint32_t n_tiles = dist_tile_table(c, g, bm, bn, !full && o.same && a.ref_off == a.qry_off && c->dbg_dist_order != "plain");
   static_assert(dist_lds_bytes<true, 5, true, true>() <= 160 * 1024, "the widest tile fits the CU's LDS");
-  if (a.ani_metric != HG_ANI_MASH) {  // the containment metrics: the same choice of tiles, the CTM epilogue (hg_dist_epilogue.h)
-    const size_t cs = dist_lds_bytes<false, 4, false, true>(), cd = dist_lds_bytes<true, 4, true, true>();
-    const size_t cw = dist_lds_bytes<true, 5, true, true>(), cc = dist_lds_bytes<true, NT_CHUNKED, true, true>();
-    if (big_chunked) le = launch(HG_DIST_CTM_K(true, false, true, true, NT_CHUNKED), TileCfg<true, NT_CHUNKED>::THREADS, cc);
-    else if (big && nt == 5) le = launch(HG_DIST_CTM_K(false, false, true, true, 5), TileCfg<true, 5>::THREADS, cw);
-    else if (big) le = launch(HG_DIST_CTM_K(false, false, true, true), TileCfg<true>::THREADS, cd);
-    else if (whole_k && full) le = launch(HG_DIST_CTM_K(false, true, false), TileCfg<false>::THREADS, cs);
-    else if (whole_k) le = launch(HG_DIST_CTM_K(false, false, false), TileCfg<false>::THREADS, cs);
-    else if (full) le = launch(HG_DIST_CTM_K(true, true, false), TileCfg<false>::THREADS, cs);
-    else le = launch(HG_DIST_CTM_K(true, false, false), TileCfg<false>::THREADS, cs);
-    HG_HIP(c, le);
-    return HG_OK;
-  }
-  if (big_chunked) le = launch(HG_DIST_K(true, false, true, true, NT_CHUNKED), TileCfg<true, NT_CHUNKED>::THREADS, lds_chunked);
-  else if (big && nt == 5) le = launch(HG_DIST_K(false, false, true, true, 5), TileCfg<true, 5>::THREADS, lds_wide);
-  else if (big) le = launch(HG_DIST_K(false, false, true, true), TileCfg<true>::THREADS, lds_dma);
-  else if (whole_k && full) le = launch(HG_DIST_K(false, true, false), TileCfg<false>::THREADS, lds_small);
-  else if (whole_k) le = launch(HG_DIST_K(false, false, false), TileCfg<false>::THREADS, lds_small);
-  else if (full) le = launch(HG_DIST_K(true, true, false), TileCfg<false>::THREADS, lds_small);
-  else le = launch(HG_DIST_K(true, false, false), TileCfg<false>::THREADS, lds_small);
-  HG_HIP(c, le);
+  // (the containment metrics: the same choice of tiles, the CTM epilogue -- hg_dist_epilogue.h)
+  const TileKernel k = by_metric(a, [&](auto ctm) {
+    constexpr bool CTM = decltype(ctm)::value;
+    if (big_chunked) return tile_kernel<CTM, true, false, true, true, NT_CHUNKED>();
+    if (big && nt == 5) return tile_kernel<CTM, false, false, true, true, 5>();
+    if (big) return tile_kernel<CTM, false, false, true, true>();
+    if (whole_k && full) return tile_kernel<CTM, false, true, false>();
+    if (whole_k) return tile_kernel<CTM, false, false, false>();
+    if (full) return tile_kernel<CTM, true, true, false>();
+    return tile_kernel<CTM, true, false, false>();
+  });
+  // (a guarded second launch covers verdicts 1..2 only: the name stays the first one's)
+  HG_HIP(c, launch_tiles(c, k, n_tiles, g, !guard || v_lo == 0 ? &c->last_kernel[HG_T_DIST] : nullptr));
   return HG_OK;
-  };
-  if (!spec) return gemm(best_c, nullptr, 0, 0, false);
+}
+
+// ---- values too large for the f16 path: the exact integer kernel ------------------------------------------------------
+static hg_status dist_int(hg_ctx *c, const hg_dist_args &a) {
+  dim3 grid((a.Q + FB_T - 1) / FB_T, (a.R + FB_T - 1) / FB_T);
+  c->last_kernel[HG_T_DIST] = "dist_int_kernel";
+  hipLaunchKernelGGL(dist_int_kernel, grid, dim3(FB_T * FB_T), 0, c->stream, a.ref_hv, a.qry_hv, a, (float)a.ksize);
+  HG_HIP(c, hipGetLastError());
+  return HG_OK;
+}
+
+// The paths in the order they are queued: the streaming kernel for a handful of rows on one side, else the i8 attempt, the
+// centred f16 attempt and the raw-value chain, each behind the one before it and vetoed by its verdict on the device.
+hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_res, int *speculated) {
+  if (speculated) *speculated = -1;
+  DistOps o;
+  o.Kp = (a.hv_d + BK - 1) / BK * BK;
+  // Row pitch of the f16 copies: Kp + 64 elements (+128 B).  With a power-of-two pitch (8 KiB at
+  // D = 4096) every workgroup reads the same 128-byte column offset of 256 different rows at the same
+  // moment, i.e. one L2 / Infinity-Cache channel; the odd 128-byte skew spreads rows over channels.
+  o.ldk = o.Kp + 64;
+  // padded row counts cover every tile geometry (the LDS-DMA reads whole tiles, rows past R / Q must exist and be zero)
+  o.Rp = (uint32_t)hg_dist_ops_padded_rows_impl(a.R), o.Qp = (uint32_t)hg_dist_ops_padded_rows_impl(a.Q);
+  // ops_given: the reference side arrives as byte operands + control records prepared where the rows live
+  // (hg_dist_prep_ops_dev on the owning GPUs, gathered by the caller): no reference prepass here, and no f16 fallback --
+  // there are no i16 reference rows to fall back on; a veto comes back to the caller as HG_ERR_INEXACT
+  o.ops_given = a.ref_ops != nullptr;
+  o.same = !o.ops_given && (a.ref_hv == a.qry_hv) && (a.R == a.Q);
+  hg_status s;
+  bool streamed;
+  if ((s = dist_skinny(c, a, &streamed)) != HG_OK || streamed) return s;
+  // ---- i8 operand attempt (thresholded, large problems): queued first; every f16 kernel below carries its verdict
+  // word as a veto and returns at once when the i8 kernels did the work.  After a failed attempt the next few calls
+  // go straight to f16 (large sketches never qualify; probing them every time would cost ~50 us per call).
+  const uint32_t *veto = nullptr;
+  const bool i8_possible = d_res && !a.ani_out && a.hits && a.hv_d <= 8192 && a.hv_d % 8 == 0 &&
+                           ((uint64_t)a.R + a.Q) * I8_ROW_SLOTS < ((uint64_t)1 << 31);  // (32-bit entry indices)
+  if (o.ops_given && !i8_possible) return hg_fail(c, HG_ERR_UNSUPPORTED, "prepared operands: thresholded calls with hv_d <= 8192, hv_d % 8 == 0 only");
+  const bool want_i8 = o.ops_given || (c->dbg_dist_path != "f16" && i8_possible &&
+                                       ((uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256 || c->dbg_dist_path == "i8") &&
+                                       (c->i8_skip == 0 || c->dbg_dist_path == "i8"));
+  if (!want_i8 && c->i8_skip) --c->i8_skip;
+  if (want_i8) {
+    if ((s = dist_i8(c, a, o, d_res)) != HG_OK) return s;
+    veto = d_res + HG_RES_MARK;
+    if (o.ops_given) {  // (nothing to fall back on: the caller reads the verdict)
+      if (speculated) *speculated = -3;
+      return HG_OK;
+    }
+    // The previous call on exactly these operands took the i8 path: the f16 fallback chain (five launches that would
+    // all return at once) is not queued again.  Should the verdict come back negative after all, the caller reruns
+    // the statistics-driven f16 schedule (*speculated == -2).
+    if (c->i8_sig_ref == a.ref_hv && c->i8_sig_qry == a.qry_hv && c->i8_sig_r == a.R && c->i8_sig_q == a.Q && c->i8_sig_d == a.hv_d) {
+      if (speculated) *speculated = -2;
+      return HG_OK;
+    }
+  }
+  if ((s = hg_ensure(c, c->w_f16a, (size_t)o.Rp * o.ldk * 2)) != HG_OK) return s;
+  if (!o.same && (s = hg_ensure(c, c->w_f16b, (size_t)o.Qp * o.ldk * 2)) != HG_OK) return s;
+  if ((s = hg_ensure(c, c->w_stats, 256 + 2 * PREP_SLOT_VALS * PREP_SLOTS * sizeof(unsigned long long))) != HG_OK) return s;
+  o.fa = static_cast<_Float16 *>(c->w_f16a.p);
+  o.fb = o.same ? o.fa : static_cast<_Float16 *>(c->w_f16b.p);
+  // ---- centred f16 operands (thresholded, large problems; sketches that byte operands cannot hold): queued behind the
+  // i8 attempt and in front of the raw-value chain
+  const bool want_cen = d_res && !a.ani_out && a.hits && a.hv_d % 8 == 0 && c->dbg_dist_path != "f16" &&
+                        ((uint64_t)a.R * a.Q >= (uint64_t)256 * 256 * 256 || c->dbg_dist_path == "cen");
+  if (want_cen) {
+    if ((s = dist_cen(c, a, o, d_res + HG_RES_MARK)) != HG_OK) return s;
+    veto = d_res + HG_RES_MARK;
+    // the previous call on exactly these operands ran on centred operands: the raw-value chain is not queued again
+    if (c->cen_sig_ref == a.ref_hv && c->cen_sig_qry == a.qry_hv && c->cen_sig_r == a.R && c->cen_sig_q == a.Q && c->cen_sig_d == a.hv_d) {
+      if (speculated) *speculated = -2;
+      return HG_OK;
+    }
+  }
+  // ---- the raw-value chain
+  uint32_t *d_verdict = d_res ? d_res + HG_RES_VERDICT : nullptr;
+  if ((s = zero_f16_pads(c, a, o)) != HG_OK) return s;
+  RawWindows w;
+  if ((s = raw_prepass(c, a, o, d_verdict, veto, w)) != HG_OK) return s;
+  hg_timed tm(c, HG_T_DIST);
+  c->last_dist_path = w.best_c < 0 ? 2 : 0;  // (a valid i8 attempt overrides this after the caller's read-back)
+  if (w.best_c < 0) return dist_int(c, a);
+  if (!w.spec) return raw_gemm(c, a, o, veto, w.best_c, nullptr, 0, 0, false);
   // speculative: the one-window kernel for verdict 0 and, where the prepass measured the 2 048 / 1 024 windows,
   // the windowed kernel for verdicts 1..2 right behind it (whichever is not chosen returns at once)
-  hg_status gs = gemm(c_whole, d_verdict, 0, 0, false);
-  if (gs != HG_OK) return gs;
-  spec_cover = 0;
-  if (spec_win && Kp > 2048) {
-    if ((gs = gemm(4, d_verdict, 1, 2, true)) != HG_OK) return gs;
+  if ((s = raw_gemm(c, a, o, veto, w.c_whole, d_verdict, 0, 0, false)) != HG_OK) return s;
+  int spec_cover = 0;  // the highest verdict code with a guarded launch queued
+  if (w.spec_win && o.Kp > 2048) {
+    if ((s = raw_gemm(c, a, o, veto, 4, d_verdict, 1, 2, true)) != HG_OK) return s;
     spec_cover = 2;
   }
   if (speculated) *speculated = spec_cover;
@@ -1069,9 +1016,7 @@ hg_status hg_run_dist(hg_ctx *c, const hg_dist_args &a, uint32_t *d_verdict, int
 // ---- operands prepared where the rows live (sharded callers) ---------------------------------------------------------
 size_t hg_dist_ops_row_bytes_impl(uint32_t hv_d) { return (size_t)((hv_d + 127) / 128 * 128) + 128; }
 size_t hg_dist_ops_meta_bytes_impl() { return sizeof(I8RowMeta); }
-size_t hg_dist_ops_padded_rows_impl(size_t n) {
-  return std::max(std::max((n + 255) / 256 * 256, (n + 319) / 320 * 320), (n + 191) / 192 * 192);
-}
+size_t hg_dist_ops_padded_rows_impl(size_t n) { return std::max({(n + 255) / 256 * 256, (n + 319) / 320 * 320, (n + 191) / 192 * 192}); }
 hg_status hg_run_dist_prep_ops(hg_ctx *c, const int16_t *d_hv, uint32_t rows, uint32_t hv_d, uint8_t *d_ops, void *d_meta,
                                uint32_t *d_flag) {
   if (hv_d > 8192 || hv_d % 8) return hg_fail(c, HG_ERR_UNSUPPORTED, "prepared operands need hv_d <= 8192, hv_d % 8 == 0");

@@ -206,25 +206,13 @@ static hg_status hamming_block_once(hg_ctx *c, const uint32_t *d_ref_bits, size_
 extern "C" hg_status hg_hamming_search_block_dev(hg_ctx *c, const uint32_t *d_ref_bits, size_t R, size_t ref_off,
                                                  const uint32_t *d_qry_bits, size_t Q, size_t qry_off, uint32_t hv_d,
                                                  uint32_t max_dist, hg_ham_hit *d_out, size_t cap, size_t *n_out) {
-  // (32-bit hit counter: more than 2^32 - 1 pairs run as blocks of reference rows, see hg_dist_block_dev)
-  const uint64_t pair_limit = (c && c->dbg_pair_limit) ? c->dbg_pair_limit : 0xFFFFFFFFull;
-  if (c && n_out && Q && (uint64_t)R * (uint64_t)Q > pair_limit) {
-    const size_t rows_per = std::max<size_t>(1, (size_t)(pair_limit / (uint64_t)Q)), words = ((size_t)hv_d + 31) / 32;
-    size_t total = 0;
-    bool full = false;
-    *n_out = 0;
-    for (size_t r0 = 0; r0 < R; r0 += rows_per) {
-      const size_t rows = std::min(rows_per, R - r0), room = total < cap ? cap - total : 0;
-      size_t got = 0;
-      const hg_status bs = hamming_block_once(c, d_ref_bits + r0 * words, rows, ref_off + r0, d_qry_bits, Q, qry_off, hv_d, max_dist,
-                                              d_out ? d_out + std::min(total, cap) : nullptr, room, &got);
-      if (bs == HG_ERR_CAPACITY) full = true;
-      else if (bs != HG_OK) return bs;
-      total += got;
-    }
-    *n_out = total;
-    if (full || total > cap) return hg_fail(c, HG_ERR_CAPACITY, "hit buffer too small");
-    return HG_OK;
+  // (32-bit hit counter: more than 2^32 - 1 pairs run as blocks of reference rows, see hg_dist_block_dev; rows of packed bits
+  // are whole 32-bit words)
+  if (c && n_out && Q && (uint64_t)R * (uint64_t)Q > hg_pair_limit(c)) {
+    const size_t words = ((size_t)hv_d + 31) / 32;
+    return hg_run_blocks(c, R, Q, d_out, cap, n_out, [&](size_t r0, size_t rows, hg_ham_hit *out, size_t room, size_t *got) {
+      return hamming_block_once(c, d_ref_bits + r0 * words, rows, ref_off + r0, d_qry_bits, Q, qry_off, hv_d, max_dist, out, room, got);
+    });
   }
   return hamming_block_once(c, d_ref_bits, R, ref_off, d_qry_bits, Q, qry_off, hv_d, max_dist, d_out, cap, n_out);
 }

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -326,15 +327,52 @@ struct hg_dist_args {
 };
 size_t hg_dist_ops_row_bytes_impl(uint32_t hv_d);
 size_t hg_dist_ops_meta_bytes_impl();
+// rows of an operand copy: a multiple of every tile's rows and columns (128, 256, 320 and the windowed geometry's 192)
 size_t hg_dist_ops_padded_rows_impl(size_t n);
 hg_status hg_run_dist_prep_ops(hg_ctx *c, const int16_t *d_hv, uint32_t rows, uint32_t hv_d, uint8_t *d_ops, void *d_meta,
                                uint32_t *d_flag);
-// d_verdict (two uint32: code, window length) != nullptr allows the speculative schedule: prepass, on-device
-// exactness verdict (0 = one f32 window covers K; 1 / 2 = windows of 2 048 / 1 024 dims; 3 = neither) and the
-// GEMM launches guarded by it are queued without a host round trip.  *speculated = -1 if the call was not
-// speculative, else the highest verdict code a guarded launch covers: the caller reads the verdict back with
-// its own results and calls again without d_verdict if it is larger.
-hg_status hg_run_dist(hg_ctx *ctx, const hg_dist_args &a, uint32_t *d_verdict = nullptr, int *speculated = nullptr);
+// The result block of a thresholded dist call: HG_RES_WORDS words of device memory, zeroed by the caller, written by the
+// kernels hg_run_dist queues and read back in one piece (hg_publish_words).
+enum : uint32_t {
+  HG_RES_COUNT = 0,      // hit counter
+  HG_RES_VERDICT = 1,    // exactness verdict of the raw-value prepass (decide_kernel) ...
+  HG_RES_WINDOW = 2,     // ... and its window length in K-steps
+  HG_RES_I8_CTRL = 4,    // control words of the i8 prepass: [0] entries reserved, [1] failure flags
+  HG_RES_MARK = 8,       // who did the work: 1 the i8 kernel, 2 the centred f16 kernel (0: neither); the later kernels' veto
+  HG_RES_I8_KSTEPS = 9,  // K-steps of the i8 attempt (!= 0: it ran)
+  HG_RES_WORDS = 16
+};
+// d_res (a result block) != nullptr allows the speculative schedule: prepass, on-device exactness verdict
+// (HG_RES_VERDICT: 0 = one f32 window covers K; 1 / 2 = windows of 2 048 / 1 024 dims; 3 = neither) and the GEMM launches
+// guarded by it are queued without a host round trip.  *speculated = -1 if the call was not speculative, else the
+// highest verdict code a guarded launch covers: the caller reads the verdict back with its own results and calls again
+// without d_res if it is larger (-2: the i8 / centred kernel was trusted and nothing guarded was queued behind it; -3:
+// prepared operands, no fallback queued).
+hg_status hg_run_dist(hg_ctx *ctx, const hg_dist_args &a, uint32_t *d_res = nullptr, int *speculated = nullptr);
+
+// The kernels count hits in 32 bits: a call of more than hg_pair_limit pairs runs as blocks of at most
+// max(1, pair_limit / other) of its `split` rows or columns, once(first, n, d_out, room, &got) each.  The counts add up
+// in 64 bits, every block writes behind the hits of the ones before it (up to cap: the blocks behind a full buffer only
+// count), *n_out = all hits found, HG_ERR_CAPACITY once all blocks ran if they did not fit; any other error ends the loop.
+inline uint64_t hg_pair_limit(const hg_ctx *c) { return c->dbg_pair_limit ? c->dbg_pair_limit : 0xFFFFFFFFull; }
+template <class Hit, class Once>
+hg_status hg_run_blocks(hg_ctx *c, size_t split, size_t other, Hit *d_out, size_t cap, size_t *n_out, Once once) {
+  const size_t per = std::max<size_t>(1, (size_t)(hg_pair_limit(c) / (uint64_t)other));
+  size_t total = 0;
+  bool full = false;
+  *n_out = 0;
+  for (size_t i0 = 0; i0 < split; i0 += per) {
+    const size_t n = std::min(per, split - i0), room = total < cap ? cap - total : 0;
+    size_t got = 0;
+    const hg_status bs = once(i0, n, d_out ? d_out + std::min(total, cap) : nullptr, room, &got);
+    if (bs == HG_ERR_CAPACITY) full = true;
+    else if (bs != HG_OK) return bs;
+    total += got;
+  }
+  *n_out = total;
+  if (full || total > cap) return hg_fail(c, HG_ERR_CAPACITY, "hit buffer too small");
+  return HG_OK;
+}
 
 // Bit-packed Hamming search as an exact GEMM on the matrix pipe (+-1 operands expanded from the bits -- e2m1 nibbles
 // for v_mfma_scale_f32_16x16x128_f8f6f4 or bytes for v_mfma_i32_16x16x64_i8; the ANI GEMM's tiles, LDS-DMA staging and
