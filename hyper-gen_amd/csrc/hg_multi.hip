@@ -101,8 +101,8 @@ struct hg_multi {
     hg_ctx::Buf mine, mine_n2;    // this shard's uploaded reference rows (host entry points)
     hg_ctx::Buf qry, qry_n2;      // this shard's query rows (host entry points)
     hg_ctx::Buf hits;             // per-shard hit list
-    // the exchange of PREPARED operands (dist_core_ops): this shard's own rows as byte operands + control records + flag
-    // word, and what it gathers from all owners
+    // the byte form's exchange of PREPARED operands (dist_form): this shard's own rows as byte operands + control records +
+    // flag word, and what it gathers from all owners
     hg_ctx::Buf ops_mine, meta_mine, flag_mine, ops_all, meta_all, flags_all;
     hipEvent_t ready = nullptr;   // "this shard's published rows are complete"
   };
@@ -319,76 +319,82 @@ struct DrainOnExit {
   ~DrainOnExit() { drain(m); }
 };
 
-// the exchange step: every shard's gathered matrix g_hv[s] / g_n2[s] receives all owners' row blocks
-hg_status gather_refs(hg_multi *m, const int16_t *const *d_ref, const int32_t *const *d_rn, const DistPlan &pl,
-                      uint32_t hv_d, const std::vector<int16_t *> &g_hv, const std::vector<int32_t *> &g_n2) {
+bool rccl_mode(const hg_multi *m) { return m->gather == HG_GATHER_RCCL && !m->comm.empty(); }
+bool equal_blocks(const DistPlan &pl) {
+  for (size_t t = 1; t < pl.rlo.size(); ++t)
+    if (pl.rhi[t] - pl.rlo[t] != pl.rhi[0] - pl.rlo[0]) return false;
+  return true;
+}
+
+// One array of the exchange step.  Owner t contributes its reference rows -- or, `one_each`, one unit (the byte form's flag
+// word) -- of `unit` bytes at src[t]; receiver s holds owner t's block at dst[s] + first(t) * unit, first(t) being the units
+// of the owners before t.
+struct GatherArray {
+  std::vector<const void *> src;  // per owner
+  std::vector<void *> dst;        // per receiver
+  size_t unit;
+  bool one_each = false;
+};
+
+// The exchange step: every receiver gets every owner's block of every array.  Receivers are the shards with query columns;
+// under RCCL every rank takes part in the collectives, so every shard's dst must be valid there.  Each receiver's stream
+// first waits for every other owner's published data, so what the caller queues behind the exchange may read the owners'
+// rows as well.  *cross += the bytes pulled between distinct devices.
+hg_status exchange(hg_multi *m, const DistPlan &pl, const std::vector<GatherArray> &arrs, size_t *cross) {
   const int ns = (int)m->ctx.size();
-  const size_t row_bytes = (size_t)hv_d * sizeof(int16_t);
-  if (m->gather == HG_GATHER_RCCL && !m->comm.empty()) {
-    const RcclApi &r = rccl();
-    bool equal = true;
-    for (int t = 1; t < ns; ++t) equal = equal && (pl.rhi[t] - pl.rlo[t]) == (pl.rhi[0] - pl.rlo[0]);
-    ncclResult_t e = r.GroupStart();
-    for (int s = 0; s < ns && e == ncclSuccess; ++s) {
-      if (!g_hv[s]) continue;  // (a shard without query rows still has to take part: see the caller)
-      if (hipSetDevice(m->dev[s]) != hipSuccess) {  // (no return inside the group: GroupEnd below closes it on every path)
-        e = ncclSystemError;
-        break;
-      }
-      hipStream_t st = m->ctx[s]->stream;
-      if (equal) {
-        const size_t rows = pl.rhi[s] - pl.rlo[s];
-        e = r.AllGather(d_ref[s], g_hv[s], rows * row_bytes, ncclUint8, m->comm[s], st);
-        if (e == ncclSuccess) e = r.AllGather(d_rn[s], g_n2[s], rows * sizeof(int32_t), ncclUint8, m->comm[s], st);
-      } else {
-        for (int t = 0; t < ns && e == ncclSuccess; ++t) {
-          const size_t rows = pl.rhi[t] - pl.rlo[t];
-          if (!rows) continue;
-          e = r.Broadcast(d_ref[s], g_hv[s] + pl.rlo[t] * (size_t)hv_d, rows * row_bytes, ncclUint8, t, m->comm[s], st);
-          if (e == ncclSuccess)
-            e = r.Broadcast(d_rn[s], g_n2[s] + pl.rlo[t], rows * sizeof(int32_t), ncclUint8, t, m->comm[s], st);
-        }
-      }
-    }
-    const ncclResult_t e2 = r.GroupEnd();
-    if (e == ncclSuccess) e = e2;
-    if (e != ncclSuccess) return mfail(m, HG_ERR_HIP, std::string("RCCL all-gather: ") + r.GetErrorString(e));
-    int ver = 0;
-    (void)r.GetVersion(&ver);
-    m->gather_report = std::string("rccl ") + (equal ? "ncclAllGather" : "grouped ncclBroadcast") + " over " +
-                       std::to_string(ns) + " ranks, " + std::to_string(pl.R * row_bytes) + " B, version " + std::to_string(ver);
-    return HG_OK;
-  }
-  // direct pulls: one copy per peer block, all queued at once on the puller's stream
-  for (int s = 0; s < ns; ++s) {
+  const bool use_rccl = rccl_mode(m);
+  auto count = [&](const GatherArray &a, int t) { return a.one_each ? size_t(1) : pl.rhi[t] - pl.rlo[t]; };
+  auto block = [&](const GatherArray &a, int s, int t) {
+    return static_cast<uint8_t *>(a.dst[s]) + (a.one_each ? (size_t)t : pl.rlo[t]) * a.unit;
+  };
+  for (int s = 0; s < ns; ++s)
     if (hipSetDevice(m->dev[s]) != hipSuccess || hipEventRecord(m->sh[s].ready, m->ctx[s]->stream) != hipSuccess)
       return mfail(m, HG_ERR_HIP, "hg_dist_multi: event record failed");
-  }
-  size_t peer_bytes = 0;
+  // each receiver waits for the other owners; the direct pulls: one copy per (array, owner), all queued at once on its stream
   for (int s = 0; s < ns; ++s) {
-    if (!g_hv[s]) continue;
+    if (pl.chi[s] == pl.clo[s]) continue;
     hg_ctx *c = m->ctx[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
-    for (int t = 0; t < ns; ++t) {
-      const size_t rows = pl.rhi[t] - pl.rlo[t];
-      if (!rows) continue;
+    for (int t = 0; t < ns; ++t)
       if (t != s) HG_HIP(c, hipStreamWaitEvent(c->stream, m->sh[t].ready, 0));
-      HG_HIP(c, peer_copy(m, s, g_hv[s] + pl.rlo[t] * (size_t)hv_d, t, d_ref[t], rows * row_bytes));
-      HG_HIP(c, peer_copy(m, s, g_n2[s] + pl.rlo[t], t, d_rn[t], rows * sizeof(int32_t)));
-      if (m->dev[s] != m->dev[t]) peer_bytes += rows * row_bytes;
+    if (use_rccl) continue;
+    for (const GatherArray &a : arrs)
+      for (int t = 0; t < ns; ++t) {
+        const size_t bytes = count(a, t) * a.unit;
+        HG_HIP(c, peer_copy(m, s, block(a, s, t), t, a.src[t], bytes));
+        if (m->dev[s] != m->dev[t]) *cross += bytes;
+      }
+  }
+  if (!use_rccl) return HG_OK;
+  // RCCL: ncclAllGather of equal blocks, one ncclBroadcast per non-empty owner otherwise (the all-gather-v idiom)
+  const RcclApi &r = rccl();
+  const bool equal = equal_blocks(pl);
+  ncclResult_t e = r.GroupStart();
+  for (int s = 0; s < ns && e == ncclSuccess; ++s) {
+    if (hipSetDevice(m->dev[s]) != hipSuccess) e = ncclSystemError;  // (no return inside the group: GroupEnd closes it)
+    const hipStream_t st = m->ctx[s]->stream;
+    for (size_t i = 0; i < arrs.size() && e == ncclSuccess; ++i) {
+      const GatherArray &a = arrs[i];
+      if (a.one_each || equal)
+        e = r.AllGather(a.src[s], a.dst[s], count(a, s) * a.unit, ncclUint8, m->comm[s], st);
+      else
+        for (int t = 0; t < ns && e == ncclSuccess; ++t)
+          if (count(a, t)) e = r.Broadcast(a.src[s], block(a, s, t), count(a, t) * a.unit, ncclUint8, t, m->comm[s], st);
     }
   }
-  m->gather_report = "peer pulls (hipMemcpyPeerAsync), " + std::to_string(peer_bytes) + " B between distinct devices; " +
-                     m->peer_report;
+  const ncclResult_t e2 = r.GroupEnd();
+  if (e == ncclSuccess) e = e2;
+  if (e != ncclSuccess) return mfail(m, HG_ERR_HIP, std::string("RCCL all-gather: ") + r.GetErrorString(e));
   return HG_OK;
 }
 
 // shard lists back to back into the caller's buffer (hit order is unspecified by contract)
-hg_status merge_hits(hg_multi *m, const std::vector<size_t> &found, hg_status st, hg_ani_hit *out, size_t cap, size_t *n_out) {
+template <class Hit>
+hg_status merge_hits(hg_multi *m, const std::vector<size_t> &found, hg_status st, Hit *out, size_t cap, size_t *n_out) {
   const int ns = (int)m->ctx.size();
   size_t total = 0;
   for (int s = 0; s < ns; ++s) total += found[s];
-  if (n_out) *n_out = total;
+  *n_out = total;
   if (st != HG_OK && st != HG_ERR_CAPACITY) return st;
   if (total > cap) return mfail(m, HG_ERR_CAPACITY, "hit buffer too small");
   size_t at = 0;
@@ -396,7 +402,7 @@ hg_status merge_hits(hg_multi *m, const std::vector<size_t> &found, hg_status st
     if (!found[s]) continue;
     hg_ctx *c = m->ctx[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
-    HG_HIP(c, hipMemcpyAsync(out + at, m->sh[s].hits.p, found[s] * sizeof(hg_ani_hit), hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipMemcpyAsync(out + at, m->sh[s].hits.p, found[s] * sizeof(Hit), hipMemcpyDeviceToHost, c->stream));
     at += found[s];
   }
   for (int s = 0; s < ns; ++s) {
@@ -406,140 +412,119 @@ hg_status merge_hits(hg_multi *m, const std::vector<size_t> &found, hg_status st
   return HG_OK;
 }
 
-// The exchange of PREPARED operands: every shard converts its own reference rows to centred byte operands + 72-byte
-// control records once (hg_dist_prep_ops_dev), and the peers pull those -- 4.3 KB per row at D = 4096 instead of 8 KB of
-// i16, and no shard repeats another shard's prepass.  In the all-vs-all case a shard additionally pulls the i16 rows of
-// its QUERY range that it does not own itself (under `symmetric` the column ranges are balanced by pair count and do not
-// coincide with the row blocks).  Returns HG_ERR_INEXACT, with nothing reported, when an owner's or a query side's rows
-// do not fit the byte scheme: dist_core then runs the i16 exchange.
-hg_status dist_core_ops(hg_multi *m, const int16_t *const *d_ref, const int32_t *const *d_rn, const int16_t *const *d_qry,
-                        const int32_t *const *d_qn, const DistPlan &pl, uint32_t hv_d, uint32_t ksize, int symmetric,
-                        float ani_th, hg_ani_hit *out, size_t cap, size_t *n_out) {
+// One form of the exchange + compute.  The byte form (`ops`) exchanges PREPARED operands: every shard converts its own
+// reference rows to centred byte operands + 72-byte control records once (hg_dist_prep_ops_dev), and the receivers gather
+// those -- 4.3 KB per row at D = 4096 instead of 8 KB of i16, and no shard repeats another shard's prepass.  In the
+// all-vs-all case a shard then pulls the i16 rows of its QUERY range from their owners (under `symmetric` the column ranges
+// are balanced by pair count and do not coincide with the row blocks).  It returns HG_ERR_INEXACT, with nothing reported,
+// when an owner's or a query side's rows do not fit the byte scheme.  The i16 form gathers the rows themselves.
+hg_status dist_form(hg_multi *m, bool ops, const int16_t *const *d_ref, const int32_t *const *d_rn, const int16_t *const *d_qry,
+                    const int32_t *const *d_qn, const DistPlan &pl, uint32_t hv_d, uint32_t ksize, int symmetric, float ani_th,
+                    hg_ani_hit *out, size_t cap, size_t *n_out) {
+  using Shard = hg_multi::Shard;
   const int ns = (int)m->ctx.size();
   const size_t rb = hg_dist_ops_row_bytes(hv_d), mb = hg_dist_ops_meta_bytes(), row16 = (size_t)hv_d * sizeof(int16_t);
+  const bool use_rccl = rccl_mode(m);
   std::vector<size_t> found(ns, 0), caps(ns, 0);
-  const bool rccl_mode = m->gather == HG_GATHER_RCCL && !m->comm.empty();
-  // phase 1 (one thread per shard): workspaces, and the shard's own rows prepared on its stream
+  // phase 1 (one thread per shard): workspaces, and in the byte form the shard's own rows prepared on its stream
   hg_status st = for_each_shard(m, [&](int s) -> hg_status {
     hg_ctx *c = m->ctx[s];
-    hg_multi::Shard &x = m->sh[s];
+    Shard &x = m->sh[s];
     const size_t rows = pl.rhi[s] - pl.rlo[s], qn_rows = pl.chi[s] - pl.clo[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
     hg_status e;
-    if ((e = hg_ensure(c, x.ops_mine, rows * rb + 64)) != HG_OK) return e;
-    if ((e = hg_ensure(c, x.meta_mine, rows * mb + 64)) != HG_OK) return e;
-    if ((e = hg_ensure(c, x.flag_mine, 64)) != HG_OK) return e;
-    if (qn_rows || rccl_mode) {
-      if ((e = hg_ensure(c, x.ops_all, hg_dist_ops_padded_rows(pl.R) * rb + 64)) != HG_OK) return e;
-      if ((e = hg_ensure(c, x.meta_all, pl.R * mb + 64)) != HG_OK) return e;
+    if (qn_rows || use_rccl) {  // the gathered arrays
+      if (ops) {
+        if ((e = hg_ensure(c, x.ops_all, hg_dist_ops_padded_rows(pl.R) * rb + 64)) != HG_OK) return e;
+        if ((e = hg_ensure(c, x.meta_all, pl.R * mb + 64)) != HG_OK) return e;
+        if ((e = hg_ensure(c, x.flags_all, (size_t)ns * sizeof(uint32_t) + 64)) != HG_OK) return e;
+      } else if ((e = hg_ensure(c, x.ref_all, pl.R * row16 + 64)) != HG_OK) {
+        return e;
+      }
       if ((e = hg_ensure(c, x.n2_all, pl.R * sizeof(int32_t) + 64)) != HG_OK) return e;
-      if ((e = hg_ensure(c, x.flags_all, (size_t)ns * sizeof(uint32_t) + 64)) != HG_OK) return e;
     }
+    // capacity of this shard's list: its share of the caller's capacity can be exceeded by a skewed hit
+    // distribution, so it gets the whole `cap`, bounded by its pair count
+    caps[s] = (size_t)std::min<unsigned __int128>((unsigned __int128)pl.R * qn_rows, cap);
+    if ((e = hg_ensure(c, x.hits, caps[s] * sizeof(hg_ani_hit) + 64)) != HG_OK) return e;
+    if (!ops) return HG_OK;
     if (!d_qry && qn_rows) {  // all-vs-all: this shard's query rows, assembled below
       if ((e = hg_ensure(c, x.qry, qn_rows * row16 + 64)) != HG_OK) return e;
       if ((e = hg_ensure(c, x.qry_n2, qn_rows * sizeof(int32_t) + 64)) != HG_OK) return e;
     }
-    const unsigned __int128 pairs = (unsigned __int128)pl.R * qn_rows;
-    caps[s] = (size_t)std::min<unsigned __int128>(pairs, cap);
-    if ((e = hg_ensure(c, x.hits, caps[s] * sizeof(hg_ani_hit) + 64)) != HG_OK) return e;
+    if ((e = hg_ensure(c, x.ops_mine, rows * rb + 64)) != HG_OK) return e;
+    if ((e = hg_ensure(c, x.meta_mine, rows * mb + 64)) != HG_OK) return e;
+    if ((e = hg_ensure(c, x.flag_mine, 64)) != HG_OK) return e;
     HG_HIP(c, hipMemsetAsync(x.flag_mine.p, 0, 16, c->stream));
-    if (rows)
-      return hg_dist_prep_ops_dev(c, d_ref[s], rows, hv_d, static_cast<uint8_t *>(x.ops_mine.p), static_cast<uint8_t *>(x.meta_mine.p),
-                                  static_cast<uint32_t *>(x.flag_mine.p));
-    return HG_OK;
+    return hg_dist_prep_ops_dev(c, d_ref[s], rows, hv_d, static_cast<uint8_t *>(x.ops_mine.p), static_cast<uint8_t *>(x.meta_mine.p),
+                                static_cast<uint32_t *>(x.flag_mine.p));
   });
   if (st != HG_OK) return st;
-  // phase 2 (this thread): the exchange, queued on the pullers' streams behind the owners' "ready" events
-  size_t peer_bytes = 0;
-  bool equal = true;
-  for (int t = 1; t < ns; ++t) equal = equal && (pl.rhi[t] - pl.rlo[t]) == (pl.rhi[0] - pl.rlo[0]);
-  if (rccl_mode) {
-    const RcclApi &r = rccl();
-    ncclResult_t e = r.GroupStart();
-    for (int s = 0; s < ns && e == ncclSuccess; ++s) {
-      if (hipSetDevice(m->dev[s]) != hipSuccess) {
-        e = ncclSystemError;
-        break;
-      }
-      hg_multi::Shard &x = m->sh[s];
-      hipStream_t stq = m->ctx[s]->stream;
-      auto *oa = static_cast<uint8_t *>(x.ops_all.p), *ma = static_cast<uint8_t *>(x.meta_all.p);
-      auto *na = static_cast<int32_t *>(x.n2_all.p);
-      auto *fa = static_cast<uint32_t *>(x.flags_all.p);
-      if (equal) {
-        const size_t rows = pl.rhi[s] - pl.rlo[s];
-        e = r.AllGather(x.ops_mine.p, oa, rows * rb, ncclUint8, m->comm[s], stq);
-        if (e == ncclSuccess) e = r.AllGather(x.meta_mine.p, ma, rows * mb, ncclUint8, m->comm[s], stq);
-        if (e == ncclSuccess) e = r.AllGather(d_rn[s], na, rows * sizeof(int32_t), ncclUint8, m->comm[s], stq);
-      } else {
-        for (int t = 0; t < ns && e == ncclSuccess; ++t) {
-          const size_t rows = pl.rhi[t] - pl.rlo[t];
-          if (!rows) continue;
-          e = r.Broadcast(x.ops_mine.p, oa + pl.rlo[t] * rb, rows * rb, ncclUint8, t, m->comm[s], stq);
-          if (e == ncclSuccess) e = r.Broadcast(x.meta_mine.p, ma + pl.rlo[t] * mb, rows * mb, ncclUint8, t, m->comm[s], stq);
-          if (e == ncclSuccess) e = r.Broadcast(d_rn[s], na + pl.rlo[t], rows * sizeof(int32_t), ncclUint8, t, m->comm[s], stq);
-        }
-      }
-      if (e == ncclSuccess) e = r.AllGather(x.flag_mine.p, fa, sizeof(uint32_t), ncclUint8, m->comm[s], stq);
-    }
-    const ncclResult_t e2 = r.GroupEnd();
-    if (e == ncclSuccess) e = e2;
-    if (e != ncclSuccess) return mfail(m, HG_ERR_HIP, std::string("RCCL all-gather: ") + r.GetErrorString(e));
-  }
-  for (int s = 0; s < ns; ++s)
-    if (hipSetDevice(m->dev[s]) != hipSuccess || hipEventRecord(m->sh[s].ready, m->ctx[s]->stream) != hipSuccess)
-      return mfail(m, HG_ERR_HIP, "hg_dist_multi: event record failed");
-  for (int s = 0; s < ns; ++s) {
-    const size_t qn_rows = pl.chi[s] - pl.clo[s];
-    if (!qn_rows) continue;
+  // phase 2 (this thread): the exchange, queued on the receivers' streams behind the owners' "ready" events
+  auto mine = [&](hg_ctx::Buf Shard::*b) { std::vector<const void *> v; for (Shard &x : m->sh) v.push_back((x.*b).p); return v; };
+  auto all = [&](hg_ctx::Buf Shard::*b) { std::vector<void *> v; for (Shard &x : m->sh) v.push_back((x.*b).p); return v; };
+  const std::vector<const void *> ref(d_ref, d_ref + ns), rn(d_rn, d_rn + ns);
+  std::vector<GatherArray> arrs;
+  if (ops)
+    arrs = {{mine(&Shard::ops_mine), all(&Shard::ops_all), rb},
+            {mine(&Shard::meta_mine), all(&Shard::meta_all), mb},
+            {rn, all(&Shard::n2_all), sizeof(int32_t)},
+            {mine(&Shard::flag_mine), all(&Shard::flags_all), sizeof(uint32_t), true}};
+  else
+    arrs = {{ref, all(&Shard::ref_all), row16}, {rn, all(&Shard::n2_all), sizeof(int32_t)}};
+  size_t cross = 0;
+  if ((st = exchange(m, pl, arrs, &cross)) != HG_OK) return st;
+  for (int s = 0; s < ns && ops && !d_qry; ++s) {  // all-vs-all byte form: the part of s's query range that owner t holds
     hg_ctx *c = m->ctx[s];
-    hg_multi::Shard &x = m->sh[s];
+    Shard &x = m->sh[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
     for (int t = 0; t < ns; ++t) {
-      const size_t rows = pl.rhi[t] - pl.rlo[t];
-      if (!rows) continue;
-      if (t != s) HG_HIP(c, hipStreamWaitEvent(c->stream, m->sh[t].ready, 0));
-      if (!rccl_mode) {
-        HG_HIP(c, peer_copy(m, s, static_cast<uint8_t *>(x.ops_all.p) + pl.rlo[t] * rb, t, m->sh[t].ops_mine.p, rows * rb));
-        HG_HIP(c, peer_copy(m, s, static_cast<uint8_t *>(x.meta_all.p) + pl.rlo[t] * mb, t, m->sh[t].meta_mine.p, rows * mb));
-        HG_HIP(c, peer_copy(m, s, static_cast<int32_t *>(x.n2_all.p) + pl.rlo[t], t, d_rn[t], rows * sizeof(int32_t)));
-        HG_HIP(c, peer_copy(m, s, static_cast<uint32_t *>(x.flags_all.p) + t, t, m->sh[t].flag_mine.p, sizeof(uint32_t)));
-        if (m->dev[s] != m->dev[t]) peer_bytes += rows * (rb + mb + 4);
-      }
-      if (!d_qry) {  // all-vs-all: the part of this shard's query range that owner t holds, as i16 rows
-        const size_t lo = std::max(pl.clo[s], pl.rlo[t]), hi = std::min(pl.chi[s], pl.rhi[t]);
-        if (lo < hi) {
-          HG_HIP(c, peer_copy(m, s, static_cast<int16_t *>(x.qry.p) + (lo - pl.clo[s]) * (size_t)hv_d, t,
-                              d_ref[t] + (lo - pl.rlo[t]) * (size_t)hv_d, (hi - lo) * row16));
-          HG_HIP(c, peer_copy(m, s, static_cast<int32_t *>(x.qry_n2.p) + (lo - pl.clo[s]), t, d_rn[t] + (lo - pl.rlo[t]),
-                              (hi - lo) * sizeof(int32_t)));
-          if (m->dev[s] != m->dev[t]) peer_bytes += (hi - lo) * (row16 + 4);
-        }
-      }
+      const size_t lo = std::max(pl.clo[s], pl.rlo[t]), hi = std::min(pl.chi[s], pl.rhi[t]);
+      if (lo >= hi) continue;
+      HG_HIP(c, peer_copy(m, s, static_cast<int16_t *>(x.qry.p) + (lo - pl.clo[s]) * (size_t)hv_d, t,
+                          d_ref[t] + (lo - pl.rlo[t]) * (size_t)hv_d, (hi - lo) * row16));
+      HG_HIP(c, peer_copy(m, s, static_cast<int32_t *>(x.qry_n2.p) + (lo - pl.clo[s]), t, d_rn[t] + (lo - pl.rlo[t]),
+                          (hi - lo) * sizeof(int32_t)));
+      if (m->dev[s] != m->dev[t]) cross += (hi - lo) * (row16 + sizeof(int32_t));
     }
   }
-  // phase 3 (one thread per shard): (all refs, as gathered operands) x (this shard's query rows)
+  // phase 3 (one thread per shard): (all refs) x (this shard's query rows)
   std::vector<hg_status> sst(ns, HG_OK);
   st = for_each_shard(m, [&](int s) -> hg_status {
     hg_ctx *c = m->ctx[s];
-    hg_multi::Shard &x = m->sh[s];
+    Shard &x = m->sh[s];
     const size_t qn_rows = pl.chi[s] - pl.clo[s];
     if (qn_rows == 0) return HG_OK;
     HG_HIP(c, hipSetDevice(m->dev[s]));
-    const int16_t *q_hv = d_qry ? d_qry[s] : static_cast<const int16_t *>(x.qry.p);
-    const int32_t *q_n2 = d_qry ? d_qn[s] : static_cast<const int32_t *>(x.qry_n2.p);
-    sst[s] = hg_dist_block_ops_dev(c, static_cast<const uint8_t *>(x.ops_all.p), static_cast<const uint8_t *>(x.meta_all.p),
-                                   static_cast<const int32_t *>(x.n2_all.p), pl.R, 0, nullptr,
-                                   static_cast<const uint32_t *>(x.flags_all.p), (size_t)ns, q_hv, q_n2, qn_rows, pl.clo[s], hv_d,
-                                   ksize, symmetric, ani_th, static_cast<hg_ani_hit *>(x.hits.p), caps[s], &found[s]);
+    const auto *g_hv = static_cast<const int16_t *>(x.ref_all.p);
+    const auto *g_n2 = static_cast<const int32_t *>(x.n2_all.p);
+    const int16_t *q_hv = d_qry ? d_qry[s] : ops ? static_cast<const int16_t *>(x.qry.p) : g_hv + pl.clo[s] * (size_t)hv_d;
+    const int32_t *q_n2 = d_qry ? d_qn[s] : ops ? static_cast<const int32_t *>(x.qry_n2.p) : g_n2 + pl.clo[s];
+    auto *hits = static_cast<hg_ani_hit *>(x.hits.p);
+    if (!ops)
+      return hg_dist_block_dev(c, g_hv, g_n2, pl.R, 0, q_hv, q_n2, qn_rows, pl.clo[s], hv_d, ksize, symmetric, ani_th, hits, caps[s],
+                               &found[s]);
+    sst[s] = hg_dist_block_ops_dev(c, static_cast<const uint8_t *>(x.ops_all.p), static_cast<const uint8_t *>(x.meta_all.p), g_n2,
+                                   pl.R, 0, nullptr, static_cast<const uint32_t *>(x.flags_all.p), (size_t)ns, q_hv, q_n2, qn_rows,
+                                   pl.clo[s], hv_d, ksize, symmetric, ani_th, hits, caps[s], &found[s]);
     return sst[s] == HG_ERR_INEXACT ? HG_OK : sst[s];
   });
   for (int s = 0; s < ns; ++s)
     if (sst[s] == HG_ERR_INEXACT) return HG_ERR_INEXACT;  // (an owner's veto is seen by every shard; a query side's by its own)
-  m->gather_report = (rccl_mode ? std::string("rccl ") + (equal ? "ncclAllGather" : "grouped ncclBroadcast") + " over " + std::to_string(ns) + " ranks"
-                                : std::string("peer pulls (hipMemcpyPeerAsync)")) + ", prepared byte operands + control records: " +
-                     std::to_string(pl.R * (rb + mb + 4)) + " B per shard instead of " + std::to_string(pl.R * (row16 + 4)) +
-                     " B of i16 rows, " + std::to_string(peer_bytes) + " B between distinct devices; " + m->peer_report;
+  // hg_multi_gather_report: how the exchange of the call that produced the hits ran
+  size_t per_shard = 0;
+  for (const GatherArray &a : arrs) per_shard += (a.one_each ? (size_t)ns : pl.R) * a.unit;
+  std::string how = "peer pulls (hipMemcpyPeerAsync)";
+  if (use_rccl) {
+    int ver = 0;
+    (void)rccl().GetVersion(&ver);
+    how = std::string("rccl ") + (equal_blocks(pl) ? "ncclAllGather" : "grouped ncclBroadcast") + " over " + std::to_string(ns) +
+          " ranks (version " + std::to_string(ver) + ")";
+  }
+  how += (ops ? ", prepared byte operands + control records: " : ", i16 rows: ") + std::to_string(per_shard) + " B per shard";
+  if (ops) how += " instead of " + std::to_string(pl.R * (row16 + sizeof(int32_t))) + " B of i16 rows";
+  m->gather_report = how + ", " + std::to_string(cross) + " B between distinct devices; " + m->peer_report;
+  // phase 4: the per-shard lists into the caller's buffer
   return merge_hits(m, found, st, out, cap, n_out);
 }
 
@@ -547,54 +532,16 @@ hg_status dist_core_ops(hg_multi *m, const int16_t *const *d_ref, const int32_t 
 hg_status dist_core(hg_multi *m, const int16_t *const *d_ref, const int32_t *const *d_rn, const int16_t *const *d_qry,
                     const int32_t *const *d_qn, const DistPlan &pl, uint32_t hv_d, uint32_t ksize, int symmetric,
                     float ani_th, hg_ani_hit *out, size_t cap, size_t *n_out) {
-  const int ns = (int)m->ctx.size();
-  const size_t row_bytes = (size_t)hv_d * sizeof(int16_t);
   DrainOnExit drain_guard{m};  // every return below leaves all shard streams idle
-  // the exchange of prepared operands first (half the bytes, no repeated prepass); a veto -- sketches that do not fit the
-  // byte scheme -- or the "f16" hook on shard 0 brings the i16 exchange below
+  // the byte form first (half the bytes, no repeated prepass); a veto -- sketches that do not fit the byte scheme -- or
+  // the "f16" hook on shard 0 brings the i16 form
   if (hv_d <= 8192 && hv_d % 8 == 0 && m->ctx[0]->dbg_dist_path != "f16") {
-    const hg_status os = dist_core_ops(m, d_ref, d_rn, d_qry, d_qn, pl, hv_d, ksize, symmetric, ani_th, out, cap, n_out);
+    const hg_status os = dist_form(m, true, d_ref, d_rn, d_qry, d_qn, pl, hv_d, ksize, symmetric, ani_th, out, cap, n_out);
     if (os != HG_ERR_INEXACT) return os;
     drain(m);
-    if (n_out) *n_out = 0;
+    *n_out = 0;
   }
-  std::vector<size_t> found(ns, 0), caps(ns, 0);
-  std::vector<int16_t *> g_hv(ns, nullptr);
-  std::vector<int32_t *> g_n2(ns, nullptr);
-  const bool rccl_mode = m->gather == HG_GATHER_RCCL && !m->comm.empty();
-  // phase 1 (one thread per shard): workspaces.  Under RCCL every rank takes part in the collective, so every
-  // shard gets a gathered matrix; the peer pulls skip shards that have no query rows.
-  hg_status st = for_each_shard(m, [&](int s) -> hg_status {
-    hg_ctx *c = m->ctx[s];
-    hg_multi::Shard &x = m->sh[s];
-    const size_t qn_rows = pl.chi[s] - pl.clo[s];
-    if (qn_rows == 0 && !rccl_mode) return HG_OK;
-    HG_HIP(c, hipSetDevice(m->dev[s]));
-    hg_status e;
-    if ((e = hg_ensure(c, x.ref_all, pl.R * row_bytes + 64)) != HG_OK) return e;
-    if ((e = hg_ensure(c, x.n2_all, pl.R * sizeof(int32_t) + 64)) != HG_OK) return e;
-    g_hv[s] = static_cast<int16_t *>(x.ref_all.p), g_n2[s] = static_cast<int32_t *>(x.n2_all.p);
-    // capacity of this shard's list: its share of the caller's capacity can be exceeded by a skewed hit
-    // distribution, so it gets the whole `cap`, bounded by its pair count
-    const unsigned __int128 pairs = (unsigned __int128)pl.R * qn_rows;
-    caps[s] = (size_t)std::min<unsigned __int128>(pairs, cap);
-    return hg_ensure(c, x.hits, caps[s] * sizeof(hg_ani_hit) + 64);
-  });
-  if (st != HG_OK) return st;
-  // phase 2 (this thread): the exchange step, queued on the shards' streams
-  if ((st = gather_refs(m, d_ref, d_rn, pl, hv_d, g_hv, g_n2)) != HG_OK) return st;
-  // phase 3 (one thread per shard): (all refs) x (this shard's query rows)
-  st = for_each_shard(m, [&](int s) -> hg_status {
-    hg_ctx *c = m->ctx[s];
-    const size_t qn_rows = pl.chi[s] - pl.clo[s];
-    if (qn_rows == 0) return HG_OK;
-    HG_HIP(c, hipSetDevice(m->dev[s]));
-    const int16_t *q_hv = d_qry ? d_qry[s] : g_hv[s] + pl.clo[s] * (size_t)hv_d;
-    const int32_t *q_n2 = d_qry ? d_qn[s] : g_n2[s] + pl.clo[s];
-    return hg_dist_block_dev(c, g_hv[s], g_n2[s], pl.R, 0, q_hv, q_n2, qn_rows, pl.clo[s], hv_d, ksize, symmetric, ani_th,
-                             static_cast<hg_ani_hit *>(m->sh[s].hits.p), caps[s], &found[s]);
-  });
-  return merge_hits(m, found, st, out, cap, n_out);
+  return dist_form(m, false, d_ref, d_rn, d_qry, d_qn, pl, hv_d, ksize, symmetric, ani_th, out, cap, n_out);
 }
 
 // column ranges of the all-vs-all case: by pair count under `symmetric` (column j pairs with j rows)
@@ -610,6 +557,33 @@ void all_vs_all_columns(size_t n, int ns, int symmetric, DistPlan &pl) {
   }
 }
 
+// The checks the several-GPU entry points start with, in this order.  `empty`: nothing to compare -- HG_OK before any
+// pointer is looked at (empty host matrices may come as NULL); `bad`: the entry point's own argument defect, if any.
+hg_status check_args(hg_multi *m, size_t *n_out, bool empty, const char *bad, int symmetric) {
+  if (!m) return HG_ERR_INVALID;
+  if (!n_out) return mfail(m, HG_ERR_INVALID, "n_out == NULL");
+  *n_out = 0;
+  if (empty) return HG_OK;
+  if (bad) return mfail(m, HG_ERR_INVALID, bad);
+  if (symmetric && m->ctx[0]->ani_metric == HG_ANI_CONTAINMENT)
+    return mfail(m, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
+  return HG_OK;
+}
+
+// host rows [lo, hi) of `row_bytes` each -- and their norms, given n2_buf -- into a shard's buffers, queued on its stream
+hg_status upload_rows(hg_ctx *c, hg_ctx::Buf &buf, const void *rows, size_t lo, size_t hi, size_t row_bytes,
+                      hg_ctx::Buf *n2_buf = nullptr, const int32_t *n2 = nullptr) {
+  const size_t n = hi - lo;
+  hg_status e;
+  if ((e = hg_ensure(c, buf, n * row_bytes + 64)) != HG_OK) return e;
+  if (n2_buf && (e = hg_ensure(c, *n2_buf, n * sizeof(int32_t) + 64)) != HG_OK) return e;
+  if (!n) return HG_OK;
+  const auto *src = static_cast<const uint8_t *>(rows) + lo * row_bytes;
+  HG_HIP(c, hipMemcpyAsync(buf.p, src, n * row_bytes, hipMemcpyHostToDevice, c->stream));
+  if (n2_buf) HG_HIP(c, hipMemcpyAsync(n2_buf->p, n2 + lo, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  return HG_OK;
+}
+
 }  // namespace
 
 extern "C" hg_status hg_dist_multi_dev(hg_multi *m, const int16_t *const *d_ref_hv, const int32_t *const *d_ref_norm2,
@@ -617,18 +591,14 @@ extern "C" hg_status hg_dist_multi_dev(hg_multi *m, const int16_t *const *d_ref_
                                        const int32_t *const *d_qry_norm2, const size_t *qry_rows, uint32_t hv_d,
                                        uint32_t ksize, int symmetric, float ani_th, hg_ani_hit *out, size_t cap,
                                        size_t *n_out) {
-  if (!m) return HG_ERR_INVALID;
-  if (!n_out) return mfail(m, HG_ERR_INVALID, "n_out == NULL");
-  *n_out = 0;
-  if (!d_ref_hv || !d_ref_norm2 || !ref_rows || (cap && !out)) return mfail(m, HG_ERR_INVALID, "NULL argument");
-  if (d_qry_hv && (!d_qry_norm2 || !qry_rows)) return mfail(m, HG_ERR_INVALID, "query shards need norms and row counts");
-  if (symmetric && !m->ctx.empty() && m->ctx[0]->ani_metric == HG_ANI_CONTAINMENT)
-    return mfail(m, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
+  const char *bad = !d_ref_hv || !d_ref_norm2 || !ref_rows || (cap && !out) ? "NULL argument"
+                    : d_qry_hv && (!d_qry_norm2 || !qry_rows) ? "query shards need norms and row counts" : nullptr;
+  hg_status st = check_args(m, n_out, false, bad, symmetric);
+  if (st != HG_OK) return st;
   const int ns = (int)m->ctx.size();
   for (int s = 0; s < ns; ++s) {  // the shards' operands may be the outputs of a sketch step still queued on their ctx
     if (hipSetDevice(m->dev[s]) != hipSuccess) return mfail(m, HG_ERR_HIP, "hipSetDevice");
-    const hg_status st = hg_sketch_resolve(m->ctx[s]);
-    if (st != HG_OK) return mfail(m, st, hg_last_error(m->ctx[s]));
+    if ((st = hg_sketch_resolve(m->ctx[s])) != HG_OK) return mfail(m, st, hg_last_error(m->ctx[s]));
   }
   DistPlan pl;
   pl.rlo.resize(ns), pl.rhi.resize(ns);
@@ -654,14 +624,10 @@ extern "C" hg_status hg_dist_multi(hg_multi *m, const int16_t *ref_hv, const int
                                    const int16_t *qry_hv, const int32_t *qry_norm2, size_t Q, uint32_t hv_d,
                                    uint32_t ksize, int symmetric, float ani_th, hg_ani_hit *out, size_t cap,
                                    size_t *n_out) {
-  if (!m) return HG_ERR_INVALID;
-  if (!n_out) return mfail(m, HG_ERR_INVALID, "n_out == NULL");
-  *n_out = 0;
-  if (R == 0 || Q == 0) return HG_OK;
-  if (!ref_hv || !ref_norm2 || !qry_hv || !qry_norm2 || (cap && !out)) return mfail(m, HG_ERR_INVALID, "NULL argument");
-  if (hv_d == 0) return mfail(m, HG_ERR_INVALID, "hv_d == 0");
-  if (symmetric && !m->ctx.empty() && m->ctx[0]->ani_metric == HG_ANI_CONTAINMENT)
-    return mfail(m, HG_ERR_INVALID, "symmetric != 0 with HG_ANI_CONTAINMENT: the metric is directional");
+  const char *bad = !ref_hv || !ref_norm2 || !qry_hv || !qry_norm2 || (cap && !out) ? "NULL argument"
+                    : hv_d == 0 ? "hv_d == 0" : nullptr;
+  const hg_status st = check_args(m, n_out, R == 0 || Q == 0, bad, symmetric);
+  if (st != HG_OK || R == 0 || Q == 0) return st;
   const int ns = (int)m->ctx.size();
   const bool same = ref_hv == qry_hv && ref_norm2 == qry_norm2 && R == Q;
   const size_t row_bytes = (size_t)hv_d * sizeof(int16_t);
@@ -678,32 +644,17 @@ extern "C" hg_status hg_dist_multi(hg_multi *m, const int16_t *ref_hv, const int
   // upload: every reference row crosses PCIe once, to the GPU that publishes it; query rows go to their shard
   std::vector<const int16_t *> d_ref(ns), d_qry(ns);
   std::vector<const int32_t *> d_rn(ns), d_qn(ns);
-  hg_status st = for_each_shard(m, [&](int s) -> hg_status {
+  const hg_status up = for_each_shard(m, [&](int s) -> hg_status {
     hg_ctx *c = m->ctx[s];
     hg_multi::Shard &x = m->sh[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
-    hg_status e;
-    const size_t rr = pl.rhi[s] - pl.rlo[s];
-    if ((e = hg_ensure(c, x.mine, rr * row_bytes + 64)) != HG_OK) return e;
-    if ((e = hg_ensure(c, x.mine_n2, rr * sizeof(int32_t) + 64)) != HG_OK) return e;
-    if (rr) {
-      HG_HIP(c, hipMemcpyAsync(x.mine.p, ref_hv + pl.rlo[s] * (size_t)hv_d, rr * row_bytes, hipMemcpyHostToDevice, c->stream));
-      HG_HIP(c, hipMemcpyAsync(x.mine_n2.p, ref_norm2 + pl.rlo[s], rr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
+    hg_status e = upload_rows(c, x.mine, ref_hv, pl.rlo[s], pl.rhi[s], row_bytes, &x.mine_n2, ref_norm2);
+    if (e == HG_OK && !same) e = upload_rows(c, x.qry, qry_hv, pl.clo[s], pl.chi[s], row_bytes, &x.qry_n2, qry_norm2);
     d_ref[s] = static_cast<const int16_t *>(x.mine.p), d_rn[s] = static_cast<const int32_t *>(x.mine_n2.p);
-    if (!same) {
-      const size_t qq = pl.chi[s] - pl.clo[s];
-      if ((e = hg_ensure(c, x.qry, qq * row_bytes + 64)) != HG_OK) return e;
-      if ((e = hg_ensure(c, x.qry_n2, qq * sizeof(int32_t) + 64)) != HG_OK) return e;
-      if (qq) {
-        HG_HIP(c, hipMemcpyAsync(x.qry.p, qry_hv + pl.clo[s] * (size_t)hv_d, qq * row_bytes, hipMemcpyHostToDevice, c->stream));
-        HG_HIP(c, hipMemcpyAsync(x.qry_n2.p, qry_norm2 + pl.clo[s], qq * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-      }
-      d_qry[s] = static_cast<const int16_t *>(x.qry.p), d_qn[s] = static_cast<const int32_t *>(x.qry_n2.p);
-    }
-    return HG_OK;
+    d_qry[s] = static_cast<const int16_t *>(x.qry.p), d_qn[s] = static_cast<const int32_t *>(x.qry_n2.p);
+    return e;
   });
-  if (st != HG_OK) return st;
+  if (up != HG_OK) return up;
   return dist_core(m, d_ref.data(), d_rn.data(), same ? nullptr : d_qry.data(), same ? nullptr : d_qn.data(), pl, hv_d,
                    ksize, symmetric, ani_th, out, cap, n_out);
 }
@@ -712,50 +663,28 @@ extern "C" hg_status hg_dist_multi(hg_multi *m, const int16_t *ref_hv, const int
 extern "C" hg_status hg_hamming_search_multi(hg_multi *m, const uint32_t *ref_bits, size_t R, const uint32_t *qry_bits,
                                              size_t Q, uint32_t hv_d, uint32_t max_dist, hg_ham_hit *out, size_t cap,
                                              size_t *n_out) {
-  if (!m) return HG_ERR_INVALID;
-  if (!n_out) return mfail(m, HG_ERR_INVALID, "n_out == NULL");
-  *n_out = 0;
-  if (R == 0 || Q == 0) return HG_OK;
-  if (!ref_bits || !qry_bits || (cap && !out)) return mfail(m, HG_ERR_INVALID, "NULL argument");
+  const char *bad = !ref_bits || !qry_bits || (cap && !out) ? "NULL argument" : nullptr;
+  const hg_status chk = check_args(m, n_out, R == 0 || Q == 0, bad, 0);
+  if (chk != HG_OK || R == 0 || Q == 0) return chk;
   const int ns = (int)m->ctx.size();
-  const size_t words = (hv_d + 31) / 32, row_bytes = words * sizeof(uint32_t);
+  const size_t row_bytes = (hv_d + 31) / 32 * sizeof(uint32_t);
   std::vector<size_t> found(ns, 0), caps(ns, 0);
   DrainOnExit drain_guard{m};  // every return below leaves all shard streams idle
-  hg_status st = for_each_shard(m, [&](int s) -> hg_status {
+  const hg_status st = for_each_shard(m, [&](int s) -> hg_status {
     size_t lo, hi;
     hg_shard_range(R, s, ns, &lo, &hi);
     if (hi == lo) return HG_OK;
     hg_ctx *c = m->ctx[s];
     hg_multi::Shard &x = m->sh[s];
     HG_HIP(c, hipSetDevice(m->dev[s]));
+    caps[s] = (size_t)std::min<unsigned __int128>((unsigned __int128)(hi - lo) * Q, cap);
     hg_status e;
-    if ((e = hg_ensure(c, x.mine, (hi - lo) * row_bytes + 64)) != HG_OK) return e;
-    if ((e = hg_ensure(c, x.qry, Q * row_bytes + 64)) != HG_OK) return e;
-    const unsigned __int128 pairs = (unsigned __int128)(hi - lo) * Q;
-    caps[s] = (size_t)std::min<unsigned __int128>(pairs, cap);
     if ((e = hg_ensure(c, x.hits, caps[s] * sizeof(hg_ham_hit) + 64)) != HG_OK) return e;
-    HG_HIP(c, hipMemcpyAsync(x.mine.p, ref_bits + lo * words, (hi - lo) * row_bytes, hipMemcpyHostToDevice, c->stream));
-    HG_HIP(c, hipMemcpyAsync(x.qry.p, qry_bits, Q * row_bytes, hipMemcpyHostToDevice, c->stream));  // broadcast: one PCIe link per GPU
+    if ((e = upload_rows(c, x.mine, ref_bits, lo, hi, row_bytes)) != HG_OK) return e;
+    if ((e = upload_rows(c, x.qry, qry_bits, 0, Q, row_bytes)) != HG_OK) return e;  // broadcast: one PCIe link per GPU
     return hg_hamming_search_block_dev(c, static_cast<const uint32_t *>(x.mine.p), hi - lo, lo,
                                        static_cast<const uint32_t *>(x.qry.p), Q, 0, hv_d, max_dist,
                                        static_cast<hg_ham_hit *>(x.hits.p), caps[s], &found[s]);
   });
-  size_t total = 0;
-  for (int s = 0; s < ns; ++s) total += found[s];
-  *n_out = total;
-  if (st != HG_OK && st != HG_ERR_CAPACITY) return st;
-  if (total > cap) return mfail(m, HG_ERR_CAPACITY, "hit buffer too small");
-  size_t at = 0;
-  for (int s = 0; s < ns; ++s) {
-    if (!found[s]) continue;
-    hg_ctx *c = m->ctx[s];
-    HG_HIP(c, hipSetDevice(m->dev[s]));
-    HG_HIP(c, hipMemcpyAsync(out + at, m->sh[s].hits.p, found[s] * sizeof(hg_ham_hit), hipMemcpyDeviceToHost, c->stream));
-    at += found[s];
-  }
-  for (int s = 0; s < ns; ++s) {
-    HG_HIP(m->ctx[s], hipSetDevice(m->dev[s]));
-    HG_HIP(m->ctx[s], hipStreamSynchronize(m->ctx[s]->stream));
-  }
-  return HG_OK;
+  return merge_hits(m, found, st, out, cap, n_out);
 }

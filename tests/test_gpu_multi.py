@@ -154,6 +154,48 @@ def test_hg_multi_exchanges_prepared_operands_and_falls_back_to_i16_rows(hg):
                 assert ("prepared byte operands" in rep) == (case == "clean"), (case, rep)
 
 
+def test_hg_multi_row_less_owner_sends_its_flag_word(hg):
+    """every owner's flag word is exchanged with the byte operands, a shard without reference rows included: the veto an
+    earlier call left in the receivers' gathered flags must not outlive that call and push clean data to the i16 rows"""
+    import bench
+    dev = torch.device("cuda:0")
+    n = 2400
+
+    def split(x, rows):
+        cuts = np.cumsum([0] + rows)
+        return [x[a:b].contiguous() for a, b in zip(cuts[:-1], cuts[1:])]
+
+    def ptrs(parts):
+        return [t.data_ptr() if t.shape[0] else 0 for t in parts]  # pointer 0 for a shard without rows
+
+    with hg.Context(0) as one, hg.Multi([0, 0, 0]) as m:
+        def check(hv, rows, q, q_rows, sym, byte_form):
+            n2, qn = (hv.int() ** 2).sum(1).int(), (q.int() ** 2).sum(1).int()
+            r_hv, r_n2 = split(hv, rows), split(n2, rows)
+            q_hv, q_n2 = (split(q, q_rows), split(qn, q_rows)) if q_rows else (None, None)
+            out = torch.zeros(3 * 300_000, dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()  # the library's streams do not wait for torch's
+            found, st = one.dist_dev(hv.data_ptr(), n2.data_ptr(), hv.shape[0], q.data_ptr(), qn.data_ptr(), q.shape[0], D, 21,
+                                     sym, 85.0, out.data_ptr(), 300_000)
+            want = out[: 3 * found].cpu().numpy().view(hg.ANI_HIT_DTYPE)
+            if q_rows is None:  # all-vs-all
+                got = m.dist_dev(ptrs(r_hv), ptrs(r_n2), rows, None, None, None, D, 21, sym, 85.0, cap=300_000)
+            else:
+                got = m.dist_dev(ptrs(r_hv), ptrs(r_n2), rows, ptrs(q_hv), ptrs(q_n2), q_rows, D, 21, sym, 85.0, cap=300_000)
+            assert st == 0 and found > 1000 and np.array_equal(_key(got), _key(want)), (rows, q_rows, sym)
+            rep = m.gather_report()
+            assert ("prepared byte operands" in rep) == byte_form, (rows, q_rows, sym, rep)
+
+        dirty = bench.clustered_hvs(n, 0, dev).clone()
+        dirty[1000, 9] += 1  # mixed parity in owner 1's rows: its flag word vetoes the byte form
+        check(dirty, [900, 700, 800], dirty, None, False, False)
+        # owner 1 now owns no rows; its flag word is the cleared one, not the veto the receivers still hold
+        clean = bench.clustered_hvs(n, 0, dev)
+        for sym in (False, True):
+            check(clean, [1200, 0, 1200], clean, None, sym, True)
+        check(clean, [1200, 0, 1200], bench.clustered_hvs(900, 100, dev), [300, 300, 300], False, True)
+
+
 def test_hg_multi_hamming_search_sharded_refs(hg, orc):
     rng = np.random.default_rng(77)
     HD, R, Q = 2048, 1501, 64
