@@ -10,13 +10,14 @@
 //    once, classified 4 bases per instruction (SWAR on dwords: 2-bit codes, upper-cased ASCII and complement ASCII
 //    from v_perm_b32 lookups, validity from one XOR), as a forward image and a reverse-complement image in all four
 //    byte phases, so that both strands of every k-mer are runs of whole dwords;
-//  * the canonical strand is chosen by ONE 64-bit compare of 2-bit packed k-mers (A<C<G<T holds both in ASCII and in
-//    the 2-bit code, so this equals the reference's byte-wise compare, src/cuda_kernel.cu:306-311) and becomes an
+//  * the canonical strand is chosen by ONE compare of 2-bit packed k-mers (A<C<G<T holds both in ASCII and in the 2-bit
+//    code, so this equals the reference's byte-wise compare, src/cuda_kernel.cu:306-311; 32-bit on the top 16 bases for
+//    odd k, 64-bit for even k) and becomes an
 //    ADDRESS: one v_cndmask picks the image, the hash words are ds_reads with immediate offsets -- no instruction
 //    touches the bytes;
 //  * t1ha2 is specialised per k; for k = 17..32 the whole k-mer body (word reads, three or four mixup64 stages,
-//    final64, threshold compare) is one asm statement on fixed register pairs: 57 / 67 vector instructions, 25 / 30 of
-//    them v_mad_u64_u32;
+//    final64, candidate compare on the high dword) is one asm statement on fixed register pairs: 56 / 66 vector
+//    instructions, 25 / 30 of them v_mad_u64_u32;
 //  * survivors (1/scaled of the k-mers) are staged in a small LDS list and the workgroup reserves its range of the
 //    genome's hit slice with ONE global atomic at the end of its work item; lossless: no 8-slot cap like
 //    src/cuda_kernel.cu:316, hash value 0 is kept;
@@ -255,9 +256,9 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 // that goes through an SGPR pair.  Here all temporaries are fixed physical registers, every result is produced in the
 // pair that consumes it, carries go through VCC into a VOP2 v_addc (no SGPR read hazard), and what is left is what the
 // ISA forces: the high dword of a product is an ODD register and a 64-bit addend has to start at an EVEN one -- one
-// v_mov per 128-bit product (into the pair Z = {x, 0}).  57 vector instructions per hash + compare instead of 64.
+// v_mov per 128-bit product (into the pair Z = {x, 0}).  56 vector instructions per hash + candidate compare instead of 64.
 //   v[56:61] / v[62:67]  hash words of k-mer j / j+1 (filled by HG_KS_READ one k-mer ahead)
-//   Z v[68:69]  H v[70:71]  X v[72:73]  A v[74:75]  T v[76:77]  U v[78:79]  S1 v[80:81]  S2 v[82:83]  R v[84:85]
+//   Z v[68:69]  H v71 (hash high dword)  X v[72:73]  A v[74:75]  T v[76:77]  U v[78:79]  S1 v[80:81]  S2 v[82:83]  R v[84:85]
 //   Y v[86:87]  C v[88:89]
 #define HG_KS_MUL128(XLO, XHI, PLO, PHI, ADDEND, OUT, OUTHI)                                   \
   "v_mad_u64_u32 v[74:75], %[junk], " XLO ", " PLO ", 0\n\t"                                   \
@@ -332,7 +333,11 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 #define HG_KS_PAIRS0 ("v[56:57]", "v[58:59]", "v[60:61]", "v[90:91]")
 #define HG_KS_PAIRS1 ("v[62:63]", "v[64:65]", "v[66:67]", "v[92:93]")
 #define HG_KS_APPLY(M, ARGS) M ARGS
-// final64(a, b): x = (a + rot64(b, 41)) * P0, y = (rot64(a, 23) + b) * P6 (low halves), z = x ^ y, mux64(z, P5), compare
+// final64(a, b): x = (a + rot64(b, 41)) * P0, y = (rot64(a, 23) + b) * P6 (low halves), z = x ^ y, mux64(z, P5), compare.
+// The compare only marks CANDIDATES: hi32(h) <= hi32(threshold), one 32-bit compare on the high dword's v_xor instead of
+// the low dword's v_xor and a 64-bit compare.  The hash's low dword stays recoverable -- its two product dwords v74 / v78
+// are outputs -- and the exact h < threshold is decided in the wave-uniform hit path (1 k-mer in `scaled`, plus the
+// k-mers whose high dword equals the threshold's: 2^-32 of them).
 #define HG_KS_FINAL(AP, AL, AH, BP, BL, BH)                                                                          \
   "v_alignbit_b32 v86, " BL ", " BH ", 9\n\t"                                                                        \
   "v_alignbit_b32 v87, " BH ", " BL ", 9\n\t"                                                                        \
@@ -351,9 +356,8 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_mov_b32 v68, v77\n\t"                                                                                           \
   "v_mad_u64_u32 v[78:79], %[junk], v73, %[p5h], v[68:69]\n\t"                                                       \
   "v_addc_co_u32_e32 v79, vcc, 0, v79, vcc\n\t"                                                                      \
-  "v_xor_b32_e32 v70, v74, v78\n\t"                                                                                  \
   "v_xor_b32_e32 v71, v76, v79\n\t"                                                                                  \
-  "v_cmp_gt_u64_e64 %[mask], %[thr], v[70:71]"
+  "v_cmp_ge_u32_e64 %[mask], %[thrh], v71"
 // 17 <= K <= 24: three stages
 #define HG_KS_HASH_TEXT_3(W0, W1, W2, W3)                                                                            \
   /* mixup64<P3>(b, a, w0): x = seed + w0; b = K ^ lo; a = seed + hi */                                              \
@@ -396,13 +400,13 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v83, v79, v76\n\t"                                                                                  \
   HG_KS_FINAL("v[84:85]", "v84", "v85", "v[82:83]", "v82", "v83")
 #define HG_KS_HASH_INPUTS                                                                                            \
-  [seed] "s"(seed), [thr] "s"(threshold), [kk] "n"(K), [p0l] "s"((uint32_t)P0), [p0h] "s"((uint32_t)(P0 >> 32)),     \
+  [seed] "s"(seed), [thrh] "s"((uint32_t)(threshold >> 32)), [kk] "n"(K), [p0l] "s"((uint32_t)P0), [p0h] "s"((uint32_t)(P0 >> 32)),     \
       [p1l] "s"((uint32_t)P1), [p1h] "s"((uint32_t)(P1 >> 32)), [p2l] "s"((uint32_t)P2), [p2h] "s"((uint32_t)(P2 >> 32)), \
       [p3l] "s"((uint32_t)P3), [p3h] "s"((uint32_t)(P3 >> 32)), [p5l] "s"((uint32_t)P5), [p5h] "s"((uint32_t)(P5 >> 32)), \
       [p6l] "s"((uint32_t)P6), [p6h] "s"((uint32_t)(P6 >> 32)), [p4l] "s"((uint32_t)P4), [p4h] "s"((uint32_t)(P4 >> 32)),   \
       [seedl] "s"((uint32_t)seed), [seedh] "s"((uint32_t)(seed >> 32))
 #define HG_KS_HASH_CLOBBERS                                                                                          \
-  "vcc", "v72", "v73", "v74", "v75", "v76", "v77", "v78", "v79", "v80", "v81", "v82", "v83", "v84",   \
+  "vcc", "v72", "v73", "v75", "v76", "v77", "v79", "v80", "v81", "v82", "v83", "v84",                 \
       "v85", "v86", "v87", "v88", "v89"
 
 template <int K>
@@ -704,26 +708,50 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
       }
     }
 
-    // the chosen strand's base address for k-mer jj: forward < reverse complement as one 64-bit compare of 2-bit codes
+    // the chosen strand's base address for k-mer jj: forward < reverse complement as one compare of 2-bit codes (32-bit for
+    // odd K, 64-bit for even K)
     auto strand_base = [&](auto jjc) __attribute__((always_inline)) -> uint32_t {
       constexpr int jj = decltype(jjc)::value;
       uint32_t base = aF;
-      if constexpr (CANON) {
+      if constexpr (CANON && (K & 1) != 0) {
+        // odd K: the TOP dwords decide -- the first 16 bases of the forward k-mer against the first 16 of its reverse
+        // complement.  They always differ: base (K - 1) / 2 (<= 15) is the middle of both strands, code c on one and
+        // 3 - c on the other (the complement is the bitwise NOT of the code, whatever the byte was).  So the 64-bit shifts
+        // and compare of the whole values reduce to one v_alignbit per strand (none where the shift is 0) and a 32-bit
+        // compare.
+        uint32_t fh, rh;
+        if constexpr (WIN == 32) {
+          // top dwords of Gm << 2 jj and Gc << 2 (32 - K - jj)
+          constexpr int SF = 2 * jj, SR = 2 * (32 - K - jj);
+          const uint32_t gmh = (uint32_t)(Gm >> 32), gml = (uint32_t)Gm, gch = (uint32_t)(Gc >> 32), gcl = (uint32_t)Gc;
+          fh = SF == 0 ? gmh : __builtin_amdgcn_alignbit(gmh, gml, 32 - SF);
+          if constexpr (SR == 0) rh = gch;
+          else if constexpr (SR < 32) rh = __builtin_amdgcn_alignbit(gch, gcl, 32 - SR);
+          else rh = gcl << (SR - 32);  // (K < 16)
+        } else {
+          // 96-bit streams: the MSB-first forward stream from bit 2 jj (from the top); bits [e + 32, e + 64) of the LSB-first
+          // complement stream, e = 2 jj + 2 K - 64 (zeros below bit 0)
+          constexpr int o = 2 * jj;
+          fh = o == 0 ? gf[0] : __builtin_amdgcn_alignbit(gf[0], gf[1], 32 - o);
+          constexpr int e = 2 * jj + 2 * K - 64, off = e + 32, a = off >> 5, sft = off & 31;
+          static_assert(off >= 0 && a <= 1, "window inside [0, wc0, wc1, wc2]");
+          const uint32_t x_[4] = {0u, wc[0], wc[1], wc[2]};
+          rh = sft == 0 ? x_[a + 1] : __builtin_amdgcn_alignbit(x_[a + 2], x_[a + 1], sft);
+        }
+        uint64_t lt;
+        asm("v_cmp_lt_u32_e64 %0, %1, %2" : "=s"(lt) : "v"(rh), "v"(fh));
+        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(base) : "v"(aF), "v"(aR[jj >> 2]), "s"(lt));
+      } else if constexpr (CANON) {
+        // even K: the whole 2 K bits, bottom-aligned (WIN = 32) or top-aligned with what lies below them cut off
         uint64_t fv, rv;
         if constexpr (WIN == 32) {
-          if constexpr ((K & 1) != 0) {
-            // odd K: the compare is decided inside the 2K bits, the values only have to be TOP-aligned
-            fv = Gm << (2 * jj);
-            rv = Gc << (2 * (32 - K - jj));
-          } else {
-            constexpr uint64_t MASK2K = (1ull << (2 * K)) - 1;
-            fv = (Gm >> (2 * (32 - K - jj))) & MASK2K;
-            rv = (Gc >> (2 * jj)) & MASK2K;
-          }
+          constexpr uint64_t MASK2K = (1ull << (2 * K)) - 1;
+          fv = (Gm >> (2 * (32 - K - jj))) & MASK2K;
+          rv = (Gc >> (2 * jj)) & MASK2K;
         } else {
           // 96-bit streams: both values TOP-aligned in 64 bits.  Forward: the MSB-first stream from bit 2 jj (from the
           // top).  Reverse: bits [e, e + 64) of the LSB-first complement stream, e = 2 jj + 2 K - 64 (zeros below
-          // bit 0).  Even K: what lies below the 2 K bits is cut off; odd K: it cannot decide.
+          // bit 0).
           constexpr int o = 2 * jj;
           uint32_t fh, fl;
           if constexpr (o == 0) fh = gf[0], fl = gf[1];
@@ -734,7 +762,7 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
           uint32_t rl, rh;
           if constexpr (sft == 0) rl = x_[a], rh = x_[a + 1];
           else rl = __builtin_amdgcn_alignbit(x_[a + 1], x_[a], sft), rh = __builtin_amdgcn_alignbit(x_[a + 2], x_[a + 1], sft);
-          if constexpr ((K & 1) == 0 && K < 32) {
+          if constexpr (K < 32) {
             constexpr uint32_t LOWCUT = ~((1u << (64 - 2 * K)) - 1u);
             fl &= LOWCUT, rl &= LOWCUT;
           }
@@ -774,7 +802,8 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
     // addresses, one dword and the last 1..4 bytes), hash, compare with the threshold.  The buffers are bound to fixed
     // registers on both sides, so the compiler sees ordinary values and never copies them.
     uint64_t w0a = 0, w0b = 0, w0c = 0, w0d = 0, w1a = 0, w1b = 0, w1c = 0, w1d = 0;  // parity 0: v[56:61] + v[90:91], parity 1: v[62:67] + v[92:93]
-    uint64_t hmask = 0, hjunk = 0, hval = 0;
+    uint64_t hmask = 0, hjunk = 0;
+    uint32_t hlo0 = 0, hlo1 = 0, hhi = 0;  // the hash: {hlo0 ^ hlo1, hhi}
     uint64_t zpair = 0;  // Z = {x, 0}: the zero-extension pair of the products' high dwords; every asm statement rewrites
                          // its low half only, so the zero in the high half is carried from k-mer to k-mer as a value
     constexpr int KCASE = 10 * ND + NB;
@@ -790,20 +819,20 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
   if constexpr (KCASE == C)                                                                                           \
     asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS0) HG_KS_APPLY(HG_KS_READ_TEXT_##C, HG_KS_REGS1) "\n\t"   \
                  HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS0)                                                       \
-                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "={v[70:71]}"(hval), "={v[68:69]}"(zpair), HG_KS_OUT1     \
+                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair), HG_KS_OUT1     \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), [base] "v"(base), HG_KS_OFFS, HG_KS_IN0                    \
                  : HG_KS_HASH_CLOBBERS);
 #define HG_KS_ODD(C, N)                                                                                               \
   if constexpr (KCASE == C)                                                                                           \
     asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS1) HG_KS_APPLY(HG_KS_READ_TEXT_##C, HG_KS_REGS0) "\n\t"   \
                  HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS1)                                                       \
-                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "={v[70:71]}"(hval), "={v[68:69]}"(zpair), HG_KS_OUT0     \
+                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair), HG_KS_OUT0     \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), [base] "v"(base), HG_KS_OFFS, HG_KS_IN1                    \
                  : HG_KS_HASH_CLOBBERS);
 #define HG_KS_LAST(C, N)                                                                                              \
   if constexpr (KCASE == C)                                                                                           \
     asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS1) HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS1)         \
-                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "={v[70:71]}"(hval), "={v[68:69]}"(zpair)                 \
+                 : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair)                 \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), HG_KS_IN1                                                  \
                  : HG_KS_HASH_CLOBBERS);
 #define HG_KS_ALL_CASES(X) X(51, 3) X(52, 3) X(53, 3) X(54, 3) X(61, 3) X(62, 3) X(63, 3) X(64, 3) \
@@ -831,10 +860,9 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
             static_assert((M & 1) == 0, "the last k-mer's words are in the parity-1 buffer");
             HG_KS_ALL_CASES(HG_KS_LAST)
           }
-          if (hmask != 0) {  // wave-uniform: some lane's hash is below the threshold (1 k-mer in `scaled`)
-            uint32_t below;
-            asm volatile("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(below) : "s"(hmask));
-            if (below && valid && hashing) stage_hit(stage, stage_cap, hval, gm, g, hits, cnt);
+          if (hmask != 0) {  // wave-uniform: some lane is a candidate (1 k-mer in `scaled`); the exact test
+            const uint64_t h = mk64(hlo0 ^ hlo1, hhi);
+            if (h < threshold && valid && hashing) stage_hit(stage, stage_cap, h, gm, g, hits, cnt);
           }
         });
       }
