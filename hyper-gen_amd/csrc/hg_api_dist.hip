@@ -128,9 +128,12 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   } else {
     c->cen_sig_ref = c->cen_sig_qry = nullptr;
   }
+  // the guarded windowed launch of the raw-value chain did the work (verdict 1..2): its name, not the whole-K kernel's
+  const uint32_t verdict = h_res[HG_RES_VERDICT];
+  if (mark == 0u && spec_cover > 0 && verdict >= 1u && (int)verdict <= spec_cover) c->last_kernel[HG_T_DIST] = c->last_kernel_win;
   // no guarded launch applied (or the raw f16 chain was not queued behind a trusted i8 / centred attempt that failed after
   // all): statistics-driven schedule
-  if (mark == 0u && (spec_cover == -2 || (spec_cover >= 0 && (int)h_res[HG_RES_VERDICT] > spec_cover))) {
+  if (mark == 0u && (spec_cover == -2 || (spec_cover >= 0 && (int)verdict > spec_cover))) {
     c->misc_zeroed = nullptr;
     if ((s = hg_run_dist(c, a)) != HG_OK) return s;
     if ((s = hg_publish_words(c, d_count, HG_RES_WORDS, &h_res, HG_RES_WORDS)) != HG_OK) return s;

@@ -914,8 +914,9 @@ static hg_status raw_gemm(hg_ctx *c, const hg_dist_args &a, const DistOps &o, co
     if (full) return tile_kernel<CTM, true, true, false>();
     return tile_kernel<CTM, true, false, false>();
   });
-  // (a guarded second launch covers verdicts 1..2 only: the name stays the first one's)
-  HG_HIP(c, launch_tiles(c, k, n_tiles, g, !guard || v_lo == 0 ? &c->last_kernel[HG_T_DIST] : nullptr));
+  // (a guarded second launch covers verdicts 1..2 only: its name goes to its own slot, published by the caller after the
+  // read-back when the verdict fell in its range)
+  HG_HIP(c, launch_tiles(c, k, n_tiles, g, !guard || v_lo == 0 ? &c->last_kernel[HG_T_DIST] : &c->last_kernel_win));
   return HG_OK;
 }
 

@@ -92,6 +92,7 @@ struct hg_ctx {
   int last_ham_path = -1;       // last Hamming search: 0 xor + popcount kernel, 1 +-1 byte GEMM (i8), 2 +-1.0 e2m1 GEMM (FP4)
   std::string last_kernel[HG_T_COUNT];  // name of the last kernel launched per timing class (hg_ctx_last_kernel)
   std::string last_kernel_i8;           // ... of the last i8 operand attempt (it is the DIST kernel when the attempt was valid)
+  std::string last_kernel_win;          // ... of the last guarded windowed raw-value GEMM (the DIST kernel when the verdict was 1..2)
   int ani_metric = HG_ANI_MASH;  // hg_ctx_set_ani_metric: read by every dist / cluster entry point when it is called
   int last_dist_path = -1;      // operand path of the last thresholded dist call: 0 f16 MFMA (raw values), 1 i8 MFMA, 2 integer VALU, 3 f16 MFMA on centred counts
   const void *i8_sig_ref = nullptr, *i8_sig_qry = nullptr;  // operands of the last call that took the i8 path
