@@ -367,7 +367,8 @@ class Context:
         return int(a.value), int(b.value), int(c.value)
 
     def last_kernel(self, cls):
-        """Name of the kernel the last call launched for a timing class ("kmer", "dist"), as rocprofv3 prints it."""
+        """Name of the kernel the last call launched for a timing class ("kmer", "dist"), as rocprofv3 prints it; for "sort" and
+        "encode" every kernel the last sketch step queued for the class, in launch order, joined by " + "."""
         return lib().hg_ctx_last_kernel(self._h, T_NAMES.index(cls)).decode()
 
     def enable_timing(self, on=True):

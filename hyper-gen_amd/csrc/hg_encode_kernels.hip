@@ -974,7 +974,7 @@ static uint64_t sort_bucket_mul(uint32_t keys, uint64_t threshold) {
 
 hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo, uint32_t n_todo,
                                       uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t max_cap,
-                                      uint64_t threshold) {
+                                      uint64_t threshold, std::string *launched) {
   if (n_todo == 0) return hipSuccess;
   const uint32_t keys = hg_sort_lds_keys(max_cap);
   const uint64_t bucket_mul = sort_bucket_mul(keys, threshold);
@@ -982,12 +982,14 @@ hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_me
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL((sort_unique_kernel<true>), dim3(n_todo), dim3(SORT_WG), sort_lds_bytes(keys, bucket_mul), st, d_meta,
                      d_hits, d_cnt, d_ndistinct, keys, d_todo, bucket_mul, (uint32_t *)nullptr);
+  hg_note_launch(launched, "sort_unique_kernel<true>");
   return hipGetLastError();
 }
 
 hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                                  uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags) {
+                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags,
+                                 std::string *launched) {
   if (n_genomes == 0) return hipSuccess;
   const uint32_t keys = hg_sort_lds_keys(max_cap);
   const uint64_t bucket_mul = sort_bucket_mul(keys, threshold);
@@ -997,18 +999,20 @@ hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, u
   if (keys <= 64) {  // tiny sets: a wave per genome
     hipLaunchKernelGGL(sort_unique_wave_kernel, dim3((n_genomes + 3) / 4), dim3(256), 0, st, d_meta, d_hits, d_cnt, d_ndistinct,
                        n_genomes, d_flags);
+    hg_note_launch(launched, "sort_unique_wave_kernel");
     return hipGetLastError();
   }
   // genomes whose hit count exceeds the LDS budget are skipped here: the caller learns the counts and
   // runs hg_launch_sort_large / hg_launch_sort_inplace for them (or, with d_flags, reads the step's flag word)
   hipLaunchKernelGGL((sort_unique_kernel<true>), dim3(n_genomes), dim3(SORT_WG), lds, st, d_meta,
                      d_hits, d_cnt, d_ndistinct, keys, (const uint32_t *)nullptr, bucket_mul, d_flags);
+  hg_note_launch(launched, "sort_unique_kernel<true>");
   return hipGetLastError();
 }
 
 hipError_t hg_launch_sort_unique_rest(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes, uint64_t *d_hits,
                                       const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t done_cap, uint32_t max_cap,
-                                      uint64_t threshold) {
+                                      uint64_t threshold, std::string *launched) {
   const uint32_t skip = hg_sort_lds_keys(done_cap), keys = hg_sort_lds_keys(max_cap);
   if (n_genomes == 0 || skip >= keys) return hipSuccess;
   const uint64_t bucket_mul = sort_bucket_mul(keys, threshold);
@@ -1016,28 +1020,32 @@ hipError_t hg_launch_sort_unique_rest(hipStream_t st, const hg_genome_meta *d_me
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sort_unique_rest_kernel, dim3((n_genomes + SORT_WG - 1) / SORT_WG), dim3(SORT_WG),
                      sort_lds_bytes(keys, bucket_mul), st, d_meta, d_hits, d_cnt, d_ndistinct, n_genomes, skip, keys, bucket_mul);
+  hg_note_launch(launched, "sort_unique_rest_kernel");
   return hipGetLastError();
 }
 
 hipError_t hg_launch_sketch_finish(hipStream_t st, const uint32_t *d_ndistinct, uint32_t *d_nhash, uint32_t n_genomes,
-                                   const uint32_t *d_flags, uint32_t *h_slot, uint32_t seq) {
+                                   const uint32_t *d_flags, uint32_t *h_slot, uint32_t seq, std::string *launched) {
   hipLaunchKernelGGL(sketch_finish_kernel, dim3((n_genomes + 255) / 256), dim3(256), 0, st, d_ndistinct, d_nhash, n_genomes,
                      d_flags, h_slot, seq);
+  hg_note_launch(launched, "sketch_finish_kernel");
   return hipGetLastError();
 }
 
 hipError_t hg_launch_sort_inplace(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo,
-                                  uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct) {
+                                  uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
+                                  std::string *launched) {
   if (n_todo == 0) return hipSuccess;
   hipLaunchKernelGGL((sort_unique_kernel<false>), dim3(n_todo), dim3(SORT_WG), 0, st, d_meta, d_hits, d_cnt,
                      d_ndistinct, SORT_LDS_MAX_KEYS, d_todo, (uint64_t)0, (uint32_t *)nullptr);
+  hg_note_launch(launched, "sort_unique_kernel<false>");
   return hipGetLastError();
 }
 
 hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uint32_t n_jobs,
                                 const uint32_t *d_chunk_job, uint32_t n_chunks, const uint32_t *d_bucket_job,
                                 uint32_t n_buckets, uint32_t *d_bk, uint64_t *d_hits, uint64_t *d_tmp,
-                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys) {
+                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, std::string *launched) {
   if (n_jobs == 0) return hipSuccess;
   uint32_t cap_keys = (uint32_t)SORT_WG;  // (a power of two: the counting sort deals n2 / SORT_WG sub-buckets to a thread)
   while (cap_keys < bucket_cap_keys && cap_keys < SORT_LDS_MAX_KEYS) cap_keys <<= 1;
@@ -1055,6 +1063,9 @@ hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uin
   hipLaunchKernelGGL(bucket_scan_kernel, dim3(n_jobs), dim3(SORT_WG), 0, st, d_jobs, bdist, bout, d_ndistinct);
   hipLaunchKernelGGL(bucket_copy_kernel, dim3(n_buckets), dim3(BK_WG), 0, st, d_jobs, d_bucket_job, bstart, bdist, bout,
                      fail, d_tmp, d_hits);
+  for (const char *k : {"bucket_count_kernel", "bucket_scan_kernel", "bucket_scatter_kernel", "bucket_sort_kernel", "bucket_scan_kernel",
+                        "bucket_copy_kernel"})
+    hg_note_launch(launched, k);
   return hipGetLastError();
 }
 
@@ -1073,7 +1084,7 @@ static hipError_t encode_attr() {
 hipError_t hg_launch_encode(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                             const uint64_t *d_hits, const uint32_t *d_ndistinct, uint32_t hv_d,
                             uint32_t layout, int16_t *d_hv, int32_t *d_norm2, const hg_encode_split *split,
-                            uint32_t max_hashes) {
+                            uint32_t max_hashes, std::string *launched) {
   if (n_genomes == 0) return hipSuccess;
   const size_t lds = (size_t)64 * (hv_d / 64 + 1) * sizeof(uint32_t);
   if (lds > 150 * 1024) return hipErrorInvalidValue;  // hv_d up to ~38k
@@ -1088,11 +1099,13 @@ hipError_t hg_launch_encode(hipStream_t st, const hg_genome_meta *d_meta, uint32
   hipLaunchKernelGGL(encode_wave_kernel, dim3((n_genomes + 3) / 4), dim3(256), 0, st, d_meta, d_hits, d_ndistinct, n_genomes,
                      hv_d, layout, d_hv, d_norm2, wave_max);
   if ((e = hipGetLastError()) != hipSuccess) return e;
+  hg_note_launch(launched, "encode_wave_kernel");
   if (max_hashes > wave_max) {  // some genome may exceed what the wave kernel takes
     hipLaunchKernelGGL(encode_kernel<false>, dim3(n_genomes), dim3(ENC_WG), lds, st, d_meta, d_hits, d_ndistinct, hv_d,
                        layout, d_hv, d_norm2, sp ? (uint32_t)HG_ENC_SLAB : ~0u, (const uint2 *)nullptr, (uint32_t *)nullptr,
                        wave_max);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    hg_note_launch(launched, "encode_kernel<false>");
   }
   if (!sp) return e;
   if ((e = hipMemsetAsync(split->d_accum, 0, (size_t)split->n_genomes * hv_d * sizeof(uint32_t), st)) != hipSuccess) return e;
@@ -1100,5 +1113,7 @@ hipError_t hg_launch_encode(hipStream_t st, const hg_genome_meta *d_meta, uint32
                      layout, d_hv, d_norm2, ~0u, reinterpret_cast<const uint2 *>(split->d_items), split->d_accum, 0u);
   hipLaunchKernelGGL(encode_finalize_kernel, dim3(split->n_genomes), dim3(ENC_WG), 0, st, split->d_genomes, d_ndistinct,
                      split->d_accum, hv_d, layout, d_hv, d_norm2);
+  hg_note_launch(launched, "encode_kernel<true>");
+  hg_note_launch(launched, "encode_finalize_kernel");
   return hipGetLastError();
 }

@@ -236,6 +236,13 @@ hipError_t hg_launch_pack2(hipStream_t st, const uint8_t *d_seq, const uint64_t 
 #define HG_SORT_LDS_MAX_KEYS 8192u  // keys one workgroup orders in LDS with its counting sort (was 16 384 with the bitonic network behind 8 192)
 
 // ---- sort/unique + encode kernels ---------------------------------------------------------
+// Every launcher below takes `launched`: when not null, the name of each kernel it queues is appended to it, in launch
+// order, joined by " + " and spelled as rocprofv3 prints it (what hg_ctx_last_kernel reports for HG_T_SORT / HG_T_ENCODE).
+inline void hg_note_launch(std::string *launched, const char *name) {
+  if (!launched) return;
+  if (!launched->empty()) *launched += " + ";
+  *launched += name;
+}
 // Sorts each genome's hits ascending, removes duplicates in place (region start),
 // d_ndistinct[g] = distinct count.  max_cnt_pow2 bounds the LDS sort size.
 // keys the LDS sort launched for capacity `max_cap` holds per genome (a power of two, at most HG_SORT_LDS_MAX_KEYS);
@@ -243,7 +250,7 @@ hipError_t hg_launch_pack2(hipStream_t st, const uint8_t *d_seq, const uint64_t 
 uint32_t hg_sort_lds_keys(uint32_t max_cap);
 hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo, uint32_t n_todo,
                                       uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t max_cap,
-                                      uint64_t threshold);
+                                      uint64_t threshold, std::string *launched = nullptr);
 // (threshold: every key is below it -- the sampling threshold; it scales the buckets of the counting-sort fast path,
 // 0 = bitonic only)
 // d_flags != nullptr (the sync-free step): a genome whose raw count exceeds its hit region (HG_STEP_OVERFLOW) or the
@@ -251,18 +258,19 @@ hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_me
 // HG_NHASH_PENDING, which the encoders skip.
 hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                                  uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags = nullptr);
+                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags = nullptr,
+                                 std::string *launched = nullptr);
 #define HG_STEP_OVERFLOW 1u
 #define HG_STEP_LARGE_SET 2u
 // The genomes a sort sized for `done_cap` left out (more raw hits than its LDS held keys), with one sized for max_cap:
 // the workgroups find them in the counters themselves -- no list from the host.
 hipError_t hg_launch_sort_unique_rest(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes, uint64_t *d_hits,
                                       const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t done_cap, uint32_t max_cap,
-                                      uint64_t threshold);
+                                      uint64_t threshold, std::string *launched = nullptr);
 // Last kernel of a sync-free step: d_nhash[g] = d_ndistinct[g], and the step's flag word goes to the page-locked
 // check slot with the step's sequence number behind it (h_slot[0] = flags, h_slot[1] = seq).
 hipError_t hg_launch_sketch_finish(hipStream_t st, const uint32_t *d_ndistinct, uint32_t *d_nhash, uint32_t n_genomes,
-                                   const uint32_t *d_flags, uint32_t *h_slot, uint32_t seq);
+                                   const uint32_t *d_flags, uint32_t *h_slot, uint32_t seq, std::string *launched = nullptr);
 
 // Genomes with more than HG_SORT_LDS_MAX_KEYS sampled hashes: keys are bucketed by value (monotone map, so
 // the concatenation of sorted buckets is sorted), every bucket is sorted + de-duplicated in LDS by its own
@@ -281,10 +289,11 @@ struct hg_bucket_job {
 hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uint32_t n_jobs,
                                 const uint32_t *d_chunk_job, uint32_t n_chunks, const uint32_t *d_bucket_job,
                                 uint32_t n_buckets, uint32_t *d_bk, uint64_t *d_hits, uint64_t *d_tmp,
-                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys);
+                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, std::string *launched = nullptr);
 // in-place global-memory sort + unique of the listed genomes (power-of-two sized hit regions)
 hipError_t hg_launch_sort_inplace(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo,
-                                  uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct);
+                                  uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
+                                  std::string *launched = nullptr);
 
 // Genomes with more than HG_ENC_SLAB distinct hashes can be encoded by several workgroups: d_items[i] =
 // {genome, slab | slot << 16} for every slab of HG_ENC_SLAB hashes (planned from an upper bound of the distinct
@@ -300,7 +309,8 @@ struct hg_encode_split {
 hipError_t hg_launch_encode(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                             const uint64_t *d_hits, const uint32_t *d_ndistinct, uint32_t hv_d,
                             uint32_t layout, int16_t *d_hv, int32_t *d_norm2, const hg_encode_split *split = nullptr,
-                            uint32_t max_hashes = ~0u /* upper bound of the distinct counts, if the host knows one */);
+                            uint32_t max_hashes = ~0u /* upper bound of the distinct counts, if the host knows one */,
+                            std::string *launched = nullptr);
 
 // ---- dist kernels ------------------------------------------------------------------------------
 struct hg_dist_args {

@@ -66,7 +66,7 @@ static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uin
       hg_timed tm(c, HG_T_SORT);
       HG_HIP(c, hg_launch_sort_large(c->stream, d_jobs, (uint32_t)jobs.size(), d_chunk, (uint32_t)chunk_job.size(), d_bucket,
                                      (uint32_t)bucket_job.size(), d_bk, d_hits, static_cast<uint64_t *>(c->w_hits2.p), d_nd,
-                                     c->dbg_sort_buckets ? HG_SORT_LDS_MAX_KEYS : cap_keys));
+                                     c->dbg_sort_buckets ? HG_SORT_LDS_MAX_KEYS : cap_keys, &c->last_kernel[HG_T_SORT]));
     }
     HG_HIP(c, hipMemcpyAsync(fail.data(), d_bk + 5 * bucket_job.size(), jobs.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HG_HIP(c, hipStreamSynchronize(c->stream));  // also keeps the host vectors alive until the uploads are done
@@ -78,7 +78,7 @@ static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uin
     {
       hg_timed tm(c, HG_T_SORT);
       HG_HIP(c, hg_launch_sort_inplace(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), d_todo, (uint32_t)inplace.size(),
-                                       d_hits, d_cnt, d_nd));
+                                       d_hits, d_cnt, d_nd, &c->last_kernel[HG_T_SORT]));
     }
     HG_HIP(c, hipStreamSynchronize(c->stream));
   }
@@ -134,7 +134,9 @@ hg_status hg_sample_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *
       const uint32_t seen = reuse ? c->plan->max_hits : 0;
       if (seen) sort_cap = (uint32_t)std::min<uint64_t>(sort_cap, (uint64_t)seen + seen / 8 + 16);
       hg_timed tm(c, HG_T_SORT, HG_T_KMER);
-      HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold));
+      c->last_kernel[HG_T_SORT].clear();  // (an attempt after an overflow reports its own launches)
+      HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold, nullptr,
+                                      &c->last_kernel[HG_T_SORT]));
     }
     // overflow check on the raw counters (they keep counting past the capacity)
     HG_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -167,7 +169,7 @@ hg_status hg_sample_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *
           HG_HIP(c, hipMemcpyAsync(c->w_redo.p, h_redo, n_redo * 4, hipMemcpyHostToDevice, c->stream));
           hg_timed tm(c, HG_T_SORT);
           HG_HIP(c, hg_launch_sort_unique_todo(c->stream, d_meta, static_cast<uint32_t *>(c->w_redo.p), (uint32_t)n_redo,
-                                               d_hits, d_cnt, d_nd, pl.max_cap, threshold));
+                                               d_hits, d_cnt, d_nd, pl.max_cap, threshold, &c->last_kernel[HG_T_SORT]));
           HG_HIP(c, hipStreamSynchronize(c->stream));  // (rare path; the next call may rewrite the scratch at once)
         }
       }
@@ -228,9 +230,10 @@ hg_status hg_sketch_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *
   }
   {
     hg_timed tm(c, HG_T_ENCODE);
+    c->last_kernel[HG_T_ENCODE].clear();
     HG_HIP(c, hg_launch_encode(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), (uint32_t)n,
                                static_cast<uint64_t *>(c->w_hits.p), d_nd, p->hv_d, p->hv_layout, d_hv, d_norm2,
-                               split.n_items ? &split : nullptr, pl.max_hits));
+                               split.n_items ? &split : nullptr, pl.max_hits, &c->last_kernel[HG_T_ENCODE]));
   }
   if (split.n_items) HG_HIP(c, hipStreamSynchronize(c->stream));  // the pageable item tables must outlive their upload
   HG_HIP(c, hipMemcpyAsync(d_nhash, d_nd, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));

@@ -141,14 +141,18 @@ hg_status hg_sketch_step(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offset
     // outgrow it are picked up by the second launch (capacity-sized; its workgroups leave at once when there are none).
     const uint32_t sort_cap = first_sort_cap(*c->plan);
     hg_timed tm(c, HG_T_SORT, HG_T_KMER);
-    HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold, d_flags));
-    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, t.max_cap, threshold));
+    std::string *names = &c->last_kernel[HG_T_SORT];
+    names->clear();
+    HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold, d_flags, names));
+    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, t.max_cap, threshold, names));
   }
   {
     hg_timed tm(c, HG_T_ENCODE, HG_T_SORT);
+    std::string *names = &c->last_kernel[HG_T_ENCODE];
+    names->clear();
     HG_HIP(c, hg_launch_encode(c->stream, d_meta, (uint32_t)n, d_hits, d_nd, p->hv_d, p->hv_layout, d_hv, d_norm2, nullptr,
-                               std::min<uint32_t>(t.max_cap, HG_SORT_LDS_MAX_KEYS)));
-    HG_HIP(c, hg_launch_sketch_finish(c->stream, d_nd, d_nhash, (uint32_t)n, d_flags, c->h_chk + 16 * slot, seq));
+                               std::min<uint32_t>(t.max_cap, HG_SORT_LDS_MAX_KEYS), names));
+    HG_HIP(c, hg_launch_sketch_finish(c->stream, d_nd, d_nhash, (uint32_t)n, d_flags, c->h_chk + 16 * slot, seq, names));
   }
   ++c->n_fast_steps;
 
