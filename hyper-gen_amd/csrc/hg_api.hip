@@ -344,9 +344,11 @@ extern "C" hg_status hg_dev_alloc(hg_ctx *c, size_t bytes, void **dptr) {
 }
 extern "C" hg_status hg_dev_free(hg_ctx *c, void *dptr) {
   if (!c) return HG_ERR_INVALID;
-  HG_ENTER(c);  // (the block may be an operand of the queued sketch step)
-  if (dptr) HG_HIP(c, hipFree(dptr));
-  return HG_OK;
+  // the block may be an operand of the queued sketch step: that is resolved first, and the block freed whatever it reports
+  const hg_status s = [c]() -> hg_status { HG_ENTER(c); return HG_OK; }();
+  const hipError_t e = dptr ? hipFree(dptr) : hipSuccess;
+  if (s == HG_OK && e != hipSuccess) return hg_fail(c, HG_ERR_HIP, std::string("hipFree(dptr): ") + hipGetErrorString(e));
+  return s;
 }
 extern "C" hg_status hg_copy_h2d(hg_ctx *c, void *dst, const void *src, size_t bytes) {
   if (!c) return HG_ERR_INVALID;

@@ -31,6 +31,8 @@ static hg_status sketch_batch_dev_impl(hg_ctx *c, const uint8_t *d_seq, const ui
   if (!d_seq || !offsets || !lens || !d_hv || !d_norm2 || !d_nhash) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "more than 2^31 genomes in one batch");
   HG_HIP(c, hipSetDevice(c->device));  // (no HG_ENTER: hg_sketch_step reads the previous step's check word behind its own launches)
+  hg_genome_batch b{d_seq, offsets, lens, mask_offs, n, packed};
+  const hg_sketch_out out{d_hv, d_norm2, d_nhash};
   if (!packed && c->dbg_kmer_input == "packed") {
     // test hook: the batch arrived as ASCII -- pack it here and run the packed kernels on the blobs, so that every
     // ASCII entry point (and with it every parity test) can be driven through both input forms
@@ -40,9 +42,10 @@ static hg_status sketch_batch_dev_impl(hg_ctx *c, const uint8_t *d_seq, const ui
     for (size_t g = 0; g < n; ++g) hook_offs[g] = total, total += hg_pack2_size(lens[g]);
     if ((s = hg_ensure(c, c->w_pk, total + 64)) != HG_OK) return s;
     if ((s = hg_pack_batch(c, d_seq, offsets, lens, n, p->norm_mode, static_cast<uint8_t *>(c->w_pk.p), hook_offs.data())) != HG_OK) return s;
-    return hg_sketch_step(c, static_cast<const uint8_t *>(c->w_pk.p), hook_offs.data(), lens, n, p, d_hv, d_norm2, d_nhash, true, nullptr);
+    b.d_seq = static_cast<const uint8_t *>(c->w_pk.p), b.offsets = hook_offs.data(), b.packed = true;
+    return hg_sketch_step(c, b, p, out);
   }
-  return hg_sketch_step(c, d_seq, offsets, lens, n, p, d_hv, d_norm2, d_nhash, packed, mask_offs);
+  return hg_sketch_step(c, b, p, out);
 }
 
 hg_status hg_sketch_batch_dev_packed_masks(hg_ctx *c, const uint8_t *d_blobs, const uint64_t *code_offs, const uint64_t *mask_offs,
@@ -489,12 +492,13 @@ extern "C" hg_status hg_kmer_hash_sample(hg_ctx *c, const uint8_t *seq, size_t n
   // capacity heuristic wants "scaled"; derive it from the threshold (threshold = MAX / scaled)
   uint64_t scaled = threshold ? UINT64_MAX / threshold : UINT64_MAX;
   if (scaled < 1) scaled = 1;
+  const hg_genome_batch b{static_cast<uint8_t *>(c->w_seq.p), offs.data(), l64.data(), nullptr, 1, packed};
+  const hg_sketch_params p{ksize, canonical != 0, scaled, seed, 0, 0, norm_mode, 0};  // (no encode)
   hg_batch_tables pl;
   uint32_t *d_nd = nullptr;
   hg_sample_fetch fetch;
   fetch.max_hashes = out_hashes ? cap : 0;
-  s = hg_sample_batch_sync(c, static_cast<uint8_t *>(c->w_seq.p), offs.data(), l64.data(), 1, ksize, threshold, scaled,
-                         seed, canonical != 0, norm_mode, pl, &d_nd, packed, nullptr, &fetch);
+  s = hg_sample_batch_sync(c, b, &p, threshold, pl, false, &d_nd, &fetch);
   if (s != HG_OK) return s;
   if (fetch.valid) {  // count and hashes came back with sample_batch's own synchronisation
     *n_out = fetch.nd;

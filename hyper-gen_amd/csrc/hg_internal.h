@@ -27,16 +27,28 @@ struct hg_sketch_plan {
   size_t n_items = 0;
   size_t n_groups = 0;      // workgroups of the k-mer launch: groups of consecutive work items (w_items holds the table behind the items)
 };
+// One sketch batch as the caller hands it over: genomes on the device, their offset / length (/ mask offset) arrays on the host.
+struct hg_genome_batch {
+  const uint8_t *d_seq = nullptr;
+  const uint64_t *offsets = nullptr, *lens = nullptr;
+  const uint64_t *mask_offs = nullptr;  // packed only: nullptr = each bitmap directly behind its codes
+  size_t n = 0;
+  bool packed = false;
+};
+// ... and where its sketches go (device)
+struct hg_sketch_out {
+  int16_t *d_hv = nullptr;
+  int32_t *d_norm2 = nullptr;
+  uint32_t *d_nhash = nullptr;
+};
 struct hg_sketch_pending {
   bool active = false;
   uint32_t seq = 0;
   int slot = 0;
-  std::shared_ptr<const hg_sketch_plan> plan;
-  const uint8_t *d_seq = nullptr;
+  std::shared_ptr<const hg_sketch_plan> plan;  // owns the host arrays batch points into
+  hg_genome_batch batch;
   hg_sketch_params p{};
-  int16_t *d_hv = nullptr;
-  int32_t *d_norm2 = nullptr;
-  uint32_t *d_nhash = nullptr;
+  hg_sketch_out out;
 };
 
 // ---- error plumbing ----------------------------------------------------------------
@@ -123,7 +135,7 @@ struct hg_ctx {
   // the sync-free sketch step (hg_sketch_step.hip): its check word comes back through h_chk one call late
   hg_sketch_pending pending;
   uint32_t *h_chk = nullptr;   // 2 slots of 16 page-locked words the device writes {flags, ..., seq} into
-  uint32_t chk_seq = 0;
+  uint32_t chk_seq = 0;        // sequence number of the last step whose finish kernel was queued (never 0 once one was)
   uint64_t n_fast_steps = 0, n_sync_steps = 0, n_redone_steps = 0;  // (hg_ctx_sketch_path_counts: tests, bench)
   // host-fed batches: uploads run on their own stream, one event per sub-batch (hg_sketch_batch)
   hipStream_t copy_stream = nullptr;

@@ -1,9 +1,10 @@
 // hg_sketch.h -- seams between the translation units of the sketch path (not installed):
-//   hg_sketch_plan.hip  batch geometry -> hit regions + work items; the plan kept by the ctx; its upload
+//   hg_sketch_plan.hip  batch geometry -> hit regions + work items; the plan kept by the ctx (hg_plan_get), its upload
 //   hg_sketch_step.hip  the sync-free step (hash + sample -> sort / unique -> encode queued back to back, one check word
-//                       read a call late) and hg_sketch_resolve
+//                       read a call late), hg_sketch_resolve, and hg_sketch_front, the first kernels of both paths
 //   hg_sketch_rare.hip  the synchronous path: counters read back, overflow retry, multi-workgroup sorts, split encode
 //   hg_api_sketch.hip   the C ABI entry points (device-resident, host-fed, one genome per call)
+// A batch travels between them as one hg_genome_batch (hg_internal.h), its outputs as one hg_sketch_out.
 #pragma once
 #include <utility>
 
@@ -19,6 +20,7 @@ struct hg_batch_tables {
   uint64_t total_slots = 0;
   uint32_t max_cap = 0, max_expect = 0;
   size_t n_items = 0;
+  bool reused = false;      // taken from the ctx's cached plan (its tables are on the device)
   uint32_t max_hits = ~0u;  // largest stored raw hit count of the batch (upper bound of the distinct counts)
   std::vector<std::pair<uint32_t, uint32_t>> big;  // (genome, stored raw hits) with more than HG_ENC_SLAB hits
 };
@@ -30,18 +32,17 @@ inline const uint32_t *hg_plan_group_table(const hg_ctx *c, size_t n_items, size
   return n_groups ? static_cast<const uint32_t *>(c->w_items.p) + hg_plan_group_offset(n_items) : nullptr;
 }
 
-// want_caps: optional per-genome minimum capacities (retry after overflow)
-hg_status hg_plan_build(hg_ctx *c, const uint64_t *offsets, const uint64_t *lens, size_t n, uint32_t ksize, uint64_t scaled,
-                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t, const uint64_t *mask_offs);
-// the ctx's cached plan has this geometry (its tables are on the device)
-bool hg_plan_matches(const hg_ctx *c, const uint64_t *offsets, const uint64_t *lens, const uint64_t *mask_offs, size_t n,
-                     uint32_t ksize, uint64_t scaled, bool packed);
-// with_meta = false: the totals only (the sync-free step reads no per-genome record on the host: 400 000 genomes are 16 MB of them)
+// want_caps: optional per-genome minimum capacities (retry after overflow); c may be nullptr (hg_sketch_plan_describe)
+hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
+                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t);
+// The batch's plan: the ctx's cached one when the geometry matches (t.reused; with_meta = false: the totals only -- the
+// sync-free step reads no per-genome record on the host, 400 000 genomes are 16 MB of them), else built afresh.
+hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta = true);
+// the cached plan's capacities and hit offsets into t.meta (a reused plan's records, for the synchronous path)
 void hg_plan_tables_from_cache(const hg_sketch_plan &pl, size_t n, hg_batch_tables &t, bool with_meta = true);
-// Sends a freshly built plan's tables to w_gmeta / w_items through the page-locked plan staging (stream-ordered,
-// returns at once) and makes it the ctx's cached plan.
-hg_status hg_plan_upload(hg_ctx *c, const hg_batch_tables &t, const uint64_t *offsets, const uint64_t *lens,
-                         const uint64_t *mask_offs, size_t n, uint32_t ksize, uint64_t scaled, bool packed);
+// A freshly built plan (not t.reused) goes to w_gmeta / w_items through the page-locked plan staging (stream-ordered,
+// returns at once) and becomes the ctx's cached plan.
+hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled);
 
 // ASCII genomes -> hg_pack2 blobs on the device (synchronises the stream before and after: it uses the ctx's scratch)
 hg_status hg_pack_batch(hg_ctx *c, const uint8_t *d_seq, const uint64_t *seq_offs, const uint64_t *lens, size_t n,
@@ -57,19 +58,21 @@ struct hg_sample_fetch {
   bool valid = false;
 };
 
+// Both paths start here: counters zeroed, k-mer launch, first sort / unique launch (its size in *sort_cap).  sync_free: the
+// sort flags what it cannot take in the step's flag word (zeroed with the counters), and the capacity-sized second sort
+// launch follows; else the synchronous path reads the counters back.
+hg_status hg_sketch_front(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, uint64_t threshold,
+                          const hg_batch_tables &t, bool sync_free, uint32_t *sort_cap);
+
 // The synchronous path.  Runs hash + sample and sort / unique; on return (stream synchronised) the device hit buffer holds
-// each genome's ascending distinct hashes at t.meta[g].hit_off and *d_ndistinct_out the counts.
-hg_status hg_sample_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                               uint32_t ksize, uint64_t threshold, uint64_t scaled_for_cap, uint64_t seed, bool canonical,
-                               uint32_t norm_mode, hg_batch_tables &t, uint32_t **d_ndistinct_out, bool packed,
-                               const uint64_t *mask_offs, hg_sample_fetch *fetch);
+// each genome's ascending distinct hashes at t.meta[g].hit_off and *d_ndistinct_out the counts.  planned: t already holds
+// the batch's plan with its records (hg_plan_get); else it is looked up here.  p->scaled sizes the plan; threshold samples.
+hg_status hg_sample_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, uint64_t threshold,
+                               hg_batch_tables &t, bool planned, uint32_t **d_ndistinct_out, hg_sample_fetch *fetch);
 // ... followed by the encoders (several workgroups for the genomes with very large sets); returns with the encoders
 // queued, everything before them finished.
-hg_status hg_sketch_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                               const hg_sketch_params *p, int16_t *d_hv, int32_t *d_norm2, uint32_t *d_nhash, bool packed,
-                               const uint64_t *mask_offs);
+hg_status hg_sketch_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, const hg_sketch_out &out,
+                               hg_batch_tables *planned = nullptr);
 
 // One sketch step on device-resident genomes: sync-free when the batch allows it, else the synchronous path.
-hg_status hg_sketch_step(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                         const hg_sketch_params *p, int16_t *d_hv, int32_t *d_norm2, uint32_t *d_nhash, bool packed,
-                         const uint64_t *mask_offs);
+hg_status hg_sketch_step(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, const hg_sketch_out &out);

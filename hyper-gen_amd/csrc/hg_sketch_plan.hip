@@ -25,8 +25,8 @@ hg_status hg_check_sketch_params(hg_ctx *c, const hg_sketch_params *p) {
   return HG_OK;
 }
 
-hg_status hg_plan_build(hg_ctx *c, const uint64_t *offsets, const uint64_t *lens, size_t n, uint32_t ksize, uint64_t scaled,
-                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t, const uint64_t *mask_offs) {
+hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
+                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t) {
   const uint64_t item_starts = hg_kmer_item_starts(ksize);
   // groups of work items (one workgroup each): consecutive items of SMALL genomes are put together while the group stays
   // within hg_kmer_item_tiles tiles; an item that fills a work item on its own (a piece of a large genome) stays alone, so
@@ -36,17 +36,18 @@ hg_status hg_plan_build(hg_ctx *c, const uint64_t *offsets, const uint64_t *lens
   bool group_open = false;  // the last group may take more items
   t.group_first.clear();
   uint32_t group_tiles = 0;
-  t.meta.resize(n);
+  t.meta.resize(b.n);
   t.item_genome.clear();
+  t.reused = false;
   uint64_t slot = 0, max_expect = 0;
   uint32_t max_cap = 0;
-  for (size_t g = 0; g < n; ++g) {
-    if (offsets[g] & 3) return hg_fail(c, HG_ERR_INVALID, "genome offsets must be multiples of 4");
+  for (size_t g = 0; g < b.n; ++g) {
+    if (b.offsets[g] & 3) return hg_fail(c, HG_ERR_INVALID, "genome offsets must be multiples of 4");
     hg_genome_meta &m = t.meta[g];
-    m.seq_off = offsets[g];
-    m.n_bps = lens[g];
-    m.mask_off = mask_offs ? mask_offs[g] : offsets[g] + (((lens[g] + 3) / 4 + 15) & ~(uint64_t)15);  // (read by the packed kernels only)
-    const uint64_t n_starts = lens[g] >= ksize ? lens[g] - ksize + 1 : 0;
+    m.seq_off = b.offsets[g];
+    m.n_bps = b.lens[g];
+    m.mask_off = b.mask_offs ? b.mask_offs[g] : m.seq_off + (((m.n_bps + 3) / 4 + 15) & ~(uint64_t)15);  // (read by the packed kernels only)
+    const uint64_t n_starts = m.n_bps >= ksize ? m.n_bps - ksize + 1 : 0;
     const uint64_t expect = n_starts / scaled;
     uint64_t cap = expect * 2 + 1024;    // expected n_starts/scaled; sd ~ sqrt of that
     if (cap > n_starts) cap = n_starts;  // can never exceed the number of k-mers
@@ -85,18 +86,20 @@ hg_status hg_plan_build(hg_ctx *c, const uint64_t *offsets, const uint64_t *lens
   return HG_OK;
 }
 
-bool hg_plan_matches(const hg_ctx *c, const uint64_t *offsets, const uint64_t *lens, const uint64_t *mask_offs, size_t n,
-                     uint32_t ksize, uint64_t scaled, bool packed) {
+hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta) {
+  // the ctx's cached plan has this geometry (its tables are on the device)
   const hg_sketch_plan *pl = c->plan.get();
-  if (!pl || pl->ksize != ksize || pl->scaled != scaled || pl->packed != packed || pl->offs.size() != n) return false;
-  if (std::memcmp(pl->offs.data(), offsets, n * 8) != 0 || std::memcmp(pl->lens.data(), lens, n * 8) != 0) return false;
-  if (mask_offs) return pl->masks.size() == n && std::memcmp(pl->masks.data(), mask_offs, n * 8) == 0;
-  return pl->masks.empty();
+  const bool match = pl && pl->ksize == ksize && pl->scaled == scaled && pl->packed == b.packed && pl->offs.size() == b.n &&
+                     std::memcmp(pl->offs.data(), b.offsets, b.n * 8) == 0 && std::memcmp(pl->lens.data(), b.lens, b.n * 8) == 0 &&
+                     (b.mask_offs ? pl->masks.size() == b.n && std::memcmp(pl->masks.data(), b.mask_offs, b.n * 8) == 0 : pl->masks.empty());
+  if (!match) return hg_plan_build(c, b, ksize, scaled, nullptr, t);
+  hg_plan_tables_from_cache(*pl, b.n, t, with_meta);
+  return HG_OK;
 }
 
 void hg_plan_tables_from_cache(const hg_sketch_plan &pl, size_t n, hg_batch_tables &t, bool with_meta) {
   t.total_slots = pl.total_slots, t.max_cap = pl.max_cap, t.max_expect = pl.max_expect, t.n_items = pl.n_items;
-  t.n_groups = pl.n_groups;
+  t.n_groups = pl.n_groups, t.reused = true;
   t.item_genome.clear();
   t.group_first.clear();
   if (!with_meta) {
@@ -112,8 +115,9 @@ void hg_plan_tables_from_cache(const hg_sketch_plan &pl, size_t n, hg_batch_tabl
   }
 }
 
-hg_status hg_plan_upload(hg_ctx *c, const hg_batch_tables &t, const uint64_t *offsets, const uint64_t *lens,
-                         const uint64_t *mask_offs, size_t n, uint32_t ksize, uint64_t scaled, bool packed) {
+hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled) {
+  if (t.reused) return HG_OK;
+  const size_t n = b.n;
   c->plan.reset();  // (the device tables are about to change)
   hg_status s;
   const size_t n_items = t.item_genome.size();
@@ -151,12 +155,12 @@ hg_status hg_plan_upload(hg_ctx *c, const hg_batch_tables &t, const uint64_t *of
   HG_HIP(c, hipEventRecord(c->plan_uploaded, c->stream));
   c->plan_upload_pending = true;
   auto pl = std::make_shared<hg_sketch_plan>();
-  pl->offs.assign(offsets, offsets + n);
-  pl->lens.assign(lens, lens + n);
-  if (mask_offs) pl->masks.assign(mask_offs, mask_offs + n);
+  pl->offs.assign(b.offsets, b.offsets + n);
+  pl->lens.assign(b.lens, b.lens + n);
+  if (b.mask_offs) pl->masks.assign(b.mask_offs, b.mask_offs + n);
   pl->caps.resize(n);
   for (size_t g = 0; g < n; ++g) pl->caps[g] = t.meta[g].hit_cap;
-  pl->ksize = ksize, pl->scaled = scaled, pl->packed = packed;
+  pl->ksize = ksize, pl->scaled = scaled, pl->packed = b.packed;
   pl->total_slots = t.total_slots, pl->max_cap = t.max_cap, pl->max_expect = t.max_expect, pl->n_items = n_items;
   pl->n_groups = t.n_groups;
   c->plan = std::move(pl);
@@ -196,7 +200,7 @@ extern "C" hg_status hg_sketch_plan_describe(const uint64_t *offsets, const uint
                                              uint64_t counts[6], uint32_t *group_first, size_t cap) {
   if ((n && (!offsets || !lens)) || !counts || ksize < 1 || ksize > 255 || scaled < 1) return HG_ERR_INVALID;
   hg_batch_tables t;
-  const hg_status s = hg_plan_build(nullptr, offsets, lens, n, ksize, scaled, nullptr, t, nullptr);
+  const hg_status s = hg_plan_build(nullptr, {nullptr, offsets, lens, nullptr, n, false}, ksize, scaled, nullptr, t);
   if (s != HG_OK) return s;
   const uint32_t tile = hg_kmer_tile_starts(ksize);
   counts[0] = t.n_items, counts[1] = t.n_groups ? t.n_groups : t.n_items, counts[2] = t.total_slots, counts[3] = t.max_cap;

@@ -1,8 +1,9 @@
 // hg_sketch_rare.hip -- the synchronous sketch path: the per-genome raw counters are read back between sort and encode, and
 // the host takes what the sync-free step (hg_sketch_step.hip) cannot do on the device: growing hit regions after an
 // overflow, the multi-workgroup sorts of hash sets beyond the one-workgroup sort, the split encode of very large sets.
-// Taken for batches whose genomes are EXPECTED to need it (>= 10 Mbp at scaled = 1 500), for the re-run of a step whose
-// check word asked for it, and by hg_kmer_hash_sample (its result goes to the host anyway).
+// Taken for batches whose genomes are EXPECTED to need it (>= 10 Mbp at scaled = 1 500: the step hands over the plan it
+// found), for the re-run of a step whose check word asked for it, and by hg_kmer_hash_sample (its result goes to the host
+// anyway).  Its kernels up to the first sort are queued by hg_sketch_front, as the step's are.
 #include <algorithm>
 #include <cstring>
 
@@ -85,59 +86,32 @@ static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uin
   return HG_OK;
 }
 
-hg_status hg_sample_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                               uint32_t ksize, uint64_t threshold, uint64_t scaled_for_cap, uint64_t seed, bool canonical,
-                               uint32_t norm_mode, hg_batch_tables &pl, uint32_t **d_ndistinct_out, bool packed,
-                               const uint64_t *mask_offs, hg_sample_fetch *fetch) {
+hg_status hg_sample_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, uint64_t threshold,
+                               hg_batch_tables &pl, bool planned, uint32_t **d_ndistinct_out, hg_sample_fetch *fetch) {
+  const size_t n = b.n;
   if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "more than 2^31 genomes in one batch");
   ++c->n_sync_steps;
   std::vector<uint32_t> want;
   for (int attempt = 0; attempt < 3; ++attempt) {
     hg_status s;
-    // same geometry as the previous call (typical for a stream of equally shaped batches): the
-    // work-item table and the per-genome records are still on the device
-    const bool reuse = attempt == 0 && hg_plan_matches(c, offsets, lens, mask_offs, n, ksize, scaled_for_cap, packed);
-    if (reuse) {
-      hg_plan_tables_from_cache(*c->plan, n, pl);
-    } else {
-      if ((s = hg_plan_build(c, offsets, lens, n, ksize, scaled_for_cap, attempt ? &want : nullptr, pl, mask_offs)) != HG_OK) return s;
-      if ((s = hg_plan_upload(c, pl, offsets, lens, mask_offs, n, ksize, scaled_for_cap, packed)) != HG_OK) return s;
-    }
-    const size_t n_items = pl.n_items;
-    if ((s = hg_ensure(c, c->w_hits, pl.total_slots * sizeof(uint64_t) + 16)) != HG_OK) return s;
-    if ((s = hg_ensure(c, c->w_cnt, (2 * n + 16) * sizeof(uint32_t) + 16)) != HG_OK) return s;
+    // same geometry as the previous call (typical for a stream of equally shaped batches): the work-item table and the
+    // per-genome records are still on the device.  A retry after an overflow builds the plan with larger regions.
+    if (attempt) s = hg_plan_build(c, b, p->ksize, p->scaled, &want, pl);
+    else s = planned ? HG_OK : hg_plan_get(c, b, p->ksize, p->scaled, pl);
+    if (s != HG_OK || (s = hg_plan_commit(c, pl, b, p->ksize, p->scaled)) != HG_OK) return s;
     // page-locked scratch of this path: the counters, the fetch block (count + first hashes of a one-genome call), the redo list
     const size_t cnt_bytes = (n * sizeof(uint32_t) + 63) & ~(size_t)63;
     const size_t fetch_n = (fetch && n == 1) ? std::min<size_t>({fetch->max_hashes, pl.meta[0].hit_cap, (size_t)1 << 16}) : 0;
     const size_t fetch_bytes = (fetch && n == 1) ? ((64 + fetch_n * 8 + 63) & ~(size_t)63) : 0;
     const size_t fetch_off = cnt_bytes, redo_off = cnt_bytes + fetch_bytes;
     if ((s = hg_ensure_pinned(c, redo_off + cnt_bytes + 64)) != HG_OK) return s;
+    uint32_t sort_cap = 0;
+    if ((s = hg_sketch_front(c, b, p, threshold, pl, false, &sort_cap)) != HG_OK) return s;
     auto *d_meta = static_cast<hg_genome_meta *>(c->w_gmeta.p);
-    auto *d_items = static_cast<uint32_t *>(c->w_items.p);
     auto *d_hits = static_cast<uint64_t *>(c->w_hits.p);
     auto *d_cnt = static_cast<uint32_t *>(c->w_cnt.p);
     uint32_t *d_nd = d_cnt + n;
     auto *h_cnt = static_cast<uint32_t *>(c->h_pin);
-    HG_HIP(c, hipMemsetAsync(d_cnt, 0, 2 * n * sizeof(uint32_t), c->stream));
-    {
-      hg_timed tm(c, HG_T_KMER);
-      c->last_kernel[HG_T_KMER] = hg_kmer_kernel_name(ksize, canonical, packed);
-      HG_HIP(c, hg_launch_kmer_sample(c->stream, d_seq, d_meta, d_items, (uint32_t)n_items, ksize, threshold,
-                                      seed, canonical, norm_mode, d_hits, d_cnt, packed,
-                                      hg_plan_group_table(c, n_items, pl.n_groups), (uint32_t)pl.n_groups));
-    }
-    uint32_t sort_cap = pl.max_cap;
-    {
-      // The LDS sort is sized by the genomes' CAPACITIES (twice the expected count + 1 024: 64 KiB for a 5 Mbp genome,
-      // two workgroups per CU).  When the plan is a repeat, the counts of its last run are known: size by those (+ 12.5 %,
-      // 32 KiB -> five workgroups per CU); a genome that outgrows it is left to the large-set path below, as always.
-      const uint32_t seen = reuse ? c->plan->max_hits : 0;
-      if (seen) sort_cap = (uint32_t)std::min<uint64_t>(sort_cap, (uint64_t)seen + seen / 8 + 16);
-      hg_timed tm(c, HG_T_SORT, HG_T_KMER);
-      c->last_kernel[HG_T_SORT].clear();  // (an attempt after an overflow reports its own launches)
-      HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold, nullptr,
-                                      &c->last_kernel[HG_T_SORT]));
-    }
     // overflow check on the raw counters (they keep counting past the capacity)
     HG_HIP(c, hipMemcpyAsync(h_cnt, d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     uint8_t *h_fetch = static_cast<uint8_t *>(c->h_pin) + fetch_off;
@@ -200,14 +174,12 @@ hg_status hg_sample_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *
   return hg_fail(c, HG_ERR_HIP, "hit buffer overflow persisted after resizing");
 }
 
-hg_status hg_sketch_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                               const hg_sketch_params *p, int16_t *d_hv, int32_t *d_norm2, uint32_t *d_nhash, bool packed,
-                               const uint64_t *mask_offs) {
-  hg_batch_tables pl;
+hg_status hg_sketch_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, const hg_sketch_out &out,
+                               hg_batch_tables *planned) {
+  hg_batch_tables pl = planned ? std::move(*planned) : hg_batch_tables{};
   uint32_t *d_nd = nullptr;
   const uint64_t threshold = UINT64_MAX / p->scaled;  // src/sketch.rs:73
-  hg_status s = hg_sample_batch_sync(c, d_seq, offsets, lens, n, p->ksize, threshold, p->scaled, p->seed, p->canonical != 0,
-                                     p->norm_mode, pl, &d_nd, packed, mask_offs, nullptr);
+  hg_status s = hg_sample_batch_sync(c, b, p, threshold, pl, planned != nullptr, &d_nd, nullptr);
   if (s != HG_OK) return s;
   // genomes with very large hash sets are encoded by several workgroups each (plan from the raw hit counts)
   hg_encode_split split{};
@@ -231,11 +203,11 @@ hg_status hg_sketch_batch_sync(hg_ctx *c, const uint8_t *d_seq, const uint64_t *
   {
     hg_timed tm(c, HG_T_ENCODE);
     c->last_kernel[HG_T_ENCODE].clear();
-    HG_HIP(c, hg_launch_encode(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), (uint32_t)n,
-                               static_cast<uint64_t *>(c->w_hits.p), d_nd, p->hv_d, p->hv_layout, d_hv, d_norm2,
+    HG_HIP(c, hg_launch_encode(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), (uint32_t)b.n,
+                               static_cast<uint64_t *>(c->w_hits.p), d_nd, p->hv_d, p->hv_layout, out.d_hv, out.d_norm2,
                                split.n_items ? &split : nullptr, pl.max_hits, &c->last_kernel[HG_T_ENCODE]));
   }
   if (split.n_items) HG_HIP(c, hipStreamSynchronize(c->stream));  // the pageable item tables must outlive their upload
-  HG_HIP(c, hipMemcpyAsync(d_nhash, d_nd, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+  HG_HIP(c, hipMemcpyAsync(out.d_nhash, d_nd, b.n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
   return HG_OK;
 }

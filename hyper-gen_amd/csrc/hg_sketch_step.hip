@@ -13,7 +13,8 @@
 // The flag word travels to a page-locked slot behind the last kernel, and the host reads it when the NEXT call on the ctx
 // (or hg_ctx_sync) arrives -- after that call's own kernels are queued, so the device never waits for the host.  A step
 // whose word is not zero is run again through the synchronous path (hg_sketch_rare.hip); that is rare by construction
-// (a sampled k-mer repeated thousands of times, or a set 2.4x its expected size).
+// (a sampled k-mer repeated thousands of times, or a set 2.4x its expected size).  That path starts with the same front
+// (hg_sketch_front: counters zeroed, k-mer launch, first sort launch) and, for a batch the step turned away, its plan.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -26,14 +27,18 @@
 
 namespace {
 
-// the sort launched first is sized for this many raw hits per genome: what the plan's last synchronous run saw, or the
-// expected count, + 12.5 % (seven standard deviations at 3 333)
-uint32_t first_sort_cap(const hg_sketch_plan &pl) {
-  const uint64_t base = pl.max_hits ? pl.max_hits : pl.max_expect;
-  // (a batch of genomes that sample at most ~35 k-mers each -- up to 50 kbp at scaled = 1 500 -- stays within the 64 keys one
-  // WAVE sorts: sort_unique_wave_kernel, four genomes per workgroup)
+// The first sort launch of both paths is sized for this many raw hits per genome.  seen: the largest raw count the last
+// synchronous run of the plan saw, when the plan was reused (0: none, or a fresh plan).
+uint32_t first_sort_cap(const hg_ctx *c, const hg_batch_tables &t, bool sync_free) {
+  const uint64_t seen = t.reused ? c->plan->max_hits : 0;
+  if (!sync_free)  // the capacity, or what was seen + 12.5 %: a genome that outgrows it is sorted again from the counters read back
+    return seen ? (uint32_t)std::min<uint64_t>(t.max_cap, seen + seen / 8 + 16) : t.max_cap;
+  // what was seen or the expected count, + 12.5 % (seven standard deviations at 3 333): the rest launch takes the genomes that
+  // outgrow it.  (A batch of genomes that sample at most ~35 k-mers each -- up to 50 kbp at scaled = 1 500 -- stays within
+  // the 64 keys one WAVE sorts: sort_unique_wave_kernel, four genomes per workgroup.)
+  const uint64_t base = seen ? seen : t.max_expect;
   const uint64_t margin = base + base / 8 + 24 <= 64 ? 24 : 64;
-  return (uint32_t)std::min<uint64_t>(pl.max_cap, base + base / 8 + margin);
+  return (uint32_t)std::min<uint64_t>(t.max_cap, base + base / 8 + margin);
 }
 
 // the batch can go without the host: every genome is EXPECTED to fit the one-workgroup sort (those that do not after all
@@ -75,12 +80,42 @@ hg_status wait_check_word(hg_ctx *c, int slot, uint32_t seq, uint32_t *flags) {
 
 hg_status redo_step(hg_ctx *c, const hg_sketch_pending &pd) {
   ++c->n_redone_steps;
-  const hg_sketch_plan &pl = *pd.plan;
-  return hg_sketch_batch_sync(c, pd.d_seq, pl.offs.data(), pl.lens.data(), pl.offs.size(), &pd.p, pd.d_hv, pd.d_norm2, pd.d_nhash,
-                              pl.packed, pl.masks.empty() ? nullptr : pl.masks.data());
+  return hg_sketch_batch_sync(c, pd.batch, &pd.p, pd.out);
 }
 
 }  // namespace
+
+hg_status hg_sketch_front(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, uint64_t threshold,
+                          const hg_batch_tables &t, bool sync_free, uint32_t *sort_cap) {
+  const size_t n = b.n;
+  hg_status s;
+  if ((s = hg_ensure(c, c->w_hits, t.total_slots * sizeof(uint64_t) + 16)) != HG_OK) return s;
+  if ((s = hg_ensure(c, c->w_cnt, (2 * n + 16) * sizeof(uint32_t) + 16)) != HG_OK) return s;
+  auto *d_meta = static_cast<hg_genome_meta *>(c->w_gmeta.p);
+  auto *d_hits = static_cast<uint64_t *>(c->w_hits.p);
+  auto *d_cnt = static_cast<uint32_t *>(c->w_cnt.p);
+  uint32_t *d_nd = d_cnt + n, *d_flags = sync_free ? d_cnt + 2 * n : nullptr;
+  HG_HIP(c, hipMemsetAsync(d_cnt, 0, (2 * n + (sync_free ? 16 : 0)) * sizeof(uint32_t), c->stream));
+  {
+    hg_timed tm(c, HG_T_KMER);
+    c->last_kernel[HG_T_KMER] = hg_kmer_kernel_name(p->ksize, p->canonical != 0, b.packed);
+    HG_HIP(c, hg_launch_kmer_sample(c->stream, b.d_seq, d_meta, static_cast<const uint32_t *>(c->w_items.p), (uint32_t)t.n_items,
+                                    p->ksize, threshold, p->seed, p->canonical != 0, p->norm_mode, d_hits, d_cnt, b.packed,
+                                    hg_plan_group_table(c, t.n_items, t.n_groups), (uint32_t)t.n_groups));
+  }
+  // The LDS sort sized by the genomes' CAPACITIES (twice the expected count + 1 024) takes 64 KiB for a 5 Mbp genome: two
+  // workgroups per CU.  Sized by the counts to be expected it takes 32 KiB -- five per CU --, and the few genomes that
+  // outgrow it are picked up by the second launch (sync-free: capacity-sized, its workgroups leave at once when there are
+  // none) or from the counters read back (synchronous).
+  *sort_cap = first_sort_cap(c, t, sync_free);
+  hg_timed tm(c, HG_T_SORT, HG_T_KMER);
+  std::string *names = &c->last_kernel[HG_T_SORT];
+  names->clear();  // (an attempt after an overflow reports its own launches)
+  HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, threshold, d_flags, names));
+  if (sync_free)
+    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, t.max_cap, threshold, names));
+  return HG_OK;
+}
 
 hg_status hg_sketch_resolve(hg_ctx *c, bool *redone) {
   if (redone) *redone = false;
@@ -94,18 +129,18 @@ hg_status hg_sketch_resolve(hg_ctx *c, bool *redone) {
   return redo_step(c, pd);
 }
 
-hg_status hg_sketch_step(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offsets, const uint64_t *lens, size_t n,
-                         const hg_sketch_params *p, int16_t *d_hv, int32_t *d_norm2, uint32_t *d_nhash, bool packed,
-                         const uint64_t *mask_offs) {
+hg_status hg_sketch_step(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_params *p, const hg_sketch_out &out) {
   // (entered with the previous step's check word unread: it is looked at below, behind this step's launches)
+  const size_t n = b.n;
   hg_status s;
   hg_batch_tables t;
-  const bool reuse = hg_plan_matches(c, offsets, lens, mask_offs, n, p->ksize, p->scaled, packed);
-  if (reuse) hg_plan_tables_from_cache(*c->plan, n, t, false);
-  else if ((s = hg_plan_build(c, offsets, lens, n, p->ksize, p->scaled, nullptr, t, mask_offs)) != HG_OK) return s;
+  if ((s = hg_plan_get(c, b, p->ksize, p->scaled, t, false)) != HG_OK) return s;
   if (!step_can_be_sync_free(c, t, n)) {
-    if ((s = hg_sketch_resolve(c)) != HG_OK) return s;
-    return hg_sketch_batch_sync(c, d_seq, offsets, lens, n, p, d_hv, d_norm2, d_nhash, packed, mask_offs);
+    bool redone = false;
+    if ((s = hg_sketch_resolve(c, &redone)) != HG_OK) return s;
+    // the plan goes along (with the records the synchronous path reads) unless a re-run may have replaced the ctx's one
+    if (!redone && t.reused) hg_plan_tables_from_cache(*c->plan, n, t);
+    return hg_sketch_batch_sync(c, b, p, out, redone ? nullptr : &t);
   }
   if (!c->h_chk) {
     void *q = nullptr;
@@ -115,51 +150,31 @@ hg_status hg_sketch_step(hg_ctx *c, const uint8_t *d_seq, const uint64_t *offset
     c->h_chk = static_cast<uint32_t *>(q);
     std::memset(c->h_chk, 0, 32 * sizeof(uint32_t));
   }
-  if (!reuse && (s = hg_plan_upload(c, t, offsets, lens, mask_offs, n, p->ksize, p->scaled, packed)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_hits, t.total_slots * sizeof(uint64_t) + 16)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_cnt, (2 * n + 16) * sizeof(uint32_t) + 16)) != HG_OK) return s;
-  auto *d_meta = static_cast<hg_genome_meta *>(c->w_gmeta.p);
-  auto *d_items = static_cast<uint32_t *>(c->w_items.p);
-  auto *d_hits = static_cast<uint64_t *>(c->w_hits.p);
-  auto *d_cnt = static_cast<uint32_t *>(c->w_cnt.p);
-  uint32_t *d_nd = d_cnt + n, *d_flags = d_cnt + 2 * n;
+  if ((s = hg_plan_commit(c, t, b, p->ksize, p->scaled)) != HG_OK) return s;
   const uint64_t threshold = UINT64_MAX / p->scaled;  // src/sketch.rs:73
-  const uint32_t seq = ++c->chk_seq ? c->chk_seq : ++c->chk_seq;  // never 0
-  const int slot = (int)(seq & 1u);
-
-  HG_HIP(c, hipMemsetAsync(d_cnt, 0, (2 * n + 16) * sizeof(uint32_t), c->stream));
+  uint32_t sort_cap = 0;
+  if ((s = hg_sketch_front(c, b, p, threshold, t, true, &sort_cap)) != HG_OK) return s;
+  // the slot the step still unread does not hold; the sequence number counts only steps whose finish kernel was queued
+  const int slot = c->pending.active ? 1 - c->pending.slot : 0;
+  const uint32_t seq = c->chk_seq + 1 ? c->chk_seq + 1 : 1;  // never 0
   {
-    hg_timed tm(c, HG_T_KMER);
-    c->last_kernel[HG_T_KMER] = hg_kmer_kernel_name(p->ksize, p->canonical != 0, packed);
-    HG_HIP(c, hg_launch_kmer_sample(c->stream, d_seq, d_meta, d_items, (uint32_t)t.n_items, p->ksize, threshold, p->seed,
-                                    p->canonical != 0, p->norm_mode, d_hits, d_cnt, packed,
-                                    hg_plan_group_table(c, t.n_items, t.n_groups), (uint32_t)t.n_groups));
-  }
-  {
-    // The LDS sort sized by the genomes' CAPACITIES (twice the expected count + 1 024) takes 64 KiB for a 5 Mbp genome: two
-    // workgroups per CU.  Sized by the counts to be expected it takes 32 KiB -- five per CU --, and the few genomes that
-    // outgrow it are picked up by the second launch (capacity-sized; its workgroups leave at once when there are none).
-    const uint32_t sort_cap = first_sort_cap(*c->plan);
-    hg_timed tm(c, HG_T_SORT, HG_T_KMER);
-    std::string *names = &c->last_kernel[HG_T_SORT];
-    names->clear();
-    HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, threshold, d_flags, names));
-    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, sort_cap, t.max_cap, threshold, names));
-  }
-  {
+    auto *d_cnt = static_cast<uint32_t *>(c->w_cnt.p);
+    uint32_t *d_nd = d_cnt + n, *d_flags = d_cnt + 2 * n;
     hg_timed tm(c, HG_T_ENCODE, HG_T_SORT);
     std::string *names = &c->last_kernel[HG_T_ENCODE];
     names->clear();
-    HG_HIP(c, hg_launch_encode(c->stream, d_meta, (uint32_t)n, d_hits, d_nd, p->hv_d, p->hv_layout, d_hv, d_norm2, nullptr,
+    HG_HIP(c, hg_launch_encode(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), (uint32_t)n, static_cast<uint64_t *>(c->w_hits.p),
+                               d_nd, p->hv_d, p->hv_layout, out.d_hv, out.d_norm2, nullptr,
                                std::min<uint32_t>(t.max_cap, HG_SORT_LDS_MAX_KEYS), names));
-    HG_HIP(c, hg_launch_sketch_finish(c->stream, d_nd, d_nhash, (uint32_t)n, d_flags, c->h_chk + 16 * slot, seq, names));
+    HG_HIP(c, hg_launch_sketch_finish(c->stream, d_nd, out.d_nhash, (uint32_t)n, d_flags, c->h_chk + 16 * slot, seq, names));
   }
+  c->chk_seq = seq;
   ++c->n_fast_steps;
 
-  // this step is queued: now the previous one's check word (its slot is the other one)
-  hg_sketch_pending cur;
-  cur.active = true, cur.seq = seq, cur.slot = slot, cur.plan = c->plan;
-  cur.d_seq = d_seq, cur.p = *p, cur.d_hv = d_hv, cur.d_norm2 = d_norm2, cur.d_nhash = d_nhash;
+  // this step is queued: now the previous one's check word
+  const hg_sketch_plan &pl = *c->plan;  // (its copies of the host arrays live as long as the pending step)
+  hg_sketch_pending cur{true, seq, slot, c->plan,
+                        {b.d_seq, pl.offs.data(), pl.lens.data(), pl.masks.empty() ? nullptr : pl.masks.data(), b.n, b.packed}, *p, out};
   bool redone = false;
   if ((s = hg_sketch_resolve(c, &redone)) != HG_OK) return s;
   if (redone) {
