@@ -1,11 +1,12 @@
 // hg_block_scan.h -- block-wide scan primitives shared by the device kernels (hg_hits.hip: radix sort; hg_cluster.hip: dense
-// cluster ids).
+// cluster ids; hg_sort_kernels.hip: counting sort and unique).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// block-wide exclusive scan of one value per thread (256 threads); returns the block total through *total
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *s_wave /* 4 words */, uint32_t *total) {
+// block-wide exclusive scan of one value per thread (WAVES * 64 threads); returns the block total through *total
+template <uint32_t WAVES>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave /* WAVES words */, uint32_t *total) {
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t inc = v;
 #pragma unroll
@@ -17,7 +18,7 @@ __device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *s_
   __syncthreads();
   uint32_t before = 0, all = 0;
 #pragma unroll
-  for (uint32_t w = 0; w < 4; ++w) {
+  for (uint32_t w = 0; w < WAVES; ++w) {
     const uint32_t t = s_wave[w];
     before += w < wave ? t : 0u, all += t;
   }

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void cluster_compress_kernel(uint32_t *rep, ui
     rep_store(rep, (uint32_t)i, r);
   }
   uint32_t total;
-  (void)block_excl_scan_256(roots, s_wave, &total);
+  (void)block_excl_scan<4>(roots, s_wave, &total);
   if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
 }
 
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void cluster_scan_tiles_kernel(uint32_t *__res
   for (uint32_t t0 = 0; t0 < n_tiles; t0 += 256) {
     const uint32_t t = t0 + threadIdx.x, v = t < n_tiles ? tile_cnt[t] : 0u;
     uint32_t tot;
-    const uint32_t ex = block_excl_scan_256(v, s_wave, &tot);
+    const uint32_t ex = block_excl_scan<4>(v, s_wave, &tot);
     if (t < n_tiles) tile_cnt[t] = running + ex;
     running += tot;
   }
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void cluster_root_ids_kernel(const uint32_t *_
     const size_t i = base + j * 256 + threadIdx.x;
     const uint32_t root = i < n && rep[i] == (uint32_t)i;
     uint32_t tot;
-    const uint32_t ex = block_excl_scan_256(root, s_wave, &tot);
+    const uint32_t ex = block_excl_scan<4>(root, s_wave, &tot);
     if (root) cluster[i] = run + ex;
     run += tot;
   }

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void radix_scan_kernel(uint32_t *__restrict__ 
   for (uint32_t c = 0; c < n_blocks; c += 256) {
     const uint32_t i = c + threadIdx.x, v = i < n_blocks ? row[i] : 0u;
     uint32_t tot;
-    const uint32_t ex = block_excl_scan_256(v, s_wave, &tot);
+    const uint32_t ex = block_excl_scan<4>(v, s_wave, &tot);
     if (i < n_blocks) row[i] = running + ex;
     running += tot;
   }
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(const K *__restrict_
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   {
     uint32_t tot;
-    const uint32_t dbase = block_excl_scan_256(totals[threadIdx.x], s_wave, &tot);
+    const uint32_t dbase = block_excl_scan<4>(totals[threadIdx.x], s_wave, &tot);
     s_base[threadIdx.x] = dbase + counts[(size_t)threadIdx.x * n_blocks + blockIdx.x];
 #pragma unroll
     for (uint32_t w = 0; w < 4; ++w) s_cnt[w][threadIdx.x] = 0;

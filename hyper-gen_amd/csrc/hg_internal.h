@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <string>
 #include <vector>
@@ -254,6 +255,13 @@ inline void hg_note_launch(std::string *launched, const char *name) {
   if (!launched) return;
   if (!launched->empty()) *launched += " + ";
   *launched += name;
+}
+// hipFuncSetAttribute is per device: remember per device (one context per GPU may live in one process)
+inline bool attr_done_on_this_device(std::atomic<uint64_t> &mask, bool set) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) return false;
+  if (set) mask.fetch_or(1ull << dev);
+  return (mask.load() >> dev) & 1;
 }
 // Sorts each genome's hits ascending, removes duplicates in place (region start),
 // d_ndistinct[g] = distinct count.  max_cnt_pow2 bounds the LDS sort size.

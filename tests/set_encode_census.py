@@ -40,7 +40,7 @@ ROWS = [
 ENTRIES = ("hv_encode", "sketch_batch_dev", "sync")
 
 # ---- the dispatch, on the host ----------------------------------------------------------------------------------------
-# Kernel constants (hg_encode_kernels.hip / hg_internal.h).  The batch quantities -- every genome's hit region, the largest
+# Kernel constants (hg_sort_kernels.hip / hg_encode_kernels.hip / hg_internal.h).  The batch quantities -- every genome's hit region, the largest
 # region, the largest expected count -- come from hg_sketch_plan_describe.
 LDS_MAX_KEYS = 8192      # HG_SORT_LDS_MAX_KEYS
 SORT_WG = 512
