@@ -42,7 +42,7 @@ class HgError(RuntimeError):
 class SketchParams(C.Structure):
     _fields_ = [("ksize", C.c_uint32), ("canonical", C.c_uint32), ("scaled", C.c_uint64),
                 ("seed", C.c_uint64), ("hv_d", C.c_uint32), ("hv_layout", C.c_uint32),
-                ("norm_mode", C.c_uint32), ("reserved", C.c_uint32)]
+                ("norm_mode", C.c_uint32), ("min_count", C.c_uint32)]
 
 
 class AniHit(C.Structure):
@@ -64,6 +64,7 @@ EXPORTS = [
     "hg_status_str", "hg_last_error", "hg_version", "hg_ctx_create", "hg_ctx_destroy",
     "hg_ctx_set_stream", "hg_ctx_reset_stream", "hg_ctx_sync", "hg_ctx_sketch_step_counts", "hg_sketch_plan_describe", "hg_logf_dev", "hg_ani_from_dots_dev", "hg_device_count", "hg_dev_alloc", "hg_dev_free",
     "hg_copy_h2d", "hg_copy_d2h", "hg_sketch_params_default", "hg_kmer_hash_sample",
+    "hg_kmer_hash_sample_min_count",
     "hg_hv_encode", "hg_sketch_batch_dev", "hg_sketch_batch", "hg_dist_full", "hg_dist_full_dev",
     "hg_dist", "hg_dist_dev", "hg_sort_ani_hits", "hg_hv_quant_bits", "hg_hv_pack", "hg_hv_packed_bytes",
     "hg_hv_unpack", "hg_sketch_file_write", "hg_sketch_file_read", "hg_sketch_file_count",
@@ -156,6 +157,8 @@ def lib():
         "hg_sketch_params_default": (None, [C.POINTER(SketchParams)]),
         "hg_kmer_hash_sample": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
                                           C.c_uint32, vp, sz, C.POINTER(sz)]),
+        "hg_kmer_hash_sample_min_count": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int,
+                                                    C.c_uint32, C.c_uint32, vp, sz, C.POINTER(sz)]),
         "hg_hv_encode": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_int32)]),
         "hg_sketch_batch_dev": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(SketchParams), vp, vp, vp]),
         "hg_sketch_batch": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(SketchParams),
@@ -292,6 +295,7 @@ def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_fir
 
 
 def default_params(**kw):
+    """hg_sketch_params_default, then the fields given by name (min_count=2 keeps the sampled k-mers seen at least twice)."""
     p = SketchParams()
     lib().hg_sketch_params_default(C.byref(p))
     for k, v in kw.items():
@@ -383,7 +387,8 @@ class Context:
 
     # ---- host-buffer entry points -----------------------------------------------------------
     def kmer_hash_sample(self, seq, ksize=21, scaled=1500, seed=123, canonical=True,
-                         norm=NORM_ACGT, threshold=None, cap=None):
+                         norm=NORM_ACGT, threshold=None, cap=None, min_count=1):
+        """The distinct sampled hashes, ascending; min_count > 1: those that occur at least that often (hg_kmer_hash_sample_min_count)."""
         a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq,
                                  dtype=np.uint8)
         thr = (2**64 - 1) // scaled if threshold is None else threshold
@@ -391,9 +396,14 @@ class Context:
         while True:
             out = np.zeros(max(cap, 1), np.uint64)
             n = C.c_size_t(0)
-            st = lib().hg_kmer_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize,
-                                           C.c_uint64(thr), C.c_uint64(seed), int(canonical), norm,
-                                           _ptr(out), cap, C.byref(n))
+            if min_count > 1:
+                st = lib().hg_kmer_hash_sample_min_count(self._h, _ptr(a) if a.size else None, a.size, ksize,
+                                                         C.c_uint64(thr), C.c_uint64(seed), int(canonical), norm, min_count,
+                                                         _ptr(out), cap, C.byref(n))
+            else:
+                st = lib().hg_kmer_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize,
+                                               C.c_uint64(thr), C.c_uint64(seed), int(canonical), norm,
+                                               _ptr(out), cap, C.byref(n))
             if st == ERR_CAPACITY:
                 cap = n.value
                 continue

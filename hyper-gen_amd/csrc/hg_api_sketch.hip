@@ -462,6 +462,12 @@ extern "C" hg_status hg_sketch_batch(hg_ctx *c, const uint8_t *const *seqs, cons
 extern "C" hg_status hg_kmer_hash_sample(hg_ctx *c, const uint8_t *seq, size_t n_bps, uint32_t ksize,
                                          uint64_t threshold, uint64_t seed, int canonical, uint32_t norm_mode,
                                          uint64_t *out_hashes, size_t cap, size_t *n_out) {
+  return hg_kmer_hash_sample_min_count(c, seq, n_bps, ksize, threshold, seed, canonical, norm_mode, 1, out_hashes, cap, n_out);
+}
+
+extern "C" hg_status hg_kmer_hash_sample_min_count(hg_ctx *c, const uint8_t *seq, size_t n_bps, uint32_t ksize,
+                                                   uint64_t threshold, uint64_t seed, int canonical, uint32_t norm_mode,
+                                                   uint32_t min_count, uint64_t *out_hashes, size_t cap, size_t *n_out) {
   if (!c) return HG_ERR_INVALID;
   if (!n_out) return hg_fail(c, HG_ERR_INVALID, "n_out == NULL");
   *n_out = 0;
@@ -493,7 +499,7 @@ extern "C" hg_status hg_kmer_hash_sample(hg_ctx *c, const uint8_t *seq, size_t n
   uint64_t scaled = threshold ? UINT64_MAX / threshold : UINT64_MAX;
   if (scaled < 1) scaled = 1;
   const hg_genome_batch b{static_cast<uint8_t *>(c->w_seq.p), offs.data(), l64.data(), nullptr, 1, packed};
-  const hg_sketch_params p{ksize, canonical != 0, scaled, seed, 0, 0, norm_mode, 0};  // (no encode)
+  const hg_sketch_params p{ksize, canonical != 0, scaled, seed, 0, 0, norm_mode, min_count};  // (no encode)
   hg_batch_tables pl;
   uint32_t *d_nd = nullptr;
   hg_sample_fetch fetch;

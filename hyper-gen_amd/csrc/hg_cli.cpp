@@ -76,6 +76,8 @@ struct Cli {
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
   float quant_scale = 1.0f, ani_th = 85.0f;
   bool ani_th_given = false;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
+  unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
+  bool min_count_given = false;
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
 };
 
@@ -104,7 +106,9 @@ Cli parse(int argc, char **argv) {
                 "         cluster: containment = the share of the query's hashes found in the reference -- the identity of a\n"
                 "         fragment, a partial MAG or a draft with a larger genome; max_containment = the same against the\n"
                 "         smaller of the two; dist on one file with containment writes every ordered pair i != j; cluster\n"
-                "         takes mash or max_containment)\n");
+                "         takes mash or max_containment), --min_count N [1] (sketch: keep a sampled k-mer only if it occurs\n"
+                "         at least N times in the file -- for raw reads, where every sequencing error makes k-mers that occur\n"
+                "         once; 1 = every sampled k-mer, the reference's set)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -112,7 +116,8 @@ Cli parse(int argc, char **argv) {
   static const std::map<std::string, char> longs = {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
-      {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'}};
+      {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
+      {"min_count", '\x02'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -167,6 +172,10 @@ Cli parse(int argc, char **argv) {
         else if (val == "max_containment") c.ani_metric = HG_ANI_MAX_CONTAINMENT;
         else die("invalid value '" + val + "' for '--ani_metric' (mash | containment | max_containment)");
         break;  // dist / search only (cluster rejects it) (testing aid: the several-GPU path on fewer GPUs)
+      case '\x02':  // (long form only) sketch only (extension)
+        c.min_count = (unsigned)u(0xFFFFFFFFull), c.min_count_given = true;
+        if (c.min_count == 0) die("invalid value '" + val + "' for '" + a + "'");
+        break;
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -175,6 +184,7 @@ Cli parse(int argc, char **argv) {
       default: die("unexpected argument '" + a + "'");
     }
   }
+  if (c.min_count_given && c.mode != "sketch") die("--min_count is not supported by " + c.mode + ": the filter needs the k-mer counts, which a sketch no longer has");
   return c;
 }
 
@@ -237,6 +247,7 @@ int run_sketch(const Cli &c) {
   p.canonical = gpu_mode ? (c.canonical ? 1u : 0u) : 1u;
   p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2;
   p.norm_mode = gpu_mode ? HG_NORM_ACGT : HG_NORM_U2T;
+  p.min_count = c.min_count;
   const uint32_t read_mode = gpu_mode ? HG_READ_MERGE : HG_READ_NEEDLETAIL;
 
   std::vector<std::vector<int16_t>> payload(n);

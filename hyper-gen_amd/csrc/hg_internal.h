@@ -270,7 +270,9 @@ inline bool attr_done_on_this_device(std::atomic<uint64_t> &mask, bool set) {
 uint32_t hg_sort_lds_keys(uint32_t max_cap);
 hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo, uint32_t n_todo,
                                       uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t max_cap,
-                                      uint64_t threshold, std::string *launched = nullptr);
+                                      uint64_t threshold, uint32_t min_count, std::string *launched = nullptr);
+// min_count (hg_sketch_params): <= 1 launches the sort_unique_* / bucket_sort kernels, which keep every key once; > 1 their
+// min_count_* forms, which keep the keys that occur at least that often.  The front ends below choose; no caller does.
 // (threshold: every key is below it -- the sampling threshold; it scales the buckets of the counting-sort fast path,
 // 0 = bitonic only)
 // d_flags != nullptr (the sync-free step): a genome whose raw count exceeds its hit region (HG_STEP_OVERFLOW) or the
@@ -278,7 +280,7 @@ hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_me
 // HG_NHASH_PENDING, which the encoders skip.
 hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                                  uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags = nullptr,
+                                 uint32_t max_cap, uint64_t threshold, uint32_t min_count, uint32_t *d_flags = nullptr,
                                  std::string *launched = nullptr);
 #define HG_STEP_OVERFLOW 1u
 #define HG_STEP_LARGE_SET 2u
@@ -286,7 +288,7 @@ hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, u
 // the workgroups find them in the counters themselves -- no list from the host.
 hipError_t hg_launch_sort_unique_rest(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes, uint64_t *d_hits,
                                       const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t done_cap, uint32_t max_cap,
-                                      uint64_t threshold, std::string *launched = nullptr);
+                                      uint64_t threshold, uint32_t min_count, std::string *launched = nullptr);
 // Last kernel of a sync-free step: d_nhash[g] = d_ndistinct[g], and the step's flag word goes to the page-locked
 // check slot with the step's sequence number behind it (h_slot[0] = flags, h_slot[1] = seq).
 hipError_t hg_launch_sketch_finish(hipStream_t st, const uint32_t *d_ndistinct, uint32_t *d_nhash, uint32_t n_genomes,
@@ -309,11 +311,12 @@ struct hg_bucket_job {
 hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uint32_t n_jobs,
                                 const uint32_t *d_chunk_job, uint32_t n_chunks, const uint32_t *d_bucket_job,
                                 uint32_t n_buckets, uint32_t *d_bk, uint64_t *d_hits, uint64_t *d_tmp,
-                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, std::string *launched = nullptr);
+                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, uint32_t min_count,
+                                std::string *launched = nullptr);
 // in-place global-memory sort + unique of the listed genomes (power-of-two sized hit regions)
 hipError_t hg_launch_sort_inplace(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo,
                                   uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                  std::string *launched = nullptr);
+                                  uint32_t min_count, std::string *launched = nullptr);
 
 // Genomes with more than HG_ENC_SLAB distinct hashes can be encoded by several workgroups: d_items[i] =
 // {genome, slab | slot << 16} for every slab of HG_ENC_SLAB hashes (planned from an upper bound of the distinct

@@ -12,7 +12,7 @@
 // Sorts + de-duplicates the genomes whose sampled hash count exceeds what one workgroup sorts in LDS.
 // h_cnt: raw per-genome counters (host copy).  Synchronises the stream when it had work to do.
 static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uint32_t *h_cnt, size_t n, uint64_t threshold,
-                                 uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_nd) {
+                                 uint32_t min_count, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_nd) {
   // keys per bucket aimed at (512-1 024 land in one; the sort's LDS is sized for four times that, hg_launch_sort_large) /
   // buckets per genome
   constexpr uint32_t TARGET = 1024, MAX_BUCKETS = 16384;
@@ -67,7 +67,7 @@ static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uin
       hg_timed tm(c, HG_T_SORT);
       HG_HIP(c, hg_launch_sort_large(c->stream, d_jobs, (uint32_t)jobs.size(), d_chunk, (uint32_t)chunk_job.size(), d_bucket,
                                      (uint32_t)bucket_job.size(), d_bk, d_hits, static_cast<uint64_t *>(c->w_hits2.p), d_nd,
-                                     c->dbg_sort_buckets ? HG_SORT_LDS_MAX_KEYS : cap_keys, &c->last_kernel[HG_T_SORT]));
+                                     c->dbg_sort_buckets ? HG_SORT_LDS_MAX_KEYS : cap_keys, min_count, &c->last_kernel[HG_T_SORT]));
     }
     HG_HIP(c, hipMemcpyAsync(fail.data(), d_bk + 5 * bucket_job.size(), jobs.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HG_HIP(c, hipStreamSynchronize(c->stream));  // also keeps the host vectors alive until the uploads are done
@@ -79,7 +79,7 @@ static hg_status sort_large_sets(hg_ctx *c, const hg_batch_tables &pl, const uin
     {
       hg_timed tm(c, HG_T_SORT);
       HG_HIP(c, hg_launch_sort_inplace(c->stream, static_cast<hg_genome_meta *>(c->w_gmeta.p), d_todo, (uint32_t)inplace.size(),
-                                       d_hits, d_cnt, d_nd, &c->last_kernel[HG_T_SORT]));
+                                       d_hits, d_cnt, d_nd, min_count, &c->last_kernel[HG_T_SORT]));
     }
     HG_HIP(c, hipStreamSynchronize(c->stream));
   }
@@ -143,12 +143,12 @@ hg_status hg_sample_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_ske
           HG_HIP(c, hipMemcpyAsync(c->w_redo.p, h_redo, n_redo * 4, hipMemcpyHostToDevice, c->stream));
           hg_timed tm(c, HG_T_SORT);
           HG_HIP(c, hg_launch_sort_unique_todo(c->stream, d_meta, static_cast<uint32_t *>(c->w_redo.p), (uint32_t)n_redo,
-                                               d_hits, d_cnt, d_nd, pl.max_cap, threshold, &c->last_kernel[HG_T_SORT]));
+                                               d_hits, d_cnt, d_nd, pl.max_cap, threshold, p->min_count, &c->last_kernel[HG_T_SORT]));
           HG_HIP(c, hipStreamSynchronize(c->stream));  // (rare path; the next call may rewrite the scratch at once)
         }
       }
       // hash sets beyond the LDS sort: bucketed multi-workgroup sort (or, where that cannot work, in place)
-      if ((s = sort_large_sets(c, pl, h_cnt, n, threshold, d_hits, d_cnt, d_nd)) != HG_OK) return s;
+      if ((s = sort_large_sets(c, pl, h_cnt, n, threshold, p->min_count, d_hits, d_cnt, d_nd)) != HG_OK) return s;
       pl.big.clear();
       pl.max_hits = 0;
       for (size_t g = 0; g < n; ++g) {

@@ -111,9 +111,9 @@ hg_status hg_sketch_front(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_p
   hg_timed tm(c, HG_T_SORT, HG_T_KMER);
   std::string *names = &c->last_kernel[HG_T_SORT];
   names->clear();  // (an attempt after an overflow reports its own launches)
-  HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, threshold, d_flags, names));
+  HG_HIP(c, hg_launch_sort_unique(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, threshold, p->min_count, d_flags, names));
   if (sync_free)
-    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, t.max_cap, threshold, names));
+    HG_HIP(c, hg_launch_sort_unique_rest(c->stream, d_meta, (uint32_t)n, d_hits, d_cnt, d_nd, *sort_cap, t.max_cap, threshold, p->min_count, names));
   return HG_OK;
 }
 

@@ -111,8 +111,15 @@ __device__ __forceinline__ bool counting_sort_lds(const uint64_t *__restrict__ s
 // i - 1 neighbour included -- before any of it is written, and written before the next is read; the destination index never
 // exceeds the source index, so no unread element is overtaken.  Otherwise (LDS -> global memory) src is only read: the scan's
 // own barriers are the only ones.
-template <bool IN_PLACE>
-__device__ __forceinline__ uint32_t unique_scatter(const uint64_t *src, const uint32_t n, uint64_t *dst, uint32_t *s_scan) {
+// MINC (min_count = m >= 2): the start of a run survives iff the run is at least m long -- in an ascending list, iff the element
+// m - 1 places ahead equals it: one more read, ahead of the chunk.  IN_PLACE that read is safe for the reason above: every write
+// of this and the earlier chunks went to an index below the running count `base` of survivors, and the elements from `base` on
+// still hold what the sort left there (base <= c0 <= i, and where base == i every element so far survived and was written
+// onto itself); the look-ahead only reads at i + m - 1 >= i, and the barrier between a chunk's reads and its writes covers it
+// like the i - 1 read.
+template <bool IN_PLACE, bool MINC = false>
+__device__ __forceinline__ uint32_t unique_scatter(const uint64_t *src, const uint32_t n, uint64_t *dst, uint32_t *s_scan,
+                                                   const uint32_t m = 1) {
   const uint32_t tid = threadIdx.x;
   uint32_t base = 0;
   for (uint32_t c0 = 0; c0 < n; c0 += SORT_WG) {
@@ -122,6 +129,7 @@ __device__ __forceinline__ uint32_t unique_scatter(const uint64_t *src, const ui
     if (i < n) {
       v = src[i];
       keep = (i == 0 || v != src[i - 1]) ? 1u : 0u;
+      if constexpr (MINC) keep = (keep && m - 1 < n - i && src[i + (m - 1)] == v) ? 1u : 0u;
     }
     if (IN_PLACE) __syncthreads();
     uint32_t total;
@@ -134,9 +142,10 @@ __device__ __forceinline__ uint32_t unique_scatter(const uint64_t *src, const ui
 }
 
 // Up to 64 keys ordered and de-duplicated by ONE wave in registers (lane = the calling lane, 0..63): a 64-lane bitonic
-// network over shuffles, no LDS, no barrier.
+// network over shuffles, no LDS, no barrier.  MINC: a run start survives iff the key m - 1 lanes up equals it (m > 64: none can).
+template <bool MINC = false>
 __device__ __forceinline__ void sort_unique_wave(uint64_t *__restrict__ region, const uint32_t n, const uint32_t lane,
-                                                 uint32_t *__restrict__ nd_out) {
+                                                 uint32_t *__restrict__ nd_out, const uint32_t m = 1) {
   uint64_t key = lane < n ? region[lane] : ~0ull;  // hashes are < threshold < ~0
 #pragma unroll
   for (uint32_t k = 2; k <= 64; k <<= 1)
@@ -149,7 +158,12 @@ __device__ __forceinline__ void sort_unique_wave(uint64_t *__restrict__ region, 
       key = (take_min == (other < key)) ? other : key;
     }
   const uint64_t prev = ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(key >> 32), 1) << 32) | (uint32_t)__shfl_up((int)(uint32_t)key, 1);
-  const bool keep = lane < n && (lane == 0 || key != prev);
+  bool keep = lane < n && (lane == 0 || key != prev);
+  if constexpr (MINC) {
+    const int from = (int)((lane + m - 1) & 63u);  // (every lane takes part in the shuffle; the lanes it is meant for are picked below)
+    const uint64_t ahead = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(key >> 32), from) << 32) | (uint32_t)__shfl((int)(uint32_t)key, from);
+    keep = keep && m <= 64 && lane + m - 1 < n && ahead == key;
+  }
   const unsigned long long kb = __ballot(keep);
   if (keep) region[__popcll(kb & ((1ull << lane) - 1ull))] = key;  // (every key was read before the first one is written)
   if (lane == 0) *nd_out = (uint32_t)__popcll(kb);
@@ -159,10 +173,12 @@ __device__ __forceinline__ void sort_unique_wave(uint64_t *__restrict__ region, 
 // LDS (lds_keys of them, then as many counters if bucket_mul != 0); otherwise the sort runs in place in the genome's hit region
 // (which must have next_pow2(n) slots).  Returns early -- whole waves, or the whole workgroup -- on the paths that need no
 // barrier; a caller that loops over genomes puts a barrier between them.
-template <bool USE_LDS>
+// MINC: only the keys that occur at least m (>= 2) times survive.  Sort first, then unique_scatter's look-ahead: a set this
+// size is one workgroup's work either way, and the sort it has is the one the de-duplicating form is tuned with.
+template <bool USE_LDS, bool MINC = false>
 __device__ __forceinline__ void sort_unique_one(const uint32_t g, const hg_genome_meta &gm, const uint32_t n,
                                                 uint64_t *__restrict__ hits, uint32_t *__restrict__ ndistinct,
-                                                const uint32_t lds_keys, const uint64_t bucket_mul) {
+                                                const uint32_t lds_keys, const uint64_t bucket_mul, const uint32_t m = 1) {
   extern __shared__ __attribute__((aligned(16))) uint64_t s_keys[];
   __shared__ uint32_t s_scan[SORT_WG / 64];
   uint64_t *region = hits + gm.hit_off;
@@ -171,7 +187,7 @@ __device__ __forceinline__ void sort_unique_one(const uint32_t g, const hg_genom
   const uint32_t tid = threadIdx.x;
 
   if (n <= 1) {
-    if (tid == 0) ndistinct[g] = n;
+    if (tid == 0) ndistinct[g] = (!MINC || n >= m) ? n : 0u;
     return;
   }
   uint32_t nd;
@@ -182,7 +198,7 @@ __device__ __forceinline__ void sort_unique_one(const uint32_t g, const hg_genom
       // leave.  (Through the workgroup-wide network with its barrier per pass, 100 000 such genomes took 0.96 ms; the k-mer
       // kernel of the same batch 9.3 ms.)
       if (tid >= 64) return;  // whole waves
-      sort_unique_wave(region, n, tid, ndistinct + g);
+      sort_unique_wave<MINC>(region, n, tid, ndistinct + g, m);
       return;
     }
     if (bucket_mul != 0 && n >= (uint32_t)SORT_WG) {
@@ -199,12 +215,12 @@ __device__ __forceinline__ void sort_unique_one(const uint32_t g, const hg_genom
       __syncthreads();
       bitonic_sort(s_keys, n2, tid, SORT_WG);
     }
-    nd = unique_scatter<false>(s_keys, n, region, s_scan);
+    nd = unique_scatter<false, MINC>(s_keys, n, region, s_scan, m);
   } else {
     for (uint32_t i = n + tid; i < n2; i += SORT_WG) region[i] = ~0ull;  // hashes are < threshold < ~0
     __syncthreads();
     bitonic_sort(region, n2, tid, SORT_WG);
-    nd = unique_scatter<true>(region, n, region, s_scan);
+    nd = unique_scatter<true, MINC>(region, n, region, s_scan, m);
   }
   if (tid == 0) ndistinct[g] = nd;
 }
@@ -226,44 +242,75 @@ __device__ __forceinline__ bool sort_step_guard(uint32_t &n, const uint32_t cap,
   return true;
 }
 
+// The kernels below come in two families with one body each: sort_unique_* / bucket_sort_kernel keep every key once
+// (min_count <= 1, the reference's HashSet), min_count_* keep the keys that occur at least m >= 2 times.  The body is a
+// device function with the MINC flag, so the first family compiles to what it was before the second existed.
+
 // One workgroup per genome (of the todo list, if there is one).
+template <bool USE_LDS, bool MINC>
+__device__ __forceinline__ void sort_unique_body(const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits,
+                                                 const uint32_t *__restrict__ cnt, uint32_t *__restrict__ ndistinct, uint32_t lds_keys,
+                                                 const uint32_t *__restrict__ todo, uint64_t bucket_mul, uint32_t *__restrict__ flags,
+                                                 const uint32_t m) {
+  const uint32_t g = todo ? todo[blockIdx.x] : blockIdx.x;
+  const hg_genome_meta gm = meta[g];
+  uint32_t n = cnt[g];
+  if (!sort_step_guard(n, gm.hit_cap, flags, threadIdx.x, ndistinct + g)) return;
+  sort_unique_one<USE_LDS, MINC>(g, gm, n, hits, ndistinct, lds_keys, bucket_mul, m);
+}
 template <bool USE_LDS>
 __global__ __launch_bounds__(SORT_WG) void sort_unique_kernel(
     const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits,
     const uint32_t *__restrict__ cnt, uint32_t *__restrict__ ndistinct, uint32_t lds_keys,
     const uint32_t *__restrict__ todo, uint64_t bucket_mul, uint32_t *__restrict__ flags) {
-  const uint32_t g = todo ? todo[blockIdx.x] : blockIdx.x;
-  const hg_genome_meta gm = meta[g];
-  uint32_t n = cnt[g];
-  if (!sort_step_guard(n, gm.hit_cap, flags, threadIdx.x, ndistinct + g)) return;
-  sort_unique_one<USE_LDS>(g, gm, n, hits, ndistinct, lds_keys, bucket_mul);
+  sort_unique_body<USE_LDS, false>(meta, hits, cnt, ndistinct, lds_keys, todo, bucket_mul, flags, 1u);
+}
+template <bool USE_LDS>
+__global__ __launch_bounds__(SORT_WG) void min_count_kernel(
+    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits,
+    const uint32_t *__restrict__ cnt, uint32_t *__restrict__ ndistinct, uint32_t lds_keys,
+    const uint32_t *__restrict__ todo, uint64_t bucket_mul, uint32_t *__restrict__ flags, uint32_t m) {
+  sort_unique_body<USE_LDS, true>(meta, hits, cnt, ndistinct, lds_keys, todo, bucket_mul, flags, m);
 }
 
 // One WAVE per genome, four genomes per workgroup: the first sort launch of a batch whose genomes are EXPECTED to sample at
 // most a few dozen k-mers (plasmids, viral genomes, contigs of a few kbp: 400 000 genomes of 2 kbp have 1.3 hashes each --
 // there one 512-thread workgroup per genome, seven of whose eight waves leave at once, cost 0.74 ms against 2.25 ms for
 // the k-mer kernel).  A genome with more than 64 raw hits is left to hg_launch_sort_unique_rest (skip_keys = 64).
-__global__ __launch_bounds__(256) void sort_unique_wave_kernel(
-    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
-    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t *__restrict__ flags) {
+template <bool MINC>
+__device__ __forceinline__ void sort_unique_wave_body(const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits,
+                                                      const uint32_t *__restrict__ cnt, uint32_t *__restrict__ ndistinct,
+                                                      uint32_t n_genomes, uint32_t *__restrict__ flags, const uint32_t m) {
   const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
   if (g >= n_genomes) return;
   uint32_t n = cnt[g];
   if (!sort_step_guard(n, meta[g].hit_cap, flags, lane, ndistinct + g)) return;
   if (n > 64) return;
   if (n <= 1) {
-    if (lane == 0) ndistinct[g] = n;
+    if (lane == 0) ndistinct[g] = (!MINC || n >= m) ? n : 0u;
     return;
   }
-  sort_unique_wave(hits + meta[g].hit_off, n, lane, ndistinct + g);
+  sort_unique_wave<MINC>(hits + meta[g].hit_off, n, lane, ndistinct + g, m);
+}
+__global__ __launch_bounds__(256) void sort_unique_wave_kernel(
+    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
+    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t *__restrict__ flags) {
+  sort_unique_wave_body<false>(meta, hits, cnt, ndistinct, n_genomes, flags, 1u);
+}
+__global__ __launch_bounds__(256) void min_count_wave_kernel(
+    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
+    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t *__restrict__ flags, uint32_t m) {
+  sort_unique_wave_body<true>(meta, hits, cnt, ndistinct, n_genomes, flags, m);
 }
 
 // grid: SORT_WG genomes per workgroup.  The genomes whose raw count is in (skip_keys, lds_keys] -- what a launch of
 // sort_unique_kernel with skip_keys of LDS left out -- are picked out of the counters by the workgroup itself and sorted
 // one after the other (rare by construction: skip_keys is 1.125 times the expected count, or last run's largest).
-__global__ __launch_bounds__(SORT_WG) void sort_unique_rest_kernel(
-    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
-    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t skip_keys, uint32_t lds_keys, uint64_t bucket_mul) {
+template <bool MINC>
+__device__ __forceinline__ void sort_unique_rest_body(const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits,
+                                                      const uint32_t *__restrict__ cnt, uint32_t *__restrict__ ndistinct,
+                                                      uint32_t n_genomes, uint32_t skip_keys, uint32_t lds_keys, uint64_t bucket_mul,
+                                                      const uint32_t m) {
   __shared__ uint32_t s_list[SORT_WG], s_n;
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
@@ -277,9 +324,19 @@ __global__ __launch_bounds__(SORT_WG) void sort_unique_rest_kernel(
   for (uint32_t i = 0; i < todo; ++i) {
     const uint32_t gi = s_list[i];
     const hg_genome_meta gm = meta[gi];
-    sort_unique_one<true>(gi, gm, cnt[gi], hits, ndistinct, lds_keys, bucket_mul);
+    sort_unique_one<true, MINC>(gi, gm, cnt[gi], hits, ndistinct, lds_keys, bucket_mul, m);
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(SORT_WG) void sort_unique_rest_kernel(
+    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
+    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t skip_keys, uint32_t lds_keys, uint64_t bucket_mul) {
+  sort_unique_rest_body<false>(meta, hits, cnt, ndistinct, n_genomes, skip_keys, lds_keys, bucket_mul, 1u);
+}
+__global__ __launch_bounds__(SORT_WG) void min_count_rest_kernel(
+    const hg_genome_meta *__restrict__ meta, uint64_t *__restrict__ hits, const uint32_t *__restrict__ cnt,
+    uint32_t *__restrict__ ndistinct, uint32_t n_genomes, uint32_t skip_keys, uint32_t lds_keys, uint64_t bucket_mul, uint32_t m) {
+  sort_unique_rest_body<true>(meta, hits, cnt, ndistinct, n_genomes, skip_keys, lds_keys, bucket_mul, m);
 }
 
 __global__ __launch_bounds__(256) void sketch_finish_kernel(const uint32_t *__restrict__ ndistinct, uint32_t *__restrict__ nhash,
@@ -400,20 +457,28 @@ __global__ __launch_bounds__(BK_WG) void bucket_scatter_kernel(const hg_bucket_j
 // A bucket with more keys than LDS holds (only possible when duplicates pile up: the map is balanced for
 // distinct hashes) is first de-duplicated through an LDS hash set; if even its distinct keys do not fit the
 // job is flagged and the caller sorts that genome in place instead.
-__global__ __launch_bounds__(SORT_WG) void bucket_sort_kernel(const hg_bucket_job *__restrict__ jobs,
-                                                              const uint32_t *__restrict__ bucket_job,
-                                                              const uint32_t *__restrict__ bcount,
-                                                              const uint32_t *__restrict__ bstart,
-                                                              uint64_t *__restrict__ tmp,
-                                                              uint32_t *__restrict__ bdist,
-                                                              uint32_t *__restrict__ fail, uint32_t cap_keys) {
+// MINC: equal keys share a bucket, so a bucket sees every occurrence of its keys.  Here the order is count first, sort the
+// survivors: every key goes into an LDS table of (key, occurrences) -- the hash set above with a counter per slot; the launch's
+// LDS has 4 bytes of counters per key behind the keys --, the keys seen at least m times are compacted through the bucket's own
+// scratch range (its raw keys are not needed again) and only those are sorted.  A read set is what this is for: at 30x coverage
+// a bucket of ~800 raw keys holds ~30 genuine hashes of 20-35 copies each among ~200 singletons -- the counting sort gives up
+// at 17 equal keys and the bitonic network would order all 1 024 (55 passes), the table orders ~30 (15).  The table has at
+// least two slots per raw key, so it cannot overflow, up to cap_keys / 2 raw keys; from there it has cap_keys slots and takes
+// up to 3/4 of that in DISTINCT keys.  Beyond: a bucket that fits LDS is sorted whole and filtered by unique_scatter's
+// look-ahead (the keys are still in the scratch range), one that does not flags its job as above.
+template <bool MINC>
+__device__ __forceinline__ void bucket_sort_body(const hg_bucket_job *__restrict__ jobs, const uint32_t *__restrict__ bucket_job,
+                                                 const uint32_t *__restrict__ bcount, const uint32_t *__restrict__ bstart,
+                                                 uint64_t *__restrict__ tmp, uint32_t *__restrict__ bdist,
+                                                 uint32_t *__restrict__ fail, const uint32_t cap_keys, const uint32_t m) {
   // cap_keys (a power of two, <= SORT_LDS_MAX_KEYS): keys the launch's LDS holds -- 12 bytes each, keys + counters.  The
   // launcher sizes it to four times the bucket size the plan aims at: 48 KiB for 512-1 024 expected keys, three workgroups
   // per CU (with the full 96 KiB in every launch one workgroup per CU sorted 1 500 keys at a time).
-  const uint32_t HSET_SLOTS = cap_keys, HSET_MAX = HSET_SLOTS / 4 * 3;
   extern __shared__ __attribute__((aligned(16))) uint64_t s_keys[];
   __shared__ uint32_t s_scan[SORT_WG / 64];
   __shared__ uint32_t s_distinct;
+  [[maybe_unused]] __shared__ uint32_t s_kept;
+  [[maybe_unused]] uint32_t *const s_occ = reinterpret_cast<uint32_t *>(s_keys + cap_keys);  // MINC: occurrences of the key in slot i
   const uint32_t gb = blockIdx.x, j = bucket_job[gb], tid = threadIdx.x;
   const hg_bucket_job job = jobs[j];
   const uint32_t n = bcount[gb];
@@ -422,9 +487,17 @@ __global__ __launch_bounds__(SORT_WG) void bucket_sort_kernel(const hg_bucket_jo
     if (tid == 0) bdist[gb] = 0;
     return;
   }
-  if (n > cap_keys) {
+  if (MINC || n > cap_keys) {
+    uint32_t HSET_SLOTS = cap_keys;  // (a power of two)
+    if constexpr (MINC)
+      if (n <= cap_keys / 2) HSET_SLOTS = n <= 32 ? 64u : 2 * next_pow2(n);
+    const uint32_t HSET_MAX = HSET_SLOTS / 4 * 3;
     for (uint32_t i = tid; i < HSET_SLOTS; i += SORT_WG) s_keys[i] = ~0ull;  // no hash equals ~0 (h < threshold)
     if (tid == 0) s_distinct = 0;
+    if constexpr (MINC) {
+      for (uint32_t i = tid; i < HSET_SLOTS; i += SORT_WG) s_occ[i] = 0;
+      if (tid == 0) s_kept = 0;
+    }
     __syncthreads();
     for (uint32_t i = tid; i < n; i += SORT_WG) {
       const uint64_t h = base[i];
@@ -434,22 +507,41 @@ __global__ __launch_bounds__(SORT_WG) void bucket_sort_kernel(const hg_bucket_jo
         const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long *>(&s_keys[slot]), ~0ull, (unsigned long long)h);
         if (old == ~0ull) {
           atomicAdd(&s_distinct, 1u);
+          if constexpr (MINC) atomicAdd(&s_occ[slot], 1u);
           break;
         }
-        if (old == h) break;
+        if (old == h) {
+          if constexpr (MINC) atomicAdd(&s_occ[slot], 1u);
+          break;
+        }
         slot = (slot + 1) & (HSET_SLOTS - 1);
       }
     }
     __syncthreads();
-    if (s_distinct > HSET_MAX) {
+    const bool overflow = s_distinct > HSET_MAX;  // workgroup-uniform
+    if (overflow && n > cap_keys) {
       if (tid == 0) fail[j] = 1u, bdist[gb] = 0;
       return;
     }
-    bitonic_sort(s_keys, HSET_SLOTS, tid, SORT_WG);  // empty slots (~0) sort to the end
-    const uint32_t d = s_distinct;
-    for (uint32_t i = tid; i < d; i += SORT_WG) base[i] = s_keys[i];
-    if (tid == 0) bdist[gb] = d;
-    return;
+    if constexpr (!MINC) {
+      bitonic_sort(s_keys, HSET_SLOTS, tid, SORT_WG);  // empty slots (~0) sort to the end
+      const uint32_t d = s_distinct;
+      for (uint32_t i = tid; i < d; i += SORT_WG) base[i] = s_keys[i];
+      if (tid == 0) bdist[gb] = d;
+      return;
+    } else if (!overflow) {  // (the table is complete: nobody gave up above)
+      for (uint32_t i = tid; i < HSET_SLOTS; i += SORT_WG)
+        if (s_keys[i] != ~0ull && s_occ[i] >= m) base[atomicAdd(&s_kept, 1u)] = s_keys[i];  // (kept <= distinct <= n: inside the bucket's range)
+      __syncthreads();  // (orders the workgroup's global writes before its reads below, too)
+      const uint32_t d = s_kept, d2 = next_pow2(d);
+      for (uint32_t i = tid; i < d2; i += SORT_WG) s_keys[i] = i < d ? base[i] : ~0ull;
+      __syncthreads();
+      bitonic_sort(s_keys, d2, tid, SORT_WG);
+      for (uint32_t i = tid; i < d; i += SORT_WG) base[i] = s_keys[i];
+      if (tid == 0) bdist[gb] = d;
+      return;
+    }
+    __syncthreads();  // MINC, more distinct keys than the table takes, but the bucket fits LDS: everyone has read s_distinct
   }
   const uint32_t n2 = next_pow2(n);
   bool sorted = false;  // workgroup-uniform
@@ -466,8 +558,26 @@ __global__ __launch_bounds__(SORT_WG) void bucket_sort_kernel(const hg_bucket_jo
     __syncthreads();
   }
   if (!sorted) bitonic_sort(s_keys, n2, tid, SORT_WG);
-  const uint32_t run = unique_scatter<false>(s_keys, n, base, s_scan);
+  const uint32_t run = unique_scatter<false, MINC>(s_keys, n, base, s_scan, m);
   if (tid == 0) bdist[gb] = run;
+}
+__global__ __launch_bounds__(SORT_WG) void bucket_sort_kernel(const hg_bucket_job *__restrict__ jobs,
+                                                              const uint32_t *__restrict__ bucket_job,
+                                                              const uint32_t *__restrict__ bcount,
+                                                              const uint32_t *__restrict__ bstart,
+                                                              uint64_t *__restrict__ tmp,
+                                                              uint32_t *__restrict__ bdist,
+                                                              uint32_t *__restrict__ fail, uint32_t cap_keys) {
+  bucket_sort_body<false>(jobs, bucket_job, bcount, bstart, tmp, bdist, fail, cap_keys, 1u);
+}
+__global__ __launch_bounds__(SORT_WG) void min_count_bucket_kernel(const hg_bucket_job *__restrict__ jobs,
+                                                                   const uint32_t *__restrict__ bucket_job,
+                                                                   const uint32_t *__restrict__ bcount,
+                                                                   const uint32_t *__restrict__ bstart,
+                                                                   uint64_t *__restrict__ tmp,
+                                                                   uint32_t *__restrict__ bdist,
+                                                                   uint32_t *__restrict__ fail, uint32_t cap_keys, uint32_t m) {
+  bucket_sort_body<true>(jobs, bucket_job, bcount, bstart, tmp, bdist, fail, cap_keys, m);
 }
 
 // grid: buckets.  Distinct keys of the bucket -> their final place in the genome's hit region.
@@ -501,6 +611,9 @@ static hipError_t sort_lds_attr() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&sort_unique_rest_kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, SORT_LDS_BYTES_MAX);
+  for (const void *f : {reinterpret_cast<const void *>(&min_count_kernel<true>), reinterpret_cast<const void *>(&min_count_bucket_kernel),
+                        reinterpret_cast<const void *>(&min_count_rest_kernel)})
+    if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, SORT_LDS_BYTES_MAX);
   if (e == hipSuccess) attr_done_on_this_device(done, true);
   return e;
 }
@@ -535,10 +648,16 @@ static sort_lds_plan sort_lds_plan_for(uint32_t max_cap, uint64_t threshold) {
 
 hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo, uint32_t n_todo,
                                       uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t max_cap,
-                                      uint64_t threshold, std::string *launched) {
+                                      uint64_t threshold, uint32_t min_count, std::string *launched) {
   if (n_todo == 0) return hipSuccess;
   const sort_lds_plan p = sort_lds_plan_for(max_cap, threshold);
   if (p.err != hipSuccess) return p.err;
+  if (min_count > 1) {
+    hipLaunchKernelGGL((min_count_kernel<true>), dim3(n_todo), dim3(SORT_WG), p.lds_bytes, st, d_meta, d_hits, d_cnt, d_ndistinct,
+                       p.keys, d_todo, p.bucket_mul, (uint32_t *)nullptr, min_count);
+    hg_note_launch(launched, "min_count_kernel<true>");
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((sort_unique_kernel<true>), dim3(n_todo), dim3(SORT_WG), p.lds_bytes, st, d_meta, d_hits, d_cnt, d_ndistinct,
                      p.keys, d_todo, p.bucket_mul, (uint32_t *)nullptr);
   hg_note_launch(launched, "sort_unique_kernel<true>");
@@ -547,11 +666,23 @@ hipError_t hg_launch_sort_unique_todo(hipStream_t st, const hg_genome_meta *d_me
 
 hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes,
                                  uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                 uint32_t max_cap, uint64_t threshold, uint32_t *d_flags,
+                                 uint32_t max_cap, uint64_t threshold, uint32_t min_count, uint32_t *d_flags,
                                  std::string *launched) {
   if (n_genomes == 0) return hipSuccess;
   const sort_lds_plan p = sort_lds_plan_for(max_cap, threshold);
   if (p.err != hipSuccess) return p.err;
+  if (min_count > 1) {  // the same two launches, of the min_count family
+    if (p.keys <= 64) {
+      hipLaunchKernelGGL(min_count_wave_kernel, dim3((n_genomes + 3) / 4), dim3(256), 0, st, d_meta, d_hits, d_cnt, d_ndistinct,
+                         n_genomes, d_flags, min_count);
+      hg_note_launch(launched, "min_count_wave_kernel");
+      return hipGetLastError();
+    }
+    hipLaunchKernelGGL((min_count_kernel<true>), dim3(n_genomes), dim3(SORT_WG), p.lds_bytes, st, d_meta, d_hits, d_cnt,
+                       d_ndistinct, p.keys, (const uint32_t *)nullptr, p.bucket_mul, d_flags, min_count);
+    hg_note_launch(launched, "min_count_kernel<true>");
+    return hipGetLastError();
+  }
   if (p.keys <= 64) {  // tiny sets: a wave per genome
     hipLaunchKernelGGL(sort_unique_wave_kernel, dim3((n_genomes + 3) / 4), dim3(256), 0, st, d_meta, d_hits, d_cnt, d_ndistinct,
                        n_genomes, d_flags);
@@ -568,11 +699,17 @@ hipError_t hg_launch_sort_unique(hipStream_t st, const hg_genome_meta *d_meta, u
 
 hipError_t hg_launch_sort_unique_rest(hipStream_t st, const hg_genome_meta *d_meta, uint32_t n_genomes, uint64_t *d_hits,
                                       const uint32_t *d_cnt, uint32_t *d_ndistinct, uint32_t done_cap, uint32_t max_cap,
-                                      uint64_t threshold, std::string *launched) {
+                                      uint64_t threshold, uint32_t min_count, std::string *launched) {
   const uint32_t skip = hg_sort_lds_keys(done_cap);
   if (n_genomes == 0 || skip >= hg_sort_lds_keys(max_cap)) return hipSuccess;
   const sort_lds_plan p = sort_lds_plan_for(max_cap, threshold);
   if (p.err != hipSuccess) return p.err;
+  if (min_count > 1) {
+    hipLaunchKernelGGL(min_count_rest_kernel, dim3((n_genomes + SORT_WG - 1) / SORT_WG), dim3(SORT_WG), p.lds_bytes, st, d_meta,
+                       d_hits, d_cnt, d_ndistinct, n_genomes, skip, p.keys, p.bucket_mul, min_count);
+    hg_note_launch(launched, "min_count_rest_kernel");
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(sort_unique_rest_kernel, dim3((n_genomes + SORT_WG - 1) / SORT_WG), dim3(SORT_WG), p.lds_bytes, st, d_meta,
                      d_hits, d_cnt, d_ndistinct, n_genomes, skip, p.keys, p.bucket_mul);
   hg_note_launch(launched, "sort_unique_rest_kernel");
@@ -589,8 +726,14 @@ hipError_t hg_launch_sketch_finish(hipStream_t st, const uint32_t *d_ndistinct, 
 
 hipError_t hg_launch_sort_inplace(hipStream_t st, const hg_genome_meta *d_meta, const uint32_t *d_todo,
                                   uint32_t n_todo, uint64_t *d_hits, const uint32_t *d_cnt, uint32_t *d_ndistinct,
-                                  std::string *launched) {
+                                  uint32_t min_count, std::string *launched) {
   if (n_todo == 0) return hipSuccess;
+  if (min_count > 1) {
+    hipLaunchKernelGGL((min_count_kernel<false>), dim3(n_todo), dim3(SORT_WG), 0, st, d_meta, d_hits, d_cnt,
+                       d_ndistinct, SORT_LDS_MAX_KEYS, d_todo, (uint64_t)0, (uint32_t *)nullptr, min_count);
+    hg_note_launch(launched, "min_count_kernel<false>");
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL((sort_unique_kernel<false>), dim3(n_todo), dim3(SORT_WG), 0, st, d_meta, d_hits, d_cnt,
                      d_ndistinct, SORT_LDS_MAX_KEYS, d_todo, (uint64_t)0, (uint32_t *)nullptr);
   hg_note_launch(launched, "sort_unique_kernel<false>");
@@ -600,7 +743,7 @@ hipError_t hg_launch_sort_inplace(hipStream_t st, const hg_genome_meta *d_meta, 
 hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uint32_t n_jobs,
                                 const uint32_t *d_chunk_job, uint32_t n_chunks, const uint32_t *d_bucket_job,
                                 uint32_t n_buckets, uint32_t *d_bk, uint64_t *d_hits, uint64_t *d_tmp,
-                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, std::string *launched) {
+                                uint32_t *d_ndistinct, uint32_t bucket_cap_keys, uint32_t min_count, std::string *launched) {
   if (n_jobs == 0) return hipSuccess;
   uint32_t cap_keys = (uint32_t)SORT_WG;  // (a power of two: the counting sort deals n2 / SORT_WG sub-buckets to a thread)
   while (cap_keys < bucket_cap_keys && cap_keys < SORT_LDS_MAX_KEYS) cap_keys <<= 1;
@@ -613,13 +756,19 @@ hipError_t hg_launch_sort_large(hipStream_t st, const hg_bucket_job *d_jobs, uin
   hipLaunchKernelGGL(bucket_scan_kernel, dim3(n_jobs), dim3(SORT_WG), 0, st, d_jobs, bcount, bstart, (uint32_t *)nullptr);
   hipLaunchKernelGGL(bucket_scatter_kernel, dim3(n_chunks), dim3(BK_WG), 0, st, d_jobs, d_chunk_job, d_hits, bstart,
                      bcursor, d_tmp);
-  hipLaunchKernelGGL(bucket_sort_kernel, dim3(n_buckets), dim3(SORT_WG), (size_t)cap_keys * (sizeof(uint64_t) + sizeof(uint32_t)), st,
-                     d_jobs, d_bucket_job, bcount, bstart, d_tmp, bdist, fail, cap_keys);
+  // (only the per-bucket kernel knows about min_count: the buckets before it hold raw keys, the scan and copy behind it survivors)
+  const size_t bucket_lds = (size_t)cap_keys * (sizeof(uint64_t) + sizeof(uint32_t));
+  if (min_count > 1)
+    hipLaunchKernelGGL(min_count_bucket_kernel, dim3(n_buckets), dim3(SORT_WG), bucket_lds, st, d_jobs, d_bucket_job, bcount, bstart,
+                       d_tmp, bdist, fail, cap_keys, min_count);
+  else
+    hipLaunchKernelGGL(bucket_sort_kernel, dim3(n_buckets), dim3(SORT_WG), bucket_lds, st, d_jobs, d_bucket_job, bcount, bstart, d_tmp,
+                       bdist, fail, cap_keys);
   hipLaunchKernelGGL(bucket_scan_kernel, dim3(n_jobs), dim3(SORT_WG), 0, st, d_jobs, bdist, bout, d_ndistinct);
   hipLaunchKernelGGL(bucket_copy_kernel, dim3(n_buckets), dim3(BK_WG), 0, st, d_jobs, d_bucket_job, bstart, bdist, bout,
                      fail, d_tmp, d_hits);
-  for (const char *k : {"bucket_count_kernel", "bucket_scan_kernel", "bucket_scatter_kernel", "bucket_sort_kernel", "bucket_scan_kernel",
-                        "bucket_copy_kernel"})
+  for (const char *k : {"bucket_count_kernel", "bucket_scan_kernel", "bucket_scatter_kernel",
+                        min_count > 1 ? "min_count_bucket_kernel" : "bucket_sort_kernel", "bucket_scan_kernel", "bucket_copy_kernel"})
     hg_note_launch(launched, k);
   return hipGetLastError();
 }

@@ -104,7 +104,8 @@ hg_status hg_ctx_timings(hg_ctx *ctx, float ms_sum[HG_T_COUNT], uint32_t launche
  * "" if none.  A measurement harness uses it to check that a committed profile belongs to the kernel that ran.
  * HG_T_SORT / HG_T_ENCODE: every kernel the last sketch step (or hg_kmer_hash_sample's sort, hg_hv_encode's encode) queued
  * for the class, in launch order, joined by " + " ("sort_unique_kernel<true> + sort_unique_rest_kernel",
- * "encode_wave_kernel + sketch_finish_kernel"); a step run again later through the synchronous path reports that run. */
+ * "encode_wave_kernel + sketch_finish_kernel"); a step run again later through the synchronous path reports that run.
+ * With min_count > 1 the sort class names the min_count_* kernels that ran in place of sort_unique_* / bucket_sort_kernel. */
 const char *hg_ctx_last_kernel(const hg_ctx *ctx, int cls);
 
 /* minimal device-memory helpers for callers that have no HIP binding of their own
@@ -130,8 +131,21 @@ typedef struct {
   uint32_t hv_d;      /* HV dimension; chunks of 64 are filled (src/hd.rs:34,102)    */
   uint32_t hv_layout; /* HG_LAYOUT_*                                                 */
   uint32_t norm_mode; /* HG_NORM_*                                                   */
-  uint32_t reserved;
+  uint32_t min_count; /* keep a sampled k-mer only if it occurs at least this often; 0 and 1: every sampled k-mer (see below) */
 } hg_sketch_params;
+
+/* min_count (no reference counterpart; the field was `reserved` and never read).  Let raw be the multiset of sampled hashes of
+ * a genome / read set, one per sampled k-mer POSITION, and m = max(1, min_count):
+ *     kept = { h : multiplicity of h in raw >= m }, ascending
+ * nhash = |kept|; the HV and its norm are the encoder's output for kept.  m = 1 is the reference's HashSet<u64>
+ * (src/sketch.rs:93), bit for bit -- what a zero-initialised struct and hg_sketch_params_default (it writes 0) ask for.
+ * m >= 2 is for raw READS (Mash's -m): every sequencing error makes up to k k-mers that occur once, and at 30x coverage
+ * they outnumber the genome's own.  With canonical != 0 both strands of a k-mer have one hash and count together.  An empty
+ * kept gives nhash = 0 and the encoder's row for the empty set.  Counts are taken on the complete raw multiset only: a hit
+ * region that overflows is grown and the step run again exactly as for m = 1, before anything is filtered.
+ * Honoured by every entry point that takes hg_sketch_params: hg_sketch_batch_dev, hg_sketch_batch_dev_packed, hg_sketch_batch,
+ * hg_sketch_batch_multi, hg_sketch_stream_open (every push form), and a sync-free step that is run again synchronously.
+ * The .sketch container does not record it. */
 
 void hg_sketch_params_default(hg_sketch_params *p);
 
@@ -147,6 +161,13 @@ hg_status hg_kmer_hash_sample(hg_ctx *ctx, const uint8_t *seq, size_t n_bps,
                               uint32_t ksize, uint64_t threshold, uint64_t seed,
                               int canonical, uint32_t norm_mode, uint64_t *out_hashes,
                               size_t cap, size_t *n_out);
+/* The same with the min_count filter of hg_sketch_params: output = the sampled hashes that occur at least max(1, min_count)
+ * times among the sequence's sampled k-mer positions, ascending.  Same capacity rule: HG_ERR_CAPACITY and *n_out = the number
+ * of hashes kept.  min_count <= 1 is hg_kmer_hash_sample. */
+hg_status hg_kmer_hash_sample_min_count(hg_ctx *ctx, const uint8_t *seq, size_t n_bps,
+                                        uint32_t ksize, uint64_t threshold, uint64_t seed,
+                                        int canonical, uint32_t norm_mode, uint32_t min_count,
+                                        uint64_t *out_hashes, size_t cap, size_t *n_out);
 
 /* ---- HV encode -------------------------------------------------------------------
  * replaces hd::encode_hash_hd{,_avx2} + dist::compute_hv_l2_norm
@@ -180,7 +201,9 @@ hg_status hg_sketch_batch_dev(hg_ctx *ctx, const uint8_t *d_seq, const uint64_t 
  *   - an error of the re-run is returned by the call that triggered it.
  * Batches whose genomes are EXPECTED to exceed the one-workgroup sort (more than ~7 000 sampled k-mers: 10 Mbp at
  * scaled = 1 500) take the synchronous path at once and are final in stream order; hg_ctx_set_debug(ctx, "sketch_path",
- * "sync") sends every batch that way (the behaviour up to round 5: counters read back between sort and encode). */
+ * "sync") sends every batch that way (the behaviour up to round 5: counters read back between sort and encode).
+ * All of this is the same for every p->min_count: the check word is raised by RAW counts (before the filter), pending rows
+ * carry HG_NHASH_PENDING, and results are final after hg_ctx_sync. */
 #define HG_NHASH_PENDING 0xFFFFFFFFu
 /* How the library would lay a batch out for the k-mer launch (host arithmetic only; no ctx, no device): counts[0] = work items
  * (pieces of 27 432 k-mer starts for k <= 21, 27 324 for k <= 32, 12 288 beyond), [1] = workgroups -- for k <= 32 the work
