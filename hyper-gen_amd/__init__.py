@@ -88,7 +88,9 @@ EXPORTS = [
     "hg_sketch_file_read_image", "hg_sketch_file_image", "hg_sketch_file_payload_offset",
     "hg_cluster_init_dev", "hg_cluster_add_hits_dev", "hg_cluster_finish_dev", "hg_cluster_dev", "hg_cluster",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
+    "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
 ]
+SEARCH_TOPK_MAX = 64  # HG_SEARCH_TOPK_MAX
 
 
 def source_stamp():
@@ -267,6 +269,13 @@ def lib():
         "hg_cluster_finish_dev": (C.c_int, [vp, vp, sz, vp, C.POINTER(sz)]),
         "hg_cluster_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, C.POINTER(sz)]),
         "hg_cluster": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, C.POINTER(sz)]),
+        "hg_search_topk_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
+        "hg_search_topk_block_dev": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
+                                               vp, vp]),
+        "hg_search_topk": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
+        "hg_search_topk_merge": (C.c_int, [C.POINTER(vp), C.POINTER(vp), sz, sz, C.c_uint32, vp, vp]),
+        "hg_search_topk_multi_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), sz,
+                                               C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here == the ABI lost a symbol
@@ -579,6 +588,24 @@ class Context:
     def topk_per_query_dev(self, d_hits, n, Q, k, d_out, d_counts):
         self._ck(lib().hg_topk_per_query_dev(self._h, _ptr(d_hits), n, Q, k, _ptr(d_out), _ptr(d_counts)))
 
+    def search_topk_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, ani_th, k, d_out, d_counts, ref_off=0, qry_off=0):
+        """hg_search_topk_block_dev (hg_search_topk_dev with both offsets 0): per query the k best references with
+        ani >= ani_th into d_out (Q * k hits, the layout of topk_per_query_dev) and d_counts; device pointers, stream-ordered."""
+        self._ck(lib().hg_search_topk_block_dev(self._h, _ptr(d_ref), _ptr(d_rn), R, ref_off, _ptr(d_qry), _ptr(d_qn), Q, qry_off,
+                                                hv_d, ksize, C.c_float(ani_th), k, _ptr(d_out), _ptr(d_counts)))
+
+    def search_topk(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21, ani_th=85.0, k=1):
+        """hg_search_topk on host sketches: (hits of shape (Q, k) with ANI_HIT_DTYPE, counts)"""
+        r = np.ascontiguousarray(ref_hv, np.int16)
+        q = np.ascontiguousarray(qry_hv, np.int16)
+        rn = np.ascontiguousarray(ref_n2, np.int32)
+        qn = np.ascontiguousarray(qry_n2, np.int32)
+        out = np.zeros((q.shape[0], k), ANI_HIT_DTYPE)
+        cnt = np.zeros(q.shape[0], np.uint32)
+        self._ck(lib().hg_search_topk(self._h, _ptr(r) if r.size else None, _ptr(rn) if rn.size else None, r.shape[0], _ptr(q),
+                                      _ptr(qn), q.shape[0], q.shape[1], ksize, C.c_float(ani_th), k, _ptr(out), _ptr(cnt)))
+        return out, cnt
+
     def dist_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, symmetric, ani_th, d_out, cap):
         n = C.c_size_t(0)
         st = lib().hg_dist_dev(self._h, _ptr(d_ref), _ptr(d_rn), R, _ptr(d_qry), _ptr(d_qn), Q, hv_d,
@@ -723,6 +750,17 @@ class Multi:
             self._ck(st)
             return out[: n.value].copy()
 
+    def search_topk_dev(self, d_ref, d_rn, ref_rows, d_qry, d_qn, Q, hv_d, ksize=21, ani_th=85.0, k=1):
+        """hg_search_topk_multi_dev: d_ref / d_rn hold each shard's reference rows, d_qry / d_qn ALL Q query rows on every
+        shard (per-shard device pointers, ints); returns host (hits of shape (Q, k), counts)."""
+        arr = lambda xs: (C.c_void_p * self.n)(*[int(x) for x in xs])
+        szs = lambda xs: (C.c_size_t * self.n)(*[int(x) for x in xs])
+        out = np.zeros((Q, k), ANI_HIT_DTYPE)
+        cnt = np.zeros(Q, np.uint32)
+        self._ck(lib().hg_search_topk_multi_dev(self._h, arr(d_ref), arr(d_rn), szs(ref_rows), arr(d_qry), arr(d_qn), Q, hv_d,
+                                                ksize, C.c_float(ani_th), k, _ptr(out), _ptr(cnt)))
+        return out, cnt
+
     def hamming_search(self, ref_bits, qry_bits, hv_d, max_dist, cap=1 << 20):
         r = np.ascontiguousarray(ref_bits, np.uint32)
         q = np.ascontiguousarray(qry_bits, np.uint32)
@@ -811,6 +849,22 @@ def read_sketch_file_image(path):
         return img, out
     finally:
         lib().hg_sketch_file_free(h)
+
+
+def search_topk_merge(lists, counts, k):
+    """hg_search_topk_merge: per-shard results (hits of shape (Q, k), counts) of disjoint reference sets -> one (hits, counts)"""
+    ls = [np.ascontiguousarray(l, ANI_HIT_DTYPE) for l in lists]
+    cs = [np.ascontiguousarray(c, np.uint32) for c in counts]
+    Q = cs[0].size if cs else 0
+    n = len(ls)
+    lp = (C.c_void_p * max(n, 1))(*[l.ctypes.data for l in ls])
+    cp = (C.c_void_p * max(n, 1))(*[c.ctypes.data for c in cs])
+    out = np.zeros((Q, k), ANI_HIT_DTYPE)
+    cnt = np.zeros(Q, np.uint32)
+    st = lib().hg_search_topk_merge(lp, cp, n, Q, k, _ptr(out), _ptr(cnt))
+    if st != OK:
+        raise HgError(st, "hg_search_topk_merge")
+    return out, cnt
 
 
 def sort_ani_hits(hits, Q, symmetric=False):

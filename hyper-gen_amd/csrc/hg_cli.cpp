@@ -78,6 +78,8 @@ struct Cli {
   bool ani_th_given = false;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   bool min_count_given = false;
+  int search_path = 0;  // --search_path auto|hits|topk (search; testing aid): 0 = topk whenever top_n <= HG_SEARCH_TOPK_MAX, 1 = the hit list, 2 = topk
+  bool search_path_given = false;
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
 };
 
@@ -108,7 +110,10 @@ Cli parse(int argc, char **argv) {
                 "         smaller of the two; dist on one file with containment writes every ordered pair i != j; cluster\n"
                 "         takes mash or max_containment), --min_count N [1] (sketch: keep a sampled k-mer only if it occurs\n"
                 "         at least N times in the file -- for raw reads, where every sequencing error makes k-mers that occur\n"
-                "         once; 1 = every sampled k-mer, the reference's set)\n");
+                "         once; 1 = every sampled k-mer, the reference's set), --search_path auto|hits|topk [auto] (search:\n"
+                "         topk selects the -n best per query on the device while blocks of the ANI matrix stream past -- memory\n"
+                "         does not grow with the number of pairs above -a; hits builds the thresholded hit list first; auto =\n"
+                "         topk for -n <= 64, hits beyond; both write the same file)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -117,7 +122,7 @@ Cli parse(int argc, char **argv) {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
       {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
-      {"min_count", '\x02'}};
+      {"min_count", '\x02'}, {"search_path", '\x03'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -176,6 +181,13 @@ Cli parse(int argc, char **argv) {
         c.min_count = (unsigned)u(0xFFFFFFFFull), c.min_count_given = true;
         if (c.min_count == 0) die("invalid value '" + val + "' for '" + a + "'");
         break;
+      case '\x03':  // (long form only) search only (testing aid)
+        if (val == "auto") c.search_path = 0;
+        else if (val == "hits") c.search_path = 1;
+        else if (val == "topk") c.search_path = 2;
+        else die("invalid value '" + val + "' for '--search_path' (auto | hits | topk)");
+        c.search_path_given = true;
+        break;
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -184,6 +196,9 @@ Cli parse(int argc, char **argv) {
       default: die("unexpected argument '" + a + "'");
     }
   }
+  if (c.search_path_given && c.mode != "search") die("--search_path is not supported by " + c.mode + ": it chooses how search selects its results");
+  if (c.search_path == 2 && c.top_n > HG_SEARCH_TOPK_MAX)
+    die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
   if (c.min_count_given && c.mode != "sketch") die("--min_count is not supported by " + c.mode + ": the filter needs the k-mer counts, which a sketch no longer has");
   return c;
 }
@@ -426,7 +441,8 @@ struct DevSet {
   std::vector<const int32_t *> n2;
   std::vector<size_t> rows;
 };
-void to_devices(hg_multi *m, const Loaded &L, DevSet &D) {
+// whole: every shard gets ALL records (the query side of the top-k search: the small side is broadcast).
+void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false) {
   char buf[96];
   std::snprintf(buf, sizeof buf, "Decompressing sketch with HV dim=%llu", (unsigned long long)L.hv_d);
   logline("INFO", buf);
@@ -437,6 +453,7 @@ void to_devices(hg_multi *m, const Loaded &L, DevSet &D) {
   auto work = [&](int s) {
     size_t lo = 0, hi = 0;
     hg_shard_range(L.n, s, ns, &lo, &hi);
+    if (whole) lo = 0, hi = L.n;
     if (hi == lo) return;
     hg_ctx *ctx = hg_multi_ctx(m, s);
     const uint64_t b0 = L.off[lo], b1 = L.off[hi - 1] + 2 * hg_sketch_file_get(L.f, hi - 1)->hv_len;
@@ -723,30 +740,41 @@ int run_search(const Cli &c) {
   if (R.ksize != Q.ksize) die("Ref and query sketches use different kmer sizes!");
   if (R.hv_d != Q.hv_d) die("Ref and query sketches use different HV dimensions!");
   tp = now_s();
+  const uint32_t k = std::max(1u, c.top_n);
+  // The fused path (hg_search_topk_multi_dev): the k best per query are selected on the device while blocks of the ANI
+  // matrix stream past -- no hit list, memory does not depend on how many pairs lie above the threshold.  Every shard keeps
+  // its reference rows and holds ALL queries.  -n beyond HG_SEARCH_TOPK_MAX (or --search_path hits) takes the hit list.
+  const bool fused = c.search_path == 2 || (c.search_path == 0 && k <= HG_SEARCH_TOPK_MAX);
   DevSet dR, dQ;
   to_devices(multi, R, dR);
-  to_devices(multi, Q, dQ);
+  to_devices(multi, Q, dQ, fused);
   debugf("payloads uploaded and decompressed on the device(s) in %.1f ms", (now_s() - tp) * 1e3);
   logline("INFO", "Searching..");
   tp = now_s();
-  HitBuf hits;
-  void *d_hits = nullptr, *d_out = nullptr, *d_cnt = nullptr;
-  const size_t found = all_hits(multi, R, dR, &Q, &dQ, c.ani_th, false, hits, &d_hits);
-  release(multi, dR), release(multi, dQ);
-  debugf("ANI matrix (%zu hits) in %.1f ms", found, (now_s() - tp) * 1e3);
-  tp = now_s();
-  hg_ctx *ctx = hg_multi_ctx(multi, 0);
-  const uint32_t k = std::max(1u, c.top_n);
-  ck(ctx, hg_dev_alloc(ctx, Q.n * (size_t)k * sizeof(hg_ani_hit), &d_out), "alloc");
-  ck(ctx, hg_dev_alloc(ctx, Q.n * sizeof(uint32_t), &d_cnt), "alloc");
-  ck(ctx, hg_topk_per_query_dev(ctx, static_cast<hg_ani_hit *>(d_hits), found, Q.n, k, static_cast<hg_ani_hit *>(d_out),
-                                static_cast<uint32_t *>(d_cnt)), "top-k");
   std::vector<hg_ani_hit> best(Q.n * (size_t)k);
   std::vector<uint32_t> cnt(Q.n);
-  ck(ctx, hg_copy_d2h(ctx, best.data(), d_out, best.size() * sizeof(hg_ani_hit)), "download");
-  ck(ctx, hg_copy_d2h(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t)), "download");
-  hg_dev_free(ctx, d_hits), hg_dev_free(ctx, d_out), hg_dev_free(ctx, d_cnt);
-  debugf("top-%u per query in %.1f ms", k, (now_s() - tp) * 1e3);
+  if (fused) {
+    ckm(multi, hg_search_topk_multi_dev(multi, dR.hv.data(), dR.n2.data(), dR.rows.data(), dQ.hv.data(), dQ.n2.data(), Q.n,
+                                        (uint32_t)R.hv_d, R.ksize, c.ani_th, k, best.data(), cnt.data()), "search");
+    release(multi, dR), release(multi, dQ);
+    debugf("top-%u per query, selected block by block, in %.1f ms", k, (now_s() - tp) * 1e3);
+  } else {
+    HitBuf hits;
+    void *d_hits = nullptr, *d_out = nullptr, *d_cnt = nullptr;
+    const size_t found = all_hits(multi, R, dR, &Q, &dQ, c.ani_th, false, hits, &d_hits);
+    release(multi, dR), release(multi, dQ);
+    debugf("ANI matrix (%zu hits) in %.1f ms", found, (now_s() - tp) * 1e3);
+    tp = now_s();
+    hg_ctx *ctx = hg_multi_ctx(multi, 0);
+    ck(ctx, hg_dev_alloc(ctx, Q.n * (size_t)k * sizeof(hg_ani_hit), &d_out), "alloc");
+    ck(ctx, hg_dev_alloc(ctx, Q.n * sizeof(uint32_t), &d_cnt), "alloc");
+    ck(ctx, hg_topk_per_query_dev(ctx, static_cast<hg_ani_hit *>(d_hits), found, Q.n, k, static_cast<hg_ani_hit *>(d_out),
+                                  static_cast<uint32_t *>(d_cnt)), "top-k");
+    ck(ctx, hg_copy_d2h(ctx, best.data(), d_out, best.size() * sizeof(hg_ani_hit)), "download");
+    ck(ctx, hg_copy_d2h(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t)), "download");
+    hg_dev_free(ctx, d_hits), hg_dev_free(ctx, d_out), hg_dev_free(ctx, d_cnt);
+    debugf("top-%u per query in %.1f ms", k, (now_s() - tp) * 1e3);
+  }
   tp = now_s();
   // "query<TAB>reference<TAB>ani" per result, queries in file order, best first; formatted by -t threads over contiguous
   // ranges of the queries (like dist's lines: two memcpy and put_ani per line)

@@ -115,6 +115,10 @@ struct hg_ctx {
   Buf w_clu_res;  // clustering: 16 result words ([0] cluster count, [1] error word of the hook kernel), never regrown
   Buf w_clu;      // clustering: per-tile root counts of the dense-id scan
   Buf w_clu_hits; // hg_cluster_dev: scratch hit list of one row block
+  Buf w_srch_blk;   // hg_search_topk*: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
+  Buf w_srch_lists; // ... the slice lists of one block: keys, then counts
+  Buf w_srch_state; // ... the running k best keys per query, state[j * Q + q]
+  Buf w_srch_out;   // hg_search_topk: staged results (rows, then counts)
   // optional per-kernel timing (hg_ctx_enable_timing)
   bool timing = false;
   struct TimedLaunch {
@@ -155,6 +159,7 @@ struct hg_ctx {
   std::string dbg_dist_tile, dbg_dist_path, dbg_ham_path, dbg_dist_order, dbg_kmer_input, dbg_hostfed, dbg_sketch_path;
   int dbg_sort_buckets = 0;
   uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the scratch list of hg_cluster_dev starts with (0: its own size)
+  uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_pair_limit = 0;  // test hook "pair_limit": pairs one kernel launch of a comparison may enumerate (0: 2^32 - 1, the hit counter's reach)
   // pinned host scratch
   void *h_pin = nullptr;

@@ -688,3 +688,46 @@ extern "C" hg_status hg_hamming_search_multi(hg_multi *m, const uint32_t *ref_bi
   });
   return merge_hits(m, found, st, out, cap, n_out);
 }
+
+// ---- search top-k: references sharded by rows where they live, every shard holds all query rows, lists merged ---------
+extern "C" hg_status hg_search_topk_multi_dev(hg_multi *m, const int16_t *const *d_ref_hv, const int32_t *const *d_ref_norm2,
+                                              const size_t *ref_rows, const int16_t *const *d_qry_hv,
+                                              const int32_t *const *d_qry_norm2, size_t Q, uint32_t hv_d, uint32_t ksize,
+                                              float ani_th, uint32_t k, hg_ani_hit *out, uint32_t *counts) {
+  if (!m) return HG_ERR_INVALID;
+  if (k == 0 || Q == 0) return HG_OK;
+  if (k > HG_SEARCH_TOPK_MAX) return mfail(m, HG_ERR_UNSUPPORTED, "k exceeds HG_SEARCH_TOPK_MAX");
+  if (!d_ref_hv || !d_ref_norm2 || !ref_rows || !d_qry_hv || !d_qry_norm2 || !out || !counts) return mfail(m, HG_ERR_INVALID, "NULL argument");
+  const int ns = (int)m->ctx.size();
+  std::vector<size_t> first(ns + 1, 0);
+  for (int s = 0; s < ns; ++s) {
+    first[s + 1] = first[s] + ref_rows[s];
+    if ((ref_rows[s] && (!d_ref_hv[s] || !d_ref_norm2[s])) || !d_qry_hv[s] || !d_qry_norm2[s]) return mfail(m, HG_ERR_INVALID, "NULL shard operand");
+  }
+  if (first[ns] > 0x7FFFFFFFull) return mfail(m, HG_ERR_UNSUPPORTED, "R must be < 2^31");
+  const size_t slots = Q * (size_t)k, ob = slots * sizeof(hg_ani_hit);
+  std::vector<std::vector<hg_ani_hit>> lists(ns, std::vector<hg_ani_hit>(slots));
+  std::vector<std::vector<uint32_t>> cnts(ns, std::vector<uint32_t>(Q));
+  DrainOnExit drain_guard{m};  // every return below leaves all shard streams idle
+  const hg_status st = for_each_shard(m, [&](int s) -> hg_status {
+    hg_ctx *c = m->ctx[s];
+    hg_multi::Shard &x = m->sh[s];
+    HG_HIP(c, hipSetDevice(m->dev[s]));
+    hg_status e;
+    if ((e = hg_ensure(c, x.hits, ob + Q * sizeof(uint32_t) + 64)) != HG_OK) return e;
+    auto *d_out = static_cast<hg_ani_hit *>(x.hits.p);
+    auto *d_cnt = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(x.hits.p) + ob);
+    if ((e = hg_search_topk_block_dev(c, d_ref_hv[s], d_ref_norm2[s], ref_rows[s], first[s], d_qry_hv[s], d_qry_norm2[s], Q, 0, hv_d,
+                                      ksize, ani_th, k, d_out, d_cnt)) != HG_OK)
+      return e;
+    HG_HIP(c, hipMemcpyAsync(lists[s].data(), d_out, ob, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipMemcpyAsync(cnts[s].data(), d_cnt, Q * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(c, hipStreamSynchronize(c->stream));
+    return HG_OK;
+  });
+  if (st != HG_OK) return st;
+  std::vector<const hg_ani_hit *> lp(ns);
+  std::vector<const uint32_t *> cp(ns);
+  for (int s = 0; s < ns; ++s) lp[s] = lists[s].data(), cp[s] = cnts[s].data();
+  return hg_search_topk_merge(lp.data(), cp.data(), (size_t)ns, Q, k, out, counts);
+}

@@ -84,6 +84,8 @@ int hg_device_count(void);
  *                                      split into blocks of reference rows; 0 = 2^32 - 1, the reach of the hit counter)
  *       "cluster_hit_cap" = "<n>"     (hits the scratch list of hg_cluster_dev starts with -- small forces its grow path;
  *                                      0 = the ctx's own size)
+ *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
+ *                                      HG_SEARCH_BLOCK_BYTES)
  * Nothing in the library reads environment variables. */
 hg_status hg_ctx_set_debug(hg_ctx *ctx, const char *key, const char *value);
 
@@ -278,7 +280,8 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * dot <= 0 gives 0, a zero denominator 0 (dot = 0) or 100 (dot > 0), dot > denominator 100.
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
- * (hg_multi_set_ani_metric sets every shard's ctx), hg_cluster{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev} and
+ * hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev}
  * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev (it takes hits), hg_dist_prep_ops_dev, the
  * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
@@ -374,6 +377,45 @@ hg_status hg_sort_ani_hits_staged(hg_ctx *ctx, hg_ani_hit *hits, size_t n, size_
  * d_counts[q] = number of valid entries (<= k).  Device pointers; stream-ordered. */
 hg_status hg_topk_per_query_dev(hg_ctx *ctx, const hg_ani_hit *d_hits, size_t n, size_t Q, uint32_t k,
                                 hg_ani_hit *d_out, uint32_t *d_counts);
+
+/* search: exact top-k per query in bounded memory (no reference counterpart, like hg_topk_per_query_dev).  The same result
+ * as hg_dist_dev(ani_th) followed by hg_topk_per_query_dev -- per query the k references with the highest ANI among those with
+ * ani >= ani_th (the float comparison of hg_dist_dev), descending ANI, ties by ascending GLOBAL reference index -- without the
+ * hit list: the ANI matrix is computed in blocks of reference rows (hg_dist_full_dev into a scratch block of the ctx, at most
+ * HG_SEARCH_BLOCK_BYTES unless one row is larger; debug key "search_block_rows" forces the row count), each block goes
+ * through search_topk_select_kernel (a sorted list of k keys per thread in LDS; one compare against the k-th key rejects)
+ * and search_topk_merge_kernel (slice lists into the running Q x k state).  Device memory: one block + its slice lists (32 MiB
+ * at most unless Q * k * 8 is larger) + Q * k * 8 bytes, whatever the number of pairs at or above the threshold.  The order is
+ * total, so the output does not depend on block size, slices or scheduling.  k <= HG_SEARCH_TOPK_MAX (HG_ERR_UNSUPPORTED
+ * beyond); k == 0 or Q == 0: HG_OK, nothing is written; R == 0: every count 0, every slot empty; NULL pointers:
+ * HG_ERR_INVALID; errors of the dist call (HG_ERR_INEXACT ...) pass through.  Honours hg_ctx_set_ani_metric.
+ * Output layout of hg_topk_per_query_dev: d_out holds Q * k hg_ani_hit, query q's results at d_out[q * k ..], best first,
+ * unused slots have ref_idx = 0xFFFFFFFF (qry_idx = 0xFFFFFFFF, ani = 0); d_counts[q] <= k.
+ *   hg_search_topk_dev       : device pointers; stream-ordered, returns without synchronising (the dist call's operand
+ *                              prepass reads a few statistics words back per block; nothing else waits for the device).
+ *   hg_search_topk_block_dev : the same on rows ref_off.. / columns qry_off.. of a larger problem: hits carry global indices.
+ *   hg_search_topk           : host arrays in and out, staged through the ctx like hg_dist.
+ *   hg_search_topk_merge     : host side, no ctx: n_lists results of the layout above (lists[l], counts[l]; the same Q and
+ *                              k, disjoint references) merged by the same order into out / counts_out.
+ *   hg_search_topk_multi_dev : references sharded by rows -- shard s holds ref_rows[s] consecutive rows at d_ref_hv[s] /
+ *                              d_ref_norm2[s] on its device, global row order = shard order -- and ALL Q query rows on every
+ *                              shard (d_qry_hv[s] / d_qry_norm2[s]: the small side is broadcast, like
+ *                              hg_hamming_search_multi; no reference row moves).  Every shard runs
+ *                              hg_search_topk_block_dev; the lists are merged on the host into out / counts (host memory). */
+#define HG_SEARCH_TOPK_MAX 64u
+#define HG_SEARCH_BLOCK_BYTES ((size_t)256 << 20) /* budget of the scratch block of the ANI matrix: 256 MiB */
+hg_status hg_search_topk_dev(hg_ctx *ctx, const int16_t *d_ref_hv, const int32_t *d_ref_norm2, size_t R,
+                             const int16_t *d_qry_hv, const int32_t *d_qry_norm2, size_t Q, uint32_t hv_d, uint32_t ksize,
+                             float ani_th, uint32_t k, hg_ani_hit *d_out, uint32_t *d_counts);
+hg_status hg_search_topk_block_dev(hg_ctx *ctx, const int16_t *d_ref_hv, const int32_t *d_ref_norm2, size_t R, size_t ref_off,
+                                   const int16_t *d_qry_hv, const int32_t *d_qry_norm2, size_t Q, size_t qry_off,
+                                   uint32_t hv_d, uint32_t ksize, float ani_th, uint32_t k, hg_ani_hit *d_out,
+                                   uint32_t *d_counts);
+hg_status hg_search_topk(hg_ctx *ctx, const int16_t *ref_hv, const int32_t *ref_norm2, size_t R, const int16_t *qry_hv,
+                         const int32_t *qry_norm2, size_t Q, uint32_t hv_d, uint32_t ksize, float ani_th, uint32_t k,
+                         hg_ani_hit *out, uint32_t *counts);
+hg_status hg_search_topk_merge(const hg_ani_hit *const *lists, const uint32_t *const *counts, size_t n_lists, size_t Q,
+                               uint32_t k, hg_ani_hit *out, uint32_t *counts_out);
 
 /* `cluster` (no reference counterpart; its users cluster dump_ani_file's TSV, src/utils.rs:262-285, in another tool):
  * single-linkage clustering at an ANI threshold.  The graph has an edge {i, j} for every pair i < j with ani >= ani_th
@@ -675,6 +717,13 @@ hg_status hg_dist_multi_dev(hg_multi *m, const int16_t *const *d_ref_hv, const i
 hg_status hg_hamming_search_multi(hg_multi *m, const uint32_t *ref_bits, size_t R, const uint32_t *qry_bits,
                                   size_t Q, uint32_t hv_d, uint32_t max_dist, hg_ham_hit *out, size_t cap,
                                   size_t *n_out);
+
+/* hg_search_topk_dev over all shards (see "search: exact top-k per query" above); out: Q * k hg_ani_hit and counts: Q uint32
+ * of HOST memory.  The metric is the shards' (hg_multi_set_ani_metric). */
+hg_status hg_search_topk_multi_dev(hg_multi *m, const int16_t *const *d_ref_hv, const int32_t *const *d_ref_norm2,
+                                   const size_t *ref_rows, const int16_t *const *d_qry_hv, const int32_t *const *d_qry_norm2,
+                                   size_t Q, uint32_t hv_d, uint32_t ksize, float ani_th, uint32_t k, hg_ani_hit *out,
+                                   uint32_t *counts);
 
 /* ---- synthetic genomes (benchmark / test utility, not part of the reference surface) -----
  * Genome g = first_genome + i is written at d_out + i * stride as 'N' followed by L bases
