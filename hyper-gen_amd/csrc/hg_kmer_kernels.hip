@@ -428,7 +428,25 @@ struct GeoS {
   static constexpr int ND = (K + 3) / 4, NB = K - 4 * (ND - 1), NW = (K + 7) / 8;
   static_assert(M + K - 1 <= WIN && K <= 32, "a lane's k-mers live in its code window; 2 K bits fit a 64-bit compare");
   static_assert(((N_R - K) & 3) == 3, "reverse phase of start j is 3 - (j & 3)");
+  // A tile is INTERIOR when every byte a lane of it fetches holds bases of the genome: the last lane's window ends at
+  // tile_start + (UNITS - 1) M + WIN (packed: WIN codes, and the bitmap word's bits up to the 64th matter only below
+  // WIN) resp. + 4 (DW + 1) (ASCII), both <= tile_start + SPAN.  Its staging addresses are a scalar base plus a lane
+  // constant, which rests on:
+  static constexpr int SPAN = NB_T + WIN;           // a tile at tile_start is interior iff tile_start + SPAN <= n_bps
+  static constexpr int PAR8 = (TILE % 8) / 4;       // 1: tile_start & 7 alternates between 0 and 4 from tile to tile
+  static_assert(TILE % 4 == 0 && ITEM % 4 == 0, "a tile starts at a whole code byte and an aligned ASCII dword");
+  static_assert(TILE % 8 == 0 || TILE % 8 == 4, "a tile starts at bit 0 or bit 4 of a bitmap byte");
+  static_assert(4 * (DW + 1) <= WIN && (UNITS - 1) * M + WIN <= SPAN, "SPAN covers the last lane's fetches");
+  static_assert(SPAN - (UNITS - 1) * M >= WIN && SPAN - (UNITS - 1) * M >= M, "no lane of an interior tile has a base behind the end in its window");
+  static_assert(SPAN - K + 1 > (WG - 64) * M, "every wave of an interior tile has k-mer starts");
 };
+// (hg_kmer_tile_starts / hg_kmer_item_tiles give the host ONE geometry per code-window class)
+template <int... Ks>
+constexpr bool geos_one_geometry_per_class(std::integer_sequence<int, Ks...>) {
+  return ((GeoS<Ks + 1>::TILE == GeoS<(Ks + 1 <= 21 ? 21 : 32)>::TILE && GeoS<Ks + 1>::TILES == GeoS<21>::TILES &&
+           GeoS<Ks + 1>::SPAN == GeoS<(Ks + 1 <= 21 ? 21 : 32)>::SPAN) && ...);
+}
+static_assert(geos_one_geometry_per_class(std::make_integer_sequence<int, 32>{}), "TILE, TILES and SPAN depend on K only through WIN");
 
 // PACKED: the genome is a hg_pack2 blob (include/hypergen.h: 2-bit codes, 4 bases per byte, then the not-a-base bitmap;
 // 0.375 bytes per base in HBM instead of 1) and the tile level does no classification at all: a lane fetches its whole
@@ -493,12 +511,36 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
   for (int gq = 0; gq < M / 4; ++gq)
     aR[gq] = (uint32_t)(uintptr_t)(lds_u8p)(reinterpret_cast<const uint8_t *>(s_r)) + 4u * ((uint32_t)(N_R - K) >> 2) - M * tid - 8u * gq;
 
-  // stage unit u of the tile: bases [M u, M u + M) at genome position P, one lookahead dword
-  auto stage_unit = [&](uint32_t u, uint64_t tile_start, uint32_t par) __attribute__((always_inline)) {
+  // A tile's scalar load base, as a global-memory pointer.  The empty statement pins it to a scalar register pair inside
+  // the tile loop: left alone, the compiler adds the lane's offset to the genome's base once per item instead and carries
+  // a 64-bit vector address that it advances per tile -- the arithmetic the interior front end is there to avoid.  With
+  // a 32-bit lane offset the loads take the form global_load v, v_off, s[base:base+1].  The lane offsets are constants of
+  // the lane, kept in io_seq / io_mask and passed through an empty statement at the top of every tile, so that what is
+  // carried from tile to tile is the 32-bit value and not its 64-bit extension.
+  using glb_u8p = __attribute__((address_space(1))) const uint8_t *;
+  using glb_u32p = __attribute__((address_space(1))) const uint32_t *;
+  using glb_u32up = __attribute__((address_space(1))) const uint32_t __attribute__((aligned(1))) *;
+  using glb_u64up = __attribute__((address_space(1))) const uint64_t __attribute__((aligned(1))) *;
+  auto tile_base = [](const uint8_t *p) __attribute__((always_inline)) {
+    uint64_t a = (uint64_t)(uintptr_t)p;
+    asm volatile("" : "+s"(a));
+    return (glb_u8p)a;
+  };
+  uint32_t io_seq = (PACKED ? 3u : (uint32_t)M) * tid;  // the lane's unit from the tile's base: code bytes / ASCII bytes
+  uint32_t io_mask = (3u * tid) >> 1;                   // its bitmap byte, in a tile that starts at bit 0 of one
+  // stage unit u of the tile: bases [M u, M u + M) at genome position P, one lookahead dword.  Two front ends: a lane of
+  // an INTERIOR tile (GeoS::SPAN) loads from the tile's scalar base plus its constant 32-bit offset and has no base behind
+  // the genome end; an edge tile does the arithmetic per lane.  Behind the loads they are the same code.
+  auto stage_unit = [&](auto interiorc, uint32_t u, uint64_t tile_start, uint32_t par) __attribute__((always_inline)) {
+    constexpr bool INTERIOR = decltype(interiorc)::value;
     const uint64_t P = tile_start + (uint64_t)u * M;
     uint32_t x[DW + 1];
-    const int64_t rem64 = (int64_t)n_bps - (int64_t)P;  // bases of the genome from P on
-    if (rem64 + 32 >= 4 * (DW + 1)) {  // the caller provides 32 readable bytes behind every genome
+    const int64_t rem64 = INTERIOR ? (int64_t)M : (int64_t)n_bps - (int64_t)P;  // bases of the genome from P on (interior: M or more)
+    if constexpr (INTERIOR) {
+      const glb_u32p src = (glb_u32p)(tile_base(gseq + tile_start) + io_seq);
+#pragma unroll
+      for (int t = 0; t <= DW; ++t) x[t] = src[t];
+    } else if (rem64 + 32 >= 4 * (DW + 1)) {  // the caller provides 32 readable bytes behind every genome
       const uint32_t *src = reinterpret_cast<const uint32_t *>(gseq + P);
 #pragma unroll
       for (int t = 0; t <= DW; ++t) x[t] = src[t];
@@ -586,8 +628,22 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
   typedef uint32_t __attribute__((aligned(1))) u32u;
   typedef uint64_t __attribute__((aligned(1))) u64u;
   const uint8_t *__restrict__ gmask = seq;
-  auto stage_unit_packed = [&](uint32_t u, uint64_t tile_start, uint32_t par, uint32_t &c0, uint32_t &c1, uint32_t &c2,
-                               inv_t &invw) __attribute__((always_inline)) {
+  auto stage_unit_packed = [&](auto interiorc, uint32_t u, uint64_t tile_start, uint32_t par, uint32_t &c0, uint32_t &c1,
+                               uint32_t &c2, inv_t &invw) __attribute__((always_inline)) {
+    if constexpr (decltype(interiorc)::value) {
+      // interior tile (GeoS::SPAN): P = tile_start + M u lies at code byte (tile_start >> 2) + 3 u and at bitmap bit
+      // 4 q of byte tile_start >> 3, q = 3 u + (tile_start >> 2 & 1) -- scalar bases, 32-bit lane offsets, and no base of
+      // the window lies behind the genome end
+      const glb_u8p cp = tile_base(gseq + (tile_start >> 2)) + io_seq;
+      c0 = *(glb_u32up)cp;
+      c1 = *(glb_u32up)(cp + 4);
+      c2 = WIN > 32 ? *(glb_u32up)(cp + 8) : 0u;
+      const uint32_t q = 3u * u + (G::PAR8 ? (uint32_t)(tile_start >> 2) & 1u : 0u);
+      const uint64_t mb = *(glb_u64up)(tile_base(gmask + (tile_start >> 3)) + (G::PAR8 ? q >> 1 : io_mask));
+      const uint32_t sh = (q & 1u) << 2;
+      if constexpr (WIN > 32) invw = (inv_t)(mb >> sh);
+      else invw = __builtin_amdgcn_alignbit((uint32_t)(mb >> 32), (uint32_t)mb, sh);
+    } else {
     const uint64_t P = tile_start + (uint64_t)u * M;  // a multiple of 4: whole code bytes
     const int64_t rem64 = (int64_t)n_bps - (int64_t)P;
     const uint64_t Pc = rem64 > 0 ? P : 0;            // (a window that starts behind the end reads the blob's first bytes: all invalid anyway)
@@ -600,6 +656,7 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
     const uint64_t mb = *reinterpret_cast<const u64u *>(gmask + (Pc >> 3));
     invw = (inv_t)(mb >> (uint32_t)(Pc & 7));
     if (rem64 < WIN) invw |= rem64 <= 0 ? ~(inv_t)0 : (inv_t)(~(inv_t)0 << (uint32_t)rem64);
+    }
     const bool dirty = invw != 0;
     if (__any(dirty)) {
       if ((threadIdx.x & 63) == 0 || dirty) s_dirty[par] = 1u;  // (same value from every writer)
@@ -650,18 +707,37 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
   gseq = seq + gm.seq_off;
   gmask = seq + gm.mask_off;
   item_start = (uint64_t)(item - gm.item_first) * G::ITEM;
+  // (uniform; the plan makes no item behind the last start.  One of a foreign plan that does lie there has no tile and
+  // stages no hit, so it also skips the flush of an empty list at the loop's end, like the genome shorter than K above; the
+  // subtraction below must not wrap into "interior")
+  if (item_start >= n_starts) continue;
+  // bases from the item's start to the genome's end, saturated: tile t of the item is interior iff t TILE + SPAN <= item_rem
+  const uint64_t item_rem64 = n_bps - item_start;
+  const uint32_t item_rem = (item_rem64 >> 32) != 0 ? ~0u : (uint32_t)item_rem64;
 #pragma unroll 1
   for (int tile = 0; tile < G::TILES; ++tile, ++tile_no) {
     const uint64_t tile_start = item_start + (uint64_t)tile * G::TILE;
-    if (tile_start >= n_starts) break;  // uniform
+    if ((uint32_t)tile * (uint32_t)G::TILE + (uint32_t)(K - 1) >= item_rem) break;  // tile_start >= n_starts; uniform
     const uint32_t par = tile_no & 1u;
     uint32_t pc0 = 0, pc1 = 0, pc2 = 0;
     inv_t pinv = 0;
     // (a wave whose units all lie behind everything a live lane's window can reach -- the last k-mer start + WIN bases -- stages
     // nothing: wave-uniform; its slots of the images keep what an earlier tile left there and nobody reads them)
-    if (tile_start + (uint64_t)(tid & ~63u) * M < n_starts + (uint64_t)WIN) {
-      if constexpr (PACKED) stage_unit_packed(tid, tile_start, par, pc0, pc1, pc2, pinv);
-      else stage_unit(tid, tile_start, par);
+    // An interior tile (scalar test) takes the staging front end without address or tail arithmetic, and all its waves
+    // stage and hash.
+    asm volatile("" : "+v"(io_seq), "+v"(io_mask));
+    const bool interior = (uint32_t)tile * (uint32_t)G::TILE + (uint32_t)G::SPAN <= item_rem;
+    bool wave_live = true;
+    if (interior) {
+      if constexpr (PACKED) stage_unit_packed(std::true_type{}, tid, tile_start, par, pc0, pc1, pc2, pinv);
+      else stage_unit(std::true_type{}, tid, tile_start, par);
+    } else {
+      const uint64_t wave_start = tile_start + (uint64_t)(tid & ~63u) * M;
+      if (wave_start < n_starts + (uint64_t)WIN) {
+        if constexpr (PACKED) stage_unit_packed(std::false_type{}, tid, tile_start, par, pc0, pc1, pc2, pinv);
+        else stage_unit(std::false_type{}, tid, tile_start, par);
+      }
+      wave_live = wave_start < n_starts;
     }
 #ifndef HG_KS_EXP
 #define HG_KS_EXP 0
@@ -885,7 +961,7 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
     // A wave whose 64 x M starts all lie behind the genome's last k-mer hashes nothing (wave-uniform): a 2 kbp genome fills
     // three of its one tile's four waves, the last tile of a 10 kbp genome two -- the idle wave only meets the others at the
     // barriers, and its issue slots go to the other workgroups of the CU (2 kbp genomes: 0.27 -> 0.4 of the per-base rate).
-    const bool wave_live = tile_start + (uint64_t)(tid & ~63u) * M < n_starts;
+    // (Every wave of an interior tile has starts; an edge tile made the test beside its staging test above.)
     if (wave_live) {
       if constexpr (ASM_BODY) {
         if (!tile_dirty) kmers_asm(std::false_type{});

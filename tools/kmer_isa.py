@@ -10,7 +10,9 @@ The kernel is compiled to gfx950 assembly with the flags of hyper-gen_amd/csrc/M
     (word reads of k-mer j + 1, t1ha2 of k-mer j, threshold compare) and the scalar test of the hit mask; the twelve
     blocks of the clean-tile copy of the loop are averaged;
   * the tile level: staging (load, classify, the eight phase images, codes, validity word), the code window and the
-    barriers, once per 12 k-mers and lane.
+    barriers, once per 12 k-mers and lane.  Staging is compiled twice: the INTERIOR tile's copy (loads of the form
+    global_load v, v_off, s[base]: all tiles of a genome but its last one or two) is the tile level; the edge tile's
+    copy (64-bit vector addresses, genome-end arithmetic) is a rare path.
 Not on the main path ("rare"): the u/U -> T rewrite (HG_NORM_U2T only), the per-base validity mask (tiles with a non-base
 or a genome end), the second copy of the k-mer loop (same instructions, with the validity test in its hit path), hit
 staging (1 k-mer in `scaled`), byte-wise tail loads, prologue / epilogue.
@@ -108,11 +110,24 @@ def main():
     assert len(hash_blocks) == 2 * M, "expected two copies of the %d-k-mer loop, found %d hash blocks" % (M, len(hash_blocks))
     body = hash_blocks[:M]   # (the two copies' main-path blocks are the same instructions)
     md = blocks[hash_blocks[0]][0]  # loop depth of the tile loop (1 until round 5; 2 since the work items of a group are a loop around it)
+    # the edge tile's staging copy: from the block that forms the wave's 64-bit start (or loads through a vector address) to the
+    # block in front of the tile's first barrier -- or of the interior copy, should the compiler lay that one out second
+    SADDR, VADDR = r"global_load_\w+ v\S+, v\d+, s\[", r"global_load_\w+ v\S+, v\[\d+:\d+\], off"
+    staging = [i for i in range(min(hash_blocks)) if blocks[i][0] == md]
+    assert any(re.search(SADDR, text[i]) for i in staging), "no interior staging copy (scalar-base loads) in front of the k-mer loop"
+    edge, inside = set(), False
+    for i in staging:
+        if "s_barrier" in text[i] or re.search(SADDR, text[i]):
+            inside = False
+        elif cnt[i]["v_lshl_add_u64"] or cnt[i]["global_load_ubyte"] or re.search(VADDR, text[i]):
+            inside = True
+        if inside:
+            edge.add(i)
     main_ops, rare_ops = collections.Counter(), collections.Counter()
     weights = collections.Counter()
     for i, ((d, b), c) in enumerate(zip(blocks, cnt)):
         in_loop_copy = min(hash_blocks) <= i <= max(hash_blocks)
-        rare = (d != md or (in_loop_copy and i not in body)
+        rare = (d != md or (in_loop_copy and i not in body) or i in edge
                 or any(c[o] for o in ("ds_add_rtn_u32", "global_atomic_add", "flat_store_dwordx2", "global_store_dwordx2",
                                       "global_load_ubyte", "s_endpgm"))
                 or (c["v_mul_lo_u32"] >= 2 and c["v_mad_u64_u32"] == 0)                 # the per-base validity mask
@@ -141,7 +156,7 @@ def main():
            "by_class_per_kmer": {k: round(v, 3) for k, v in by_class.items()},
            "top_opcodes_per_kmer": {k: round(v, 3) for k, v in main_ops.most_common(40)},
            "method": "tools/kmer_isa.py: hipcc -S of hg_kmer_kernels.hip (Makefile flags); the twelve k-mer body blocks of one "
-                     "copy of the loop + the tile-level blocks, per k-mer (see the tool's header)"}
+                     "copy of the loop + the tile-level blocks (staging: the interior tile's copy), per k-mer (see the tool's header)"}
     out = os.path.join(ROOT, "profiles")
     json.dump(res, open(os.path.join(out, tag + SUFFIX + ".json"), "w"), indent=1, sort_keys=True)
     with open(os.path.join(out, tag + SUFFIX + ".txt"), "w") as fo:
@@ -155,7 +170,7 @@ def main():
         fo.write("\n%-28s %10s   class\n" % ("opcode", "per k-mer"))
         for op, n in main_ops.most_common(60):
             fo.write("%-28s %10.2f   %s\n" % (op, n, cls(op)))
-        fo.write("\nrare paths (u/U -> T rewrite, validity mask, second loop copy, hit staging, tails, prologue/epilogue): %d static VALU instructions\n"
+        fo.write("\nrare paths (u/U -> T rewrite, validity mask, second loop copy, hit staging, edge-tile staging, tails, prologue/epilogue): %d static VALU instructions\n"
                  % res["rare_paths_static_valu"])
     print(open(os.path.join(out, tag + SUFFIX + ".txt")).read())
 

@@ -98,6 +98,10 @@ L += ["", "## the other files", "",
       "| `%s_derived.md` | per-kernel derived metrics (instr / cycle, MFMA busy, LDS busy, LDS conflicts, L2 hit, wait split, HBM bytes) | `tools/derive_prof.py %s` |" % (tag, tag),
       "| `%s_kmer_traffic.json`, `%s_kmer_ascii_traffic.json`, `%s_dist_traffic.json` | the `roofline.traffic` figures `bench.py` reports | idem |" % (tag, tag, tag),
       "| `%s_kmer_packed_isa.*`, `%s_kmer_isa.*` | static instruction budget of `kmer_sample_shared<21, true, PACKED>` by class, per k-mer | `tools/kmer_isa.py %s [packed]` |" % (tag, tag, tag),
+      # (rows of single changes name their own files, like the r06 .. r01 rows below: `tag` is the round of the full profile set)
+      "| `r10_kmer_ab.txt`, `r10_kmer_packed_isa.*`, `r10_kmer_isa.*` | interior tiles of `kmer_sample_shared` staged with scalar addressing: the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32 and forward-only k = 16, `SQ_INSTS_VALU`, bench line), the register table, and the static budgets with the interior staging copy as the tile level | `tools/kmer_time.py`, `tools/kmer_isa.py r10 [packed]` |",
+      *(["| `r10_kernel_stats.csv`, `r10_rocprofv3_kernel_stats_full.csv`, `r10_pmc.json`, `r10_derived.md`, `r10_kmer_traffic.json`, `r10_kmer_ascii_traffic.json` | the bench command's kernel stats and counters on the sources of that change (the k-mer kernel's `roofline.valu_issue` and `roofline.traffic` in `bench.py`; no dist-only run: the dist figures stay r06's) | `tools/profile_gpu.sh r10`, `tools/derive_prof.py r10` |"] if os.path.exists(os.path.join(P, "r10_pmc.json")) else []),
+      "| `r08_kmer_ab.txt`, `r08_kmer_packed_isa.*`, `r08_kmer_isa.*` | threshold and strand compare on dwords: the same protocol one change earlier | idem |",
       "| `r06_dist_epilogue.md` (+ `r06_dist_epilogue_raw.txt`) | where the dist kernel's time goes between \"no candidates\" and 1.29 M hits: every tile split into main loop / phase 0 / append / phase 2 / reservation / hit write from stamps of all 1 280 workgroups, A/B builds of the phase-2 arithmetic, the sixth round of 47 left-over tiles | `tools/dist_epilogue_split.py` on `-DHG_DIST_STAMPS` builds (`tools/build_variant.sh`) |",
       "| `r06_small_and_long_k.txt` | the small-genome ladder (400 000 x 2 kbp .. 1 000 x 5 Mbp: Mbase/s and kernel times per step) and the k-mer kernel's time at k = 21 .. 255, with what changed in round 6 | `tools/small_genome_sweep.sh`, `tools/kmer_time.py` |",
       "| `r06_realistic_kernel_stats.txt` | `rocprofv3 --kernel-trace --stats` of the clean / draft-assembly / many-small-genomes sketch step, both resident forms (round 6: the step's new kernels -- `sort_unique_wave_kernel`, `sort_unique_rest_kernel`, `sketch_finish_kernel`) | `tools/profile_realistic.sh r06` |",
@@ -114,5 +118,11 @@ L += ["", "## the other files", "",
       "| `r04_dist_persistent_negative.txt` | the persistent-workgroup GEMM variant of round 4: timings against one tile per workgroup and whole-tile `s_memtime` stamps of both | `tools/dist_only.py`, `tools/dist_tile_stamps.py` on `-DHG_DIST_STAMPS` builds |",
       "| `r03_mfma_ceiling.txt` | what the matrix pipe sustains in the GEMM's loop shape, ingredient by ingredient | `tools/mfma_microbench.hip` |",
       "| `r01_instruction_rates.txt` | measured issue cost of the integer instructions the k-mer kernel is made of | `tools/gpu_microbench.hip` |"]
+L += ["", "## `search_topk_bench.json` -- `python tools/search_topk_bench.py`", "",
+      "The bounded-memory `search` (`hg_search_topk_dev`) against the hit-list route (`hg_dist_dev` + `hg_topk_per_query_dev`),",
+      "alternating in one process, three rounds after a warm-up: wall ms per round, median, min and max, the ratio of the medians and",
+      "the hits the old route holds. `select_bytes` is what the selection kernels of one new call read; divided by the kernel's time",
+      "from `rocprofv3 --kernel-trace --stats -- python tools/search_topk_bench.py --only new` it is the kernel's bytes per second.",
+      "A file whose `status` is \"not measured\" records that no such run has been made on an MI355X yet."]
 open(os.path.join(P, "README.md"), "w").write("\n".join(L) + "\n")
 print("\n".join(L))
