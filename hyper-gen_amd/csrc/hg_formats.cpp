@@ -27,6 +27,7 @@
 
 #include "../../include/hypergen.h"
 #include "hg_host.h"
+#include "hg_pack2.h"
 
 extern "C" uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d) {
   if (!hv || hv_d == 0) return 6;
@@ -406,7 +407,7 @@ __attribute__((target("avx512f,avx512bw,avx512vbmi"))) size_t pack2_avx512(const
 #endif
 }  // namespace
 
-extern "C" size_t hg_pack2_size(size_t n_bps) { return al16((n_bps + 3) / 4) + al16((n_bps + 7) / 8); }
+extern "C" size_t hg_pack2_size(size_t n_bps) { return hg_pack2_code_bytes(n_bps) + hg_pack2_mask_bytes(n_bps); }
 
 namespace {
 // bases [0, n) of `seq` -> codes / mask, both pointing at the bytes of base 0 (n a multiple of 32, or the tail)
@@ -447,7 +448,7 @@ uint8_t *thread_mask(size_t bytes) {
 
 // zero padding of the code area, then the mask behind it
 void pack2_finish(uint8_t *out, size_t n_bps, uint8_t *mask) {
-  const size_t cb = al16((n_bps + 3) / 4), mb = al16((n_bps + 7) / 8), used = (n_bps + 3) / 4, mused = (n_bps + 7) / 8;
+  const size_t cb = hg_pack2_code_bytes(n_bps), mb = hg_pack2_mask_bytes(n_bps), used = (n_bps + 3) / 4, mused = (n_bps + 7) / 8;
   if (cb > used) std::memset(out + used, 0, cb - used);
   if (mb > mused) std::memset(mask + mused, 0, mb - mused);
   std::memcpy(out + cb, mask, mb);
@@ -458,12 +459,12 @@ void pack2_finish(uint8_t *out, size_t n_bps, uint8_t *mask) {
 // per base -- an assembly has a handful of them (N gaps between contigs, the 'N' per record start), so the link carries
 // 0.25 bytes per base instead of 0.375.  Layout: [codes, padded to 16 bytes][u32 n_runs, u32 0, n_runs x {u32 start,
 // u32 length}, padded to 16 bytes].  The device rebuilds the bitmap from the table (hg_stream.hip: expand_runs_kernel).
-extern "C" size_t hg_pack2s_size(size_t n_bps, size_t n_runs) { return al16((n_bps + 3) / 4) + al16(8 + 8 * n_runs); }
+extern "C" size_t hg_pack2s_size(size_t n_bps, size_t n_runs) { return hg_pack2_code_bytes(n_bps) + al16(8 + 8 * n_runs); }
 
 extern "C" hg_status hg_pack2s(const uint8_t *seq, size_t n_bps, uint32_t norm_mode, uint8_t *out, size_t cap, size_t *size_out) {
   if ((n_bps && !seq) || !out || !size_out || norm_mode > HG_NORM_U2T) return HG_ERR_INVALID;
   if (n_bps >= ((size_t)1 << 32)) return HG_ERR_UNSUPPORTED;  // (32-bit run positions; such a genome takes hg_pack2)
-  const size_t cb = al16((n_bps + 3) / 4), used = (n_bps + 3) / 4, mwords = (n_bps + 63) / 64;
+  const size_t cb = hg_pack2_code_bytes(n_bps), used = (n_bps + 3) / 4, mwords = (n_bps + 63) / 64;
   *size_out = cb + 16;
   if (cap < cb + 16) return HG_ERR_CAPACITY;
   uint8_t *mask = thread_mask(8 * mwords + 64);
@@ -517,7 +518,7 @@ extern "C" hg_status hg_pack2s(const uint8_t *seq, size_t n_bps, uint32_t norm_m
 // `out` may be `seq` itself (packing in place): the codes trail the reads, the mask is collected aside.
 extern "C" hg_status hg_pack2(const uint8_t *seq, size_t n_bps, uint32_t norm_mode, uint8_t *out) {
   if ((n_bps && !seq) || !out || norm_mode > HG_NORM_U2T) return HG_ERR_INVALID;
-  uint8_t *mask = thread_mask(al16((n_bps + 7) / 8));
+  uint8_t *mask = thread_mask(hg_pack2_mask_bytes(n_bps));
   if (!mask) return HG_ERR_OOM;
   pack2_span(seq, n_bps, norm_mode == HG_NORM_U2T, out, mask);
   pack2_finish(out, n_bps, mask);
@@ -528,11 +529,11 @@ extern "C" hg_status hg_pack2(const uint8_t *seq, size_t n_bps, uint32_t norm_mo
 // multiple of 64 or n_bps; the piece that ends the genome also writes the two paddings): several host threads pack one
 // genome, or many, in pieces of even size.  `out` must not overlap `seq`.
 void hg_pack2_piece(const uint8_t *seq, size_t n_bps, uint32_t norm_mode, uint8_t *out, size_t b0, size_t b1) {
-  const size_t cb = al16((n_bps + 3) / 4);
+  const size_t cb = hg_pack2_code_bytes(n_bps);
   uint8_t *mask = out + cb;
   pack2_span(seq + b0, b1 - b0, norm_mode == HG_NORM_U2T, out + (b0 >> 2), mask + (b0 >> 3), true);
   if (b1 == n_bps) {
-    const size_t mb = al16((n_bps + 7) / 8), used = (n_bps + 3) / 4, mused = (n_bps + 7) / 8;
+    const size_t mb = hg_pack2_mask_bytes(n_bps), used = (n_bps + 3) / 4, mused = (n_bps + 7) / 8;
     if (cb > used) std::memset(out + used, 0, cb - used);
     if (mb > mused) std::memset(mask + mused, 0, mb - mused);
   }
@@ -715,11 +716,11 @@ hg_status hg_read_fastx_impl(const char *path, uint32_t mode, uint8_t **pbuf, si
     st = HG_ERR_OOM;
   }
   if (st == HG_OK && !grow(buf, cap, fsize + 64, 0, user)) st = HG_ERR_OOM;
-  if (st == HG_OK && pack && !(mask = thread_mask(al16((fsize + 7) / 8) + 64))) st = HG_ERR_OOM;
+  if (st == HG_OK && pack && !(mask = thread_mask(hg_pack2_mask_bytes(fsize) + 64))) st = HG_ERR_OOM;
   // The buffers were sized from fstat(), but the file may hold more than st_size by the time it is read (a file
   // that is still being appended to, procfs-style files that report size 0): every block checks the room it needs
   // first and grows the result -- and, when packing, the mask -- keeping what was produced so far.
-  size_t mask_cap = al16((fsize + 7) / 8) + 64;
+  size_t mask_cap = hg_pack2_mask_bytes(fsize) + 64;
   auto emit = [&](size_t n_lines_bytes) {  // blk[0, n) holds whole lines (or the file's last, open one)
     // a merged block is never longer than its text: every 'N' replaces a header line of at least one byte
     if (!pack) {
@@ -736,8 +737,8 @@ hg_status hg_read_fastx_impl(const char *path, uint32_t mode, uint8_t **pbuf, si
       st = HG_ERR_OOM;
       return;
     }
-    if (al16((bases_max + 7) / 8) + 64 > mask_cap) {
-      mask_cap = 2 * al16((bases_max + 7) / 8) + 64;
+    if (hg_pack2_mask_bytes(bases_max) + 64 > mask_cap) {
+      mask_cap = 2 * hg_pack2_mask_bytes(bases_max) + 64;
       if (!(mask = thread_mask(mask_cap))) {  // (a resize: the bits collected so far stay)
         st = HG_ERR_OOM;
         return;

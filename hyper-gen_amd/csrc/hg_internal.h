@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/hypergen.h"
+#include "hg_pack2.h"
 
 // ---- sketch batch plans (hg_sketch_plan.hip) ----------------------------------------------------------------
 // Geometry of one sketch batch as the k-mer kernel sees it: hit regions and work items per genome.  Kept by the ctx
@@ -248,6 +249,10 @@ uint32_t hg_kmer_item_tiles(uint32_t ksize);
 // lens[i] bases goes to d_blobs + blob_offs[i] (multiples of 16).  d_tab: 3 * n uint64 of device scratch for the tables.
 hipError_t hg_launch_pack2(hipStream_t st, const uint8_t *d_seq, const uint64_t *d_tab, uint32_t n, uint32_t blocks_max,
                            uint32_t u2t, uint8_t *d_blobs);
+// the job-table kernels of a stream chunk (hg_pack2.h: n_blocks = the sum of the jobs' block counts, first_block ascending):
+// every job's blob in d_pk expanded to ASCII at d_out + out_off / every sparse job's bitmap rebuilt from its run table
+hipError_t hg_launch_unpack2_jobs(hipStream_t st, const uint8_t *d_pk, uint8_t *d_out, const UnpackJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks);
+hipError_t hg_launch_expand_runs(hipStream_t st, uint8_t *d_pk, const SparseJob *d_jobs, uint32_t n_jobs, uint32_t n_blocks);
 
 // keys one workgroup can sort in LDS; genomes with more sampled hashes are sorted in place in
 // global memory, which needs a power-of-two sized hit region (the host rounds hit_cap up).

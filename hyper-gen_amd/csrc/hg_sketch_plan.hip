@@ -46,7 +46,7 @@ hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uin
     hg_genome_meta &m = t.meta[g];
     m.seq_off = b.offsets[g];
     m.n_bps = b.lens[g];
-    m.mask_off = b.mask_offs ? b.mask_offs[g] : m.seq_off + (((m.n_bps + 3) / 4 + 15) & ~(uint64_t)15);  // (read by the packed kernels only)
+    m.mask_off = b.mask_offs ? b.mask_offs[g] : m.seq_off + hg_pack2_code_bytes(m.n_bps);  // (read by the packed kernels only)
     const uint64_t n_starts = m.n_bps >= ksize ? m.n_bps - ksize + 1 : 0;
     const uint64_t expect = n_starts / scaled;
     uint64_t cap = expect * 2 + 1024;    // expected n_starts/scaled; sd ~ sqrt of that
@@ -182,7 +182,7 @@ hg_status hg_pack_batch(hg_ctx *c, const uint8_t *d_seq, const uint64_t *seq_off
     max_len = std::max(max_len, lens[g]);
   }
   HG_HIP(c, hipMemcpyAsync(c->w_pktab.p, tab, 3 * n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  const uint64_t groups = ((((max_len + 7) / 8 + 15) & ~(uint64_t)15) + 3) / 4;  // lanes per genome: one per 4 bitmap bytes
+  const uint64_t groups = (hg_pack2_mask_bytes(max_len) + 3) / 4;  // lanes per genome: one per 4 bitmap bytes
   const uint64_t blocks = (groups + 255) / 256;
   if (blocks > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "pack2: genome too long for one launch");
   if (blocks)

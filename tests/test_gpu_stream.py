@@ -341,3 +341,35 @@ def test_single_thread_push_everything_then_pop_and_reused_tags(hg, orc):
             res.append(r)
         assert len(res) == 300 and all(r[0] == 7 for r in res)
         assert sorted(int(r[3]) for r in res) == sorted(int(x) for x in nh[:300])
+
+
+def test_stream_more_packed_genomes_than_a_job_table_holds(hg, orc):
+    """4 200 short genomes, the three input kinds in rotation, pushed back to back by one thread: more than the 4 096
+    entries of a chunk's job tables (and of a chunk), so wherever the chunks end, no table may take a genome too many.
+    Equality only -- how many genomes share a chunk depends on timing; the bound itself is checked on the CPU
+    (tests/native/stream_layout_driver.cpp)."""
+    n = 4200
+    rng = np.random.default_rng(17)
+    base = orc.synth_genome(11, 60_000)[1:]
+    starts = rng.integers(0, base.size - 600, n)
+    sizes = rng.integers(40, 601, n)
+    genomes = [base[s:s + m].copy() for s, m in zip(starts, sizes)]
+    for i in range(0, n, 5):  # some with a run or two of non-bases
+        a = int(rng.integers(0, sizes[i] - 8))
+        genomes[i][a:a + 1 + i % 7] = ord("N")
+    p = hg.default_params(scaled=5)
+    with hg.Context(0) as ctx:
+        hv, n2, nh = ctx.sketch_batch(genomes, p)
+    with hg.SketchStream((0,), p) as st:
+        for i, g in enumerate(genomes):
+            blob = hg.pack2s(g) if i % 3 == 2 else None
+            if i % 3 == 0:
+                st.push(g, i)
+            elif blob is None:
+                st.push_packed(hg.pack2(g), g.size, i)
+            else:
+                st.push_packed_sparse(blob, g.size, i)
+        st.finish()
+        out = _drain(st, n)
+    for i in range(n):
+        assert out[i][2] == nh[i] and out[i][1] == n2[i] and np.array_equal(out[i][0], hv[i]), i

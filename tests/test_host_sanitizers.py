@@ -32,3 +32,15 @@ def test_call_pool_and_piece_packer_under_tsan(tmp_path):
     if "FATAL: ThreadSanitizer: unexpected memory mapping" in out.stderr:
         pytest.skip("ThreadSanitizer cannot map its shadow in this container")
     assert out.returncode == 0 and "tsan driver ok" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_stream_chunk_layout_under_asan_ubsan(tmp_path):
+    """the chunk layout of the streaming sketcher (hg_stream_layout.h: where every genome of a chunk goes, when the chunk
+    closes, the size ramp, when an area grows) played through seeded push sequences of all three input kinds"""
+    exe = tmp_path / "layout_driver"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "native", "stream_layout_driver.cpp"),
+                           "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "stream layout driver ok" in out.stdout, out.stdout + out.stderr
