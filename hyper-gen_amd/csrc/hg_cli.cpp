@@ -81,6 +81,8 @@ struct Cli {
   int search_path = 0;  // --search_path auto|hits|topk (search; testing aid): 0 = topk whenever top_n <= HG_SEARCH_TOPK_MAX, 1 = the hit list, 2 = topk
   bool search_path_given = false;
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
+  bool greedy = false, linkage_given = false;     // --linkage single|greedy (cluster)
+  bool order_size = false, order_given = false;   // --order file|size (cluster --linkage greedy)
 };
 
 Cli parse(int argc, char **argv) {
@@ -96,7 +98,7 @@ Cli parse(int argc, char **argv) {
                 "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
                 "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
                 "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
-                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0]\n\n"
+                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy]\n\n"
                 "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
                 "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
                 "         -Q --quant_scale [1.0], -a --ani_th [85.0], -D --device [cpu]\n"
@@ -113,7 +115,14 @@ Cli parse(int argc, char **argv) {
                 "         once; 1 = every sampled k-mer, the reference's set), --search_path auto|hits|topk [auto] (search:\n"
                 "         topk selects the -n best per query on the device while blocks of the ANI matrix stream past -- memory\n"
                 "         does not grow with the number of pairs above -a; hits builds the thresholded hit list first; auto =\n"
-                "         topk for -n <= 64, hits beyond; both write the same file)\n");
+                "         topk for -n <= 64, hits beyond; both write the same file), --linkage single|greedy [single]\n"
+                "         (cluster: greedy = one representative per cluster, as dereplication tools choose them -- a sketch is\n"
+                "         a representative unless an earlier representative is within -a of it, else it joins the best such\n"
+                "         one; representatives are pairwise below -a, every member is within -a of its own; one line per\n"
+                "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative),\n"
+                "         --order file|size [file] (cluster --linkage greedy: the order the sketches are processed in; size =\n"
+                "         descending hv_norm_2, ties in file order -- the most complete genome of a group represents it;\n"
+                "         cluster ids count the representatives in that order, the lines stay in file order)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -122,7 +131,7 @@ Cli parse(int argc, char **argv) {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
       {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
-      {"min_count", '\x02'}, {"search_path", '\x03'}};
+      {"min_count", '\x02'}, {"search_path", '\x03'}, {"linkage", '\x04'}, {"order", '\x05'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -188,6 +197,18 @@ Cli parse(int argc, char **argv) {
         else die("invalid value '" + val + "' for '--search_path' (auto | hits | topk)");
         c.search_path_given = true;
         break;
+      case '\x04':  // (long form only) cluster only (extension)
+        if (val == "single") c.greedy = false;
+        else if (val == "greedy") c.greedy = true;
+        else die("invalid value '" + val + "' for '--linkage' (single | greedy)");
+        c.linkage_given = true;
+        break;
+      case '\x05':  // (long form only) cluster --linkage greedy only (extension)
+        if (val == "file") c.order_size = false;
+        else if (val == "size") c.order_size = true;
+        else die("invalid value '" + val + "' for '--order' (file | size)");
+        c.order_given = true;
+        break;
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -199,6 +220,9 @@ Cli parse(int argc, char **argv) {
   if (c.search_path_given && c.mode != "search") die("--search_path is not supported by " + c.mode + ": it chooses how search selects its results");
   if (c.search_path == 2 && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
+  if (c.linkage_given && c.mode != "cluster") die("--linkage is not supported by " + c.mode + ": it chooses how cluster forms its clusters");
+  if (c.order_given && !(c.mode == "cluster" && c.greedy))
+    die("--order needs cluster --linkage greedy: single-linkage components do not depend on the order of the sketches");
   if (c.min_count_given && c.mode != "sketch") die("--min_count is not supported by " + c.mode + ": the filter needs the k-mer counts, which a sketch no longer has");
   return c;
 }
@@ -442,7 +466,9 @@ struct DevSet {
   std::vector<size_t> rows;
 };
 // whole: every shard gets ALL records (the query side of the top-k search: the small side is broadcast).
-void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false) {
+// perm (one shard only; cluster --order): row k of the matrix is record perm[k] -- the decode offsets are permuted, the
+// payload bytes travel as they lie in the file.
+void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false, const std::vector<uint32_t> *perm = nullptr) {
   char buf[96];
   std::snprintf(buf, sizeof buf, "Decompressing sketch with HV dim=%llu", (unsigned long long)L.hv_d);
   logline("INFO", buf);
@@ -460,13 +486,25 @@ void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false) {
     if (b1 > img_bytes || b0 > b1) die("corrupt sketch payload");
     std::vector<uint64_t> rel(hi - lo);
     for (size_t i = lo; i < hi; ++i) rel[i - lo] = L.off[i] - b0;
+    std::vector<int32_t> p_n2;
+    std::vector<uint8_t> p_q, p_lay;
+    if (perm) {
+      if (ns != 1 || perm->size() != L.n) die("internal: a permuted upload takes one shard and every record");
+      p_n2.resize(L.n), p_q.resize(L.n), p_lay.resize(L.n);
+      for (size_t k = 0; k < L.n; ++k) {
+        const uint32_t i = (*perm)[k];
+        rel[k] = L.off[i] - b0, p_n2[k] = L.n2[i], p_q[k] = L.q[i], p_lay[k] = L.lay[i];
+      }
+    }
+    const int32_t *n2_src = perm ? p_n2.data() : L.n2.data() + lo;
+    const uint8_t *q_src = perm ? p_q.data() : L.q.data() + lo, *lay_src = perm ? p_lay.data() : L.lay.data() + lo;
     void *d_img = nullptr, *d_hv = nullptr, *d_n2 = nullptr;
     ck(ctx, hg_dev_alloc(ctx, b1 - b0, &d_img), "alloc");
     ck(ctx, hg_dev_alloc(ctx, (hi - lo) * L.hv_d * sizeof(int16_t), &d_hv), "alloc");
     ck(ctx, hg_dev_alloc(ctx, (hi - lo) * sizeof(int32_t), &d_n2), "alloc");
     ck(ctx, hg_copy_h2d(ctx, d_img, img + b0, b1 - b0), "upload");
-    ck(ctx, hg_copy_h2d(ctx, d_n2, L.n2.data() + lo, (hi - lo) * sizeof(int32_t)), "upload");
-    ck(ctx, hg_hv_unpack_batch_dev(ctx, static_cast<const uint8_t *>(d_img), b1 - b0, rel.data(), L.q.data() + lo, L.lay.data() + lo,
+    ck(ctx, hg_copy_h2d(ctx, d_n2, n2_src, (hi - lo) * sizeof(int32_t)), "upload");
+    ck(ctx, hg_hv_unpack_batch_dev(ctx, static_cast<const uint8_t *>(d_img), b1 - b0, rel.data(), q_src, lay_src,
                                    hi - lo, (uint32_t)L.hv_d, static_cast<int16_t *>(d_hv)), "unpack");
     ck(ctx, hg_dev_free(ctx, d_img), "free");
     D.hv[s] = static_cast<const int16_t *>(d_hv), D.n2[s] = static_cast<const int32_t *>(d_n2), D.rows[s] = hi - lo;
@@ -838,6 +876,11 @@ int run_search(const Cli &c) {
 // ANI threshold, computed where the hits are (hg_cluster_dev: the symmetric comparison in row blocks, each block's hits
 // unioned on the device).  One line per sketch record, in file order: "<file_str>\t<cluster id>\t<file_str of the
 // cluster's first member>\n" -- ids count the clusters in the order of their first members.
+// --linkage greedy (hg_cluster_greedy_dev): one representative per cluster, the sketches processed in file order or
+// (--order size) by descending hv_norm_2, ties in file order.  The rows go to the library in processing order -- the decode
+// offsets of the upload are permuted, nothing is gathered on the device -- and the lines stay in file order:
+// "<file_str>\t<cluster id>\t<file_str of its representative>\t<ANI with it, as dist prints it>\n"; ids count the
+// representatives in processing order.
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.shards) die("--shards is not supported by cluster: it runs on the first visible GPU");
@@ -853,7 +896,13 @@ int run_cluster(const Cli &c) {
   load(c.path, L);
   opener.join();
   DevSet D;
-  to_devices(multi, L, D);
+  std::vector<uint32_t> perm;  // greedy: processing position -> record
+  if (c.greedy) {
+    perm.resize(L.n);
+    for (size_t i = 0; i < L.n; ++i) perm[i] = (uint32_t)i;
+    if (c.order_size) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return L.n2[a] > L.n2[b]; });
+  }
+  to_devices(multi, L, D, false, c.order_size ? &perm : nullptr);
   char buf[512];
   std::snprintf(buf, sizeof buf, "Clustering %zu genomes at ANI threshold %.1f..", L.n, th);
   logline("INFO", buf);
@@ -863,9 +912,21 @@ int run_cluster(const Cli &c) {
   ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_rep), "alloc");
   ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_cl), "alloc");
   size_t n_cl = 0;
-  ck(ctx, hg_cluster_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
-                         static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
   std::vector<uint32_t> rep(L.n), cl(L.n);
+  std::vector<float> ani;
+  if (c.greedy) {
+    void *d_ani = nullptr;
+    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(float), &d_ani), "alloc");
+    ck(ctx, hg_cluster_greedy_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
+                                  static_cast<uint32_t *>(d_cl), static_cast<float *>(d_ani), &n_cl), "cluster");
+    ani.resize(L.n);
+    ck(ctx, hg_copy_d2h(ctx, ani.data(), d_ani, L.n * sizeof(float)), "download");
+    (void)hg_dev_free(ctx, d_ani);
+    debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
+  } else {
+    ck(ctx, hg_cluster_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
+                           static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
+  }
   ck(ctx, hg_copy_d2h(ctx, rep.data(), d_rep, L.n * sizeof(uint32_t)), "download");
   ck(ctx, hg_copy_d2h(ctx, cl.data(), d_cl, L.n * sizeof(uint32_t)), "download");
   (void)hg_dev_free(ctx, d_rep), (void)hg_dev_free(ctx, d_cl);
@@ -879,13 +940,28 @@ int run_cluster(const Cli &c) {
   size_t singletons = 0;
   for (uint32_t s : size) singletons += s == 1;
   std::string o;
-  for (size_t i = 0; i < L.n; ++i) {
-    o += hg_sketch_file_get(L.f, i)->file_str;
-    o += '\t';
-    o += std::to_string(cl[i]);
-    o += '\t';
-    o += hg_sketch_file_get(L.f, rep[i])->file_str;
-    o += '\n';
+  if (c.greedy) {
+    std::vector<uint32_t> pos(L.n);  // record -> processing position
+    for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
+    char num[16];
+    for (size_t i = 0; i < L.n; ++i) {
+      const uint32_t k = pos[i];
+      o += hg_sketch_file_get(L.f, i)->file_str;
+      o += '\t';
+      o += std::to_string(cl[k]);
+      o += '\t';
+      o += hg_sketch_file_get(L.f, perm[rep[k]])->file_str;
+      o.append(num, put_ani(num, ani[k]));  // "\t<ani>\n"
+    }
+  } else {
+    for (size_t i = 0; i < L.n; ++i) {
+      o += hg_sketch_file_get(L.f, i)->file_str;
+      o += '\t';
+      o += std::to_string(cl[i]);
+      o += '\t';
+      o += hg_sketch_file_get(L.f, rep[i])->file_str;
+      o += '\n';
+    }
   }
   FILE *f = std::fopen(c.out.c_str(), "wb");
   if (!f || std::fwrite(o.data(), 1, o.size(), f) != o.size() || std::fclose(f) != 0) die("Dump cluster file failed!");

@@ -147,8 +147,16 @@ inline unsigned grid_for(hg_ctx *c, size_t items) {
   return (unsigned)std::max<size_t>(1, std::min(want, most));
 }
 
-// the ctx's result block: [0] cluster count, [1] error word (an index >= n was given to hg_cluster_add_hits_dev)
-hg_status cluster_res(hg_ctx *c, uint32_t **out) {
+hg_status check_n(hg_ctx *c, size_t n, const uint32_t *d_rep) {
+  if (n > 0xFFFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^32 (indices are uint32)");
+  if (n && !d_rep) return hg_fail(c, HG_ERR_INVALID, "NULL rep array");
+  return HG_OK;
+}
+}  // namespace
+
+// the ctx's result block: [0] cluster count, [1] error word (an index >= n was given to hg_cluster_add_hits_dev or
+// hg_cluster_greedy_hits_dev); hg_cluster_greedy.hip keeps its round words behind them (hg_internal.h)
+hg_status hg_cluster_res(hg_ctx *c, uint32_t **out) {
   const bool fresh = c->w_clu_res.p == nullptr;
   hg_status s = hg_ensure(c, c->w_clu_res, 64);
   if (s != HG_OK) return s;
@@ -157,51 +165,10 @@ hg_status cluster_res(hg_ctx *c, uint32_t **out) {
   return HG_OK;
 }
 
-hg_status check_n(hg_ctx *c, size_t n, const uint32_t *d_rep) {
-  if (n > 0xFFFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^32 (indices are uint32)");
-  if (n && !d_rep) return hg_fail(c, HG_ERR_INVALID, "NULL rep array");
-  return HG_OK;
-}
-}  // namespace
-
-extern "C" hg_status hg_cluster_init_dev(hg_ctx *c, uint32_t *d_rep, size_t n) {
-  if (!c) return HG_ERR_INVALID;
-  hg_status s = check_n(c, n, d_rep);
-  if (s != HG_OK) return s;
-  HG_ENTER(c);
-  uint32_t *res;
-  if ((s = cluster_res(c, &res)) != HG_OK) return s;
-  hipLaunchKernelGGL(cluster_init_kernel, dim3(grid_for(c, n)), dim3(256), 0, c->stream, d_rep, (uint32_t)n, res);
-  HG_HIP(c, hipGetLastError());
-  return HG_OK;
-}
-
-extern "C" hg_status hg_cluster_add_hits_dev(hg_ctx *c, uint32_t *d_rep, size_t n, const hg_ani_hit *d_hits, size_t n_hits,
-                                             float ani_th) {
-  if (!c) return HG_ERR_INVALID;
-  hg_status s = check_n(c, n, d_rep);
-  if (s != HG_OK) return s;
-  if (n_hits == 0) return HG_OK;
-  if (!d_hits) return hg_fail(c, HG_ERR_INVALID, "NULL hit list");
-  HG_ENTER(c);
-  uint32_t *res;
-  if ((s = cluster_res(c, &res)) != HG_OK) return s;
-  hipLaunchKernelGGL(cluster_hook_kernel, dim3(grid_for(c, n_hits)), dim3(256), 0, c->stream, d_rep, (uint32_t)n, d_hits, n_hits,
-                     ani_th, res + 1);
-  HG_HIP(c, hipGetLastError());
-  return HG_OK;
-}
-
-extern "C" hg_status hg_cluster_finish_dev(hg_ctx *c, uint32_t *d_rep, size_t n, uint32_t *d_cluster, size_t *n_clusters) {
-  if (!c) return HG_ERR_INVALID;
-  if (!n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_clusters == NULL");
-  *n_clusters = 0;
-  hg_status s = check_n(c, n, d_rep);
-  if (s != HG_OK) return s;
-  if (n && !d_cluster) return hg_fail(c, HG_ERR_INVALID, "NULL cluster array");
-  HG_ENTER(c);
-  uint32_t *res;
-  if ((s = cluster_res(c, &res)) != HG_OK) return s;
+// The finishing launches on a rep[] whose trees may have any depth (the greedy resolution's have depth 1): compress + roots
+// per tile, scan (res[0] = cluster count), dense ids of the roots, ids of the other members.  Stream-ordered.
+hg_status hg_cluster_queue_ids(hg_ctx *c, uint32_t *d_rep, size_t n, uint32_t *d_cluster, uint32_t *res) {
+  hg_status s;
   const size_t n_tiles = (n + CL_TILE - 1) / CL_TILE;
   if ((s = hg_ensure(c, c->w_clu, n_tiles * sizeof(uint32_t) + 64)) != HG_OK) return s;
   auto *tiles = static_cast<uint32_t *>(c->w_clu.p);
@@ -218,6 +185,48 @@ extern "C" hg_status hg_cluster_finish_dev(hg_ctx *c, uint32_t *d_rep, size_t n,
     hipLaunchKernelGGL(cluster_member_ids_kernel, dim3(grid_for(c, n)), dim3(256), 0, c->stream, d_rep, m, d_cluster);
     HG_HIP(c, hipGetLastError());
   }
+  return HG_OK;
+}
+
+extern "C" hg_status hg_cluster_init_dev(hg_ctx *c, uint32_t *d_rep, size_t n) {
+  if (!c) return HG_ERR_INVALID;
+  hg_status s = check_n(c, n, d_rep);
+  if (s != HG_OK) return s;
+  HG_ENTER(c);
+  uint32_t *res;
+  if ((s = hg_cluster_res(c, &res)) != HG_OK) return s;
+  hipLaunchKernelGGL(cluster_init_kernel, dim3(grid_for(c, n)), dim3(256), 0, c->stream, d_rep, (uint32_t)n, res);
+  HG_HIP(c, hipGetLastError());
+  return HG_OK;
+}
+
+extern "C" hg_status hg_cluster_add_hits_dev(hg_ctx *c, uint32_t *d_rep, size_t n, const hg_ani_hit *d_hits, size_t n_hits,
+                                             float ani_th) {
+  if (!c) return HG_ERR_INVALID;
+  hg_status s = check_n(c, n, d_rep);
+  if (s != HG_OK) return s;
+  if (n_hits == 0) return HG_OK;
+  if (!d_hits) return hg_fail(c, HG_ERR_INVALID, "NULL hit list");
+  HG_ENTER(c);
+  uint32_t *res;
+  if ((s = hg_cluster_res(c, &res)) != HG_OK) return s;
+  hipLaunchKernelGGL(cluster_hook_kernel, dim3(grid_for(c, n_hits)), dim3(256), 0, c->stream, d_rep, (uint32_t)n, d_hits, n_hits,
+                     ani_th, res + 1);
+  HG_HIP(c, hipGetLastError());
+  return HG_OK;
+}
+
+extern "C" hg_status hg_cluster_finish_dev(hg_ctx *c, uint32_t *d_rep, size_t n, uint32_t *d_cluster, size_t *n_clusters) {
+  if (!c) return HG_ERR_INVALID;
+  if (!n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_clusters == NULL");
+  *n_clusters = 0;
+  hg_status s = check_n(c, n, d_rep);
+  if (s != HG_OK) return s;
+  if (n && !d_cluster) return hg_fail(c, HG_ERR_INVALID, "NULL cluster array");
+  HG_ENTER(c);
+  uint32_t *res;
+  if ((s = hg_cluster_res(c, &res)) != HG_OK) return s;
+  if ((s = hg_cluster_queue_ids(c, d_rep, n, d_cluster, res)) != HG_OK) return s;
   // (the publishing kernel clears both words behind its copy: the next clustering on this ctx starts clean)
   const uint32_t *h_res = nullptr;
   if ((s = hg_publish_words(c, res, 2, &h_res, 2)) != HG_OK) return s;

@@ -115,7 +115,9 @@ struct hg_ctx {
   Buf w_sorthits; // keys / permutations / scratch of the device-side hit ordering
   Buf w_clu_res;  // clustering: 16 result words ([0] cluster count, [1] error word of the hook kernel), never regrown
   Buf w_clu;      // clustering: per-tile root counts of the dense-id scan
-  Buf w_clu_hits; // hg_cluster_dev: scratch hit list of one row block
+  Buf w_clu_hits; // hg_cluster_dev / hg_cluster_greedy_dev: scratch hit list of one row block
+  Buf w_grd;      // hg_cluster_greedy*: per-node state -- n 64-bit best words, then n status words, then n blocked marks
+  uint64_t greedy_rounds = 0;  // rounds the last greedy call ran, summed over its blocks (hg_ctx_cluster_greedy_rounds)
   Buf w_srch_blk;   // hg_search_topk*: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
   Buf w_srch_lists; // ... the slice lists of one block: keys, then counts
   Buf w_srch_state; // ... the running k best keys per query, state[j * Q + q]
@@ -160,6 +162,7 @@ struct hg_ctx {
   std::string dbg_dist_tile, dbg_dist_path, dbg_ham_path, dbg_dist_order, dbg_kmer_input, dbg_hostfed, dbg_sketch_path;
   int dbg_sort_buckets = 0;
   uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the scratch list of hg_cluster_dev starts with (0: its own size)
+  uint64_t dbg_greedy_rounds = 0;  // test hook "greedy_rounds": rounds hg_cluster_greedy* queue per readback of the undecided count (0: its default)
   uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_pair_limit = 0;  // test hook "pair_limit": pairs one kernel launch of a comparison may enumerate (0: 2^32 - 1, the hit counter's reach)
   // pinned host scratch
@@ -177,6 +180,16 @@ hg_status hg_ensure_pinned(hg_ctx *ctx, size_t bytes);
 // the host polls that word (and the stream's own completion as a fallback) instead of paying a D2H copy command and a
 // stream synchronisation.  On return everything queued on the stream before the call has finished.  *out -> the n words.
 hg_status hg_publish_words(hg_ctx *ctx, uint32_t *d_words, uint32_t n, const uint32_t **out, uint32_t zero_n = 0);
+
+// ---- clustering: what hg_cluster.hip shares with hg_cluster_greedy.hip ----
+// The ctx's 16 clustering result words (w_clu_res): [0] cluster count, [1] error word (a hit with an index >= n); the
+// greedy resolution keeps [2], [3] = nodes still undecided after the odd / even rounds and [4] = rounds run behind them.
+// All are zero between calls: the call that reads them back clears them behind the copy (hg_publish_words).
+enum : uint32_t { HG_CLU_COUNT = 0, HG_CLU_ERR = 1, HG_CLU_UNDECIDED = 2, HG_CLU_ROUNDS = 4, HG_CLU_WORDS = 5 };
+hg_status hg_cluster_res(hg_ctx *ctx, uint32_t **out);
+// rep[] (trees of any depth) -> rep[i] = root, d_cluster = dense ids of the roots in index order, res[HG_CLU_COUNT] = their
+// number: the compress / scan / root-id / member-id launches of hg_cluster_finish_dev, stream-ordered, nothing read back.
+hg_status hg_cluster_queue_ids(hg_ctx *ctx, uint32_t *d_rep, size_t n, uint32_t *d_cluster, uint32_t *res);
 
 // RAII bracket: records events around the launches issued while it is alive (no-op unless
 // timing is enabled).

@@ -84,6 +84,8 @@ int hg_device_count(void);
  *                                      split into blocks of reference rows; 0 = 2^32 - 1, the reach of the hit counter)
  *       "cluster_hit_cap" = "<n>"     (hits the scratch list of hg_cluster_dev starts with -- small forces its grow path;
  *                                      0 = the ctx's own size)
+ *       "greedy_rounds" = "<n>"       (rounds hg_cluster_greedy* queue before they read the count of undecided nodes back;
+ *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  * Nothing in the library reads environment variables. */
@@ -280,8 +282,8 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * dot <= 0 gives 0, a zero denominator 0 (dot = 0) or 100 (dot > 0), dot > denominator 100.
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
- * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev} and
- * hg_ani_from_dots_dev.  symmetric != 0 under
+ * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
+ * hg_cluster_greedy{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev}
  * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev (it takes hits), hg_dist_prep_ops_dev, the
  * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
@@ -447,6 +449,47 @@ hg_status hg_cluster_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm
                          float ani_th, uint32_t *d_rep, uint32_t *d_cluster, size_t *n_clusters);
 hg_status hg_cluster(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
                      float ani_th, uint32_t *rep, uint32_t *cluster, size_t *n_clusters);
+
+/* Greedy representative clustering (no reference counterpart; what dereplication tools do -- CD-HIT's incremental scheme):
+ * one representative per cluster and every other sketch within the threshold of ITS representative, neither of which
+ * single linkage gives (a chain 0 - 1 - 2 with ani(0, 2) < ani_th is one component there).  Input: n sketches in
+ * processing order 0 .. n - 1 and a symmetric ANI (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT; HG_ANI_CONTAINMENT is
+ * HG_ERR_INVALID as for hg_cluster_dev); the side of the threshold is the float comparison ani >= ani_th of hg_dist_dev.
+ * Going through i = 0, 1, ...:
+ *   i is a REPRESENTATIVE iff no representative j < i has ani(j, i) >= ani_th;
+ *   otherwise i is a MEMBER of the representative j < i with the highest ani(j, i) (float comparison, ties to the smallest
+ *   j).  Only earlier representatives count: a later one that is within the threshold of i does not take it over.
+ *   A member covers nobody: if 1 is a member of 0 and 2 is within the threshold of 1 only, 2 is a representative.
+ * So representatives are pairwise below the threshold and every member is at or above it with its own representative.
+ *   rep[i]      = i for a representative, its representative for a member;
+ *   cluster[i]  = the dense id of rep[i]: 0, 1, ... in increasing order of the representatives' indices;
+ *   *n_clusters = the number of representatives;
+ *   ani[i]      = 100.0f for a representative, the ANI of the pair (rep[i], i) for a member (optional: may be NULL).
+ * The result depends on the graph and its ANI values alone -- not on block size, hit order, scheduling or the number of
+ * rounds.  n < 2^31; n == 0: HG_OK, *n_clusters = 0; NULL rep / cluster / n_clusters: HG_ERR_INVALID; results are final on
+ * return, as for hg_cluster_dev.
+ * On the device the walk is resolved in rounds (hg_cluster_greedy.hip): greedy_mark_kernel, one lane per hit -- a
+ * representative makes its later neighbours members, two undecided ends block the later one for the round -- then
+ * greedy_decide_kernel, one lane per node -- undecided and not blocked: representative; the smallest undecided node is
+ * decided in every round.  The host queues "greedy_rounds" rounds (hg_ctx_set_debug; default 4) per readback of the
+ * undecided count and stops at 0.  Dense groups resolve in about two rounds; the worst case, a path 0 - 1 - 2 - ...,
+ * takes about n / 2 rounds (accepted).  greedy_assign_kernel then gives every covered node its best representative (a 64-bit
+ * atomic max), and the dense ids come from hg_cluster_finish_dev's kernels.
+ *   hg_cluster_greedy_dev : resident sketches; the symmetric comparison in the row blocks of hg_cluster_dev (scratch list,
+ *                           "pair_limit", "cluster_hit_cap" and its grow path as there), each block resolved before the next.
+ *   hg_cluster_greedy     : host arrays in and out, staged through the ctx. */
+/* complete hit list of the caller (e.g. hg_dist_dev at a low threshold, resolved at several higher ones): either orientation,
+ * duplicates and self-pairs allowed (self-pairs ignored, a pair given twice counts with each ANI; the highest wins);
+ * hits below ani_th ignored; an index >= n (at any ANI): HG_ERR_INVALID, nothing reported, the next call starts clean */
+hg_status hg_cluster_greedy_hits_dev(hg_ctx *ctx, size_t n, const hg_ani_hit *d_hits, size_t n_hits, float ani_th,
+                                     uint32_t *d_rep, uint32_t *d_cluster, float *d_ani, size_t *n_clusters);
+hg_status hg_cluster_greedy_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d,
+                                uint32_t ksize, float ani_th, uint32_t *d_rep, uint32_t *d_cluster, float *d_ani,
+                                size_t *n_clusters);
+hg_status hg_cluster_greedy(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                            float ani_th, uint32_t *rep, uint32_t *cluster, float *ani, size_t *n_clusters);
+/* rounds of the last greedy call on this ctx, summed over its blocks (diagnostic; 0 = none yet) */
+uint64_t hg_ctx_cluster_greedy_rounds(const hg_ctx *ctx);
 
 /* ---- sketch compression (host side; src/hd.rs:114-232) -------------------------------- */
 uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d);
