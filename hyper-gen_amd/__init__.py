@@ -88,6 +88,7 @@ EXPORTS = [
     "hg_sketch_file_read_image", "hg_sketch_file_image", "hg_sketch_file_payload_offset",
     "hg_cluster_init_dev", "hg_cluster_add_hits_dev", "hg_cluster_finish_dev", "hg_cluster_dev", "hg_cluster",
     "hg_cluster_greedy_hits_dev", "hg_cluster_greedy_dev", "hg_cluster_greedy", "hg_ctx_cluster_greedy_rounds",
+    "hg_cluster_tree_hits_dev", "hg_cluster_tree_dev", "hg_cluster_tree", "hg_ctx_cluster_tree_rounds",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
 ]
@@ -274,6 +275,10 @@ def lib():
         "hg_cluster_greedy_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
         "hg_cluster_greedy": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
         "hg_ctx_cluster_greedy_rounds": (C.c_uint64, [vp]),
+        "hg_cluster_tree_hits_dev": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
+        "hg_cluster_tree_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
+        "hg_cluster_tree": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
+        "hg_ctx_cluster_tree_rounds": (C.c_uint64, [vp]),
         "hg_search_topk_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
         "hg_search_topk_block_dev": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
                                                vp, vp]),
@@ -685,6 +690,47 @@ class Context:
     def cluster_greedy_rounds(self):
         """rounds of the last greedy call on this ctx, summed over its blocks (hg_ctx_cluster_greedy_rounds)"""
         return int(lib().hg_ctx_cluster_greedy_rounds(self._h))
+
+    # ---- single-linkage tree (hg_cluster_tree*) ---------------------------------------------------
+    def cluster_tree(self, hv, n2, ksize=21, ani_th=95.0, want_clusters=True):
+        """hg_cluster_tree on host sketches: numpy (tree, rep, cluster, n_clusters) -- tree: the n - n_clusters edges
+        {ref_idx = lo, qry_idx = hi, ani} of the maximum-ANI spanning forest at the floor ani_th, strongest first
+        (ANI_HIT_DTYPE); rep / cluster as cluster() gives them at ani_th (None without want_clusters)"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        tree = np.zeros(max(n, 1) - 1, ANI_HIT_DTYPE)
+        rep = np.zeros(n, np.uint32) if want_clusters else None
+        cl = np.zeros(n, np.uint32) if want_clusters else None
+        ne, nc = C.c_size_t(0), C.c_size_t(0)
+        keep = np.zeros(1, ANI_HIT_DTYPE)  # (a pointer that is not NULL for the empty tree of n <= 1)
+        self._ck(lib().hg_cluster_tree(self._h, _ptr(h) if h.size else None, _ptr(nn) if nn.size else None, n,
+                                       h.shape[1] if h.ndim == 2 else 0, ksize, C.c_float(ani_th),
+                                       _ptr(tree if tree.size else keep), tree.size, C.byref(ne),
+                                       _ptr(rep) if want_clusters and n else None, _ptr(cl) if want_clusters and n else None,
+                                       C.byref(nc)))
+        return tree[:ne.value], rep, cl, nc.value
+
+    def cluster_tree_dev(self, d_hv, d_n2, n, hv_d, d_tree, tree_cap, d_rep=None, d_cluster=None, ksize=21, ani_th=95.0):
+        """hg_cluster_tree_dev on resident sketches (device pointers; d_rep and d_cluster both given or both None); returns
+        (n_edges, n_clusters).  HgError(ERR_CAPACITY) when tree_cap < n - 1"""
+        ne, nc = C.c_size_t(0), C.c_size_t(0)
+        self._ck(lib().hg_cluster_tree_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, C.c_float(ani_th),
+                                           _ptr(d_tree or 0), tree_cap, C.byref(ne), _ptr(d_rep or 0), _ptr(d_cluster or 0),
+                                           C.byref(nc)))
+        return ne.value, nc.value
+
+    def cluster_tree_hits_dev(self, n, d_hits, n_hits, ani_th, d_tree, tree_cap, d_rep=None, d_cluster=None):
+        """hg_cluster_tree_hits_dev on a complete device-resident hit list; returns (n_edges, n_clusters); raises
+        HgError(ERR_INVALID) if a hit has an index >= n, HgError(ERR_CAPACITY) when tree_cap < n - 1"""
+        ne, nc = C.c_size_t(0), C.c_size_t(0)
+        self._ck(lib().hg_cluster_tree_hits_dev(self._h, n, _ptr(d_hits or 0), n_hits, C.c_float(ani_th), _ptr(d_tree or 0),
+                                                tree_cap, C.byref(ne), _ptr(d_rep or 0), _ptr(d_cluster or 0), C.byref(nc)))
+        return ne.value, nc.value
+
+    def cluster_tree_rounds(self):
+        """rounds of the last tree call on this ctx, summed over its blocks (hg_ctx_cluster_tree_rounds)"""
+        return int(lib().hg_ctx_cluster_tree_rounds(self._h))
 
 
 def shard_range(n, shard, n_shards):

@@ -83,6 +83,9 @@ struct Cli {
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
   bool greedy = false, linkage_given = false;     // --linkage single|greedy (cluster)
   bool order_size = false, order_given = false;   // --order file|size (cluster --linkage greedy)
+  std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
+  std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
+  bool tree_given = false, levels_given = false;
 };
 
 Cli parse(int argc, char **argv) {
@@ -98,7 +101,8 @@ Cli parse(int argc, char **argv) {
                 "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
                 "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
                 "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
-                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy]\n\n"
+                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy]\n"
+                "                    [--tree {output_tree}] [--levels L1,L2,...]\n\n"
                 "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
                 "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
                 "         -Q --quant_scale [1.0], -a --ani_th [85.0], -D --device [cpu]\n"
@@ -122,7 +126,13 @@ Cli parse(int argc, char **argv) {
                 "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative),\n"
                 "         --order file|size [file] (cluster --linkage greedy: the order the sketches are processed in; size =\n"
                 "         descending hv_norm_2, ties in file order -- the most complete genome of a group represents it;\n"
-                "         cluster ids count the representatives in that order, the lines stay in file order)\n");
+                "         cluster ids count the representatives in that order, the lines stay in file order),\n"
+                "         --tree <file> (cluster --linkage single: the single-linkage tree at the floor -a -- the maximum-ANI\n"
+                "         spanning forest, genomes - clusters lines, strongest first: file, file, ANI as dist prints it; cut\n"
+                "         at any threshold >= -a it gives that threshold's clusters, its order is the merge order),\n"
+                "         --levels L1,L2,... (cluster --linkage single: 1 to 8 further thresholds, ascending, above -a, all from\n"
+                "         one comparison at -a; every line of -o becomes file, then for -a and each level the cluster id and\n"
+                "         the file of the cluster's first member)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -131,7 +141,8 @@ Cli parse(int argc, char **argv) {
       {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
       {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
-      {"min_count", '\x02'}, {"search_path", '\x03'}, {"linkage", '\x04'}, {"order", '\x05'}};
+      {"min_count", '\x02'}, {"search_path", '\x03'}, {"linkage", '\x04'}, {"order", '\x05'}, {"tree", '\x06'},
+      {"levels", '\x07'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -209,6 +220,26 @@ Cli parse(int argc, char **argv) {
         else die("invalid value '" + val + "' for '--order' (file | size)");
         c.order_given = true;
         break;
+      case '\x06':  // (long form only) cluster --linkage single only (extension)
+        if (val.empty()) die("invalid value '' for '--tree' (a file name)");
+        c.tree_out = val, c.tree_given = true;
+        break;
+      case '\x07': {  // (long form only) cluster --linkage single only (extension)
+        c.levels.clear(), c.levels_given = true;
+        for (size_t b = 0; b <= val.size();) {
+          const size_t e = std::min(val.find(',', b), val.size());
+          const std::string item = val.substr(b, e - b);
+          char *end = nullptr;
+          const float v = std::strtof(item.c_str(), &end);
+          if (item.empty() || *end || !(v == v) || item.find_first_not_of("0123456789.+-eE") != std::string::npos)
+            die("invalid value '" + val + "' for '--levels' (1 to 8 ANI thresholds, comma-separated, ascending)");
+          if (c.levels.size() == 8) die("invalid value '" + val + "' for '--levels': at most 8 levels");
+          if (!c.levels.empty() && !(v > c.levels.back())) die("invalid value '" + val + "' for '--levels': the levels must be strictly ascending");
+          c.levels.push_back(v);
+          b = e + 1;
+        }
+        break;
+      }
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -223,6 +254,15 @@ Cli parse(int argc, char **argv) {
   if (c.linkage_given && c.mode != "cluster") die("--linkage is not supported by " + c.mode + ": it chooses how cluster forms its clusters");
   if (c.order_given && !(c.mode == "cluster" && c.greedy))
     die("--order needs cluster --linkage greedy: single-linkage components do not depend on the order of the sketches");
+  for (int k = 0; k < 2; ++k) {
+    if (!(k ? c.levels_given : c.tree_given)) continue;
+    const std::string f = k ? "--levels" : "--tree";
+    if (c.mode != "cluster") die(f + " is not supported by " + c.mode + ": it belongs to cluster --linkage single");
+    if (c.greedy) die(f + " needs cluster --linkage single: greedy clusters are not nested and have no tree");
+    if (c.shards) die(f + " is not supported with --shards: cluster runs on the first visible GPU");
+  }
+  if (c.levels_given && !(c.levels[0] > (c.ani_th_given ? c.ani_th : 95.0f)))
+    die("invalid value for '--levels': every level must be above -a, the threshold the tree is built at");
   if (c.min_count_given && c.mode != "sketch") die("--min_count is not supported by " + c.mode + ": the filter needs the k-mer counts, which a sketch no longer has");
   return c;
 }
@@ -914,6 +954,13 @@ int run_cluster(const Cli &c) {
   size_t n_cl = 0;
   std::vector<uint32_t> rep(L.n), cl(L.n);
   std::vector<float> ani;
+  struct Level {  // --levels: one further threshold, cut from the tree
+    float th;
+    size_t n_cl = 0;
+    std::vector<uint32_t> rep, cl;
+  };
+  std::vector<Level> more;
+  std::vector<hg_ani_hit> tree;  // --tree / --levels
   if (c.greedy) {
     void *d_ani = nullptr;
     ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(float), &d_ani), "alloc");
@@ -923,6 +970,31 @@ int run_cluster(const Cli &c) {
     ck(ctx, hg_copy_d2h(ctx, ani.data(), d_ani, L.n * sizeof(float)), "download");
     (void)hg_dev_free(ctx, d_ani);
     debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
+  } else if (c.tree_given || c.levels_given) {
+    // one comparison at the floor -a (hg_cluster_tree_dev); every level is a cut of the tree (the step calls of hg_cluster)
+    void *d_tree = nullptr;
+    size_t n_edges = 0;
+    ck(ctx, hg_dev_alloc(ctx, std::max<size_t>(L.n, 2) * sizeof(hg_ani_hit), &d_tree), "alloc");
+    ck(ctx, hg_cluster_tree_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<hg_ani_hit *>(d_tree),
+                                L.n ? L.n - 1 : 0, &n_edges, static_cast<uint32_t *>(d_rep), static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
+    debugf("tree of %zu edges in %llu rounds", n_edges, (unsigned long long)hg_ctx_cluster_tree_rounds(ctx));
+    tree.resize(n_edges);
+    if (n_edges) ck(ctx, hg_copy_d2h(ctx, tree.data(), d_tree, n_edges * sizeof(hg_ani_hit)), "download");
+    void *d_rep2 = nullptr, *d_cl2 = nullptr;
+    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_rep2), "alloc");
+    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_cl2), "alloc");
+    for (const float t : c.levels) {
+      Level v;
+      v.th = t, v.rep.resize(L.n), v.cl.resize(L.n);
+      auto *r2 = static_cast<uint32_t *>(d_rep2);
+      ck(ctx, hg_cluster_init_dev(ctx, r2, L.n), "cluster");
+      ck(ctx, hg_cluster_add_hits_dev(ctx, r2, L.n, static_cast<const hg_ani_hit *>(d_tree), n_edges, t), "cluster");
+      ck(ctx, hg_cluster_finish_dev(ctx, r2, L.n, static_cast<uint32_t *>(d_cl2), &v.n_cl), "cluster");
+      ck(ctx, hg_copy_d2h(ctx, v.rep.data(), d_rep2, L.n * sizeof(uint32_t)), "download");
+      ck(ctx, hg_copy_d2h(ctx, v.cl.data(), d_cl2, L.n * sizeof(uint32_t)), "download");
+      more.push_back(std::move(v));
+    }
+    (void)hg_dev_free(ctx, d_tree), (void)hg_dev_free(ctx, d_rep2), (void)hg_dev_free(ctx, d_cl2);
   } else {
     ck(ctx, hg_cluster_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
                            static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
@@ -939,6 +1011,9 @@ int run_cluster(const Cli &c) {
   }
   size_t singletons = 0;
   for (uint32_t s : size) singletons += s == 1;
+  for (const Level &v : more)
+    for (size_t i = 0; i < L.n; ++i)
+      if (v.cl[i] >= v.n_cl || v.rep[i] > i) die("inconsistent cluster result");
   std::string o;
   if (c.greedy) {
     std::vector<uint32_t> pos(L.n);  // record -> processing position
@@ -960,14 +1035,45 @@ int run_cluster(const Cli &c) {
       o += std::to_string(cl[i]);
       o += '\t';
       o += hg_sketch_file_get(L.f, rep[i])->file_str;
+      for (const Level &v : more) {  // (--levels: the same two columns per level)
+        o += '\t';
+        o += std::to_string(v.cl[i]);
+        o += '\t';
+        o += hg_sketch_file_get(L.f, v.rep[i])->file_str;
+      }
       o += '\n';
     }
   }
   FILE *f = std::fopen(c.out.c_str(), "wb");
   if (!f || std::fwrite(o.data(), 1, o.size(), f) != o.size() || std::fclose(f) != 0) die("Dump cluster file failed!");
+  if (c.tree_given) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
+    std::string t;
+    char num[16];
+    for (const hg_ani_hit &e : tree) {
+      if (e.ref_idx >= L.n || e.qry_idx >= L.n) die("inconsistent cluster result");
+      t += hg_sketch_file_get(L.f, e.ref_idx)->file_str;
+      t += '\t';
+      t += hg_sketch_file_get(L.f, e.qry_idx)->file_str;
+      t.append(num, put_ani(num, e.ani));  // "\t<ani>\n"
+    }
+    FILE *ft = std::fopen(c.tree_out.c_str(), "wb");
+    if (!ft || std::fwrite(t.data(), 1, t.size(), ft) != t.size() || std::fclose(ft) != 0) die("Dump tree file failed!");
+  }
   std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %.1f to file %s", L.n, n_cl,
                 singletons, th, c.out.c_str());
   logline("INFO", buf);
+  for (const Level &v : more) {
+    std::vector<uint32_t> sz(v.n_cl, 0);
+    for (size_t i = 0; i < L.n; ++i) ++sz[v.cl[i]];
+    size_t single = 0;
+    for (uint32_t s : sz) single += s == 1;
+    char lv[32];  // (one decimal like -a's line where that is the level, else as many digits as it needs)
+    std::snprintf(lv, sizeof lv, "%.1f", (double)v.th);
+    if (std::strtof(lv, nullptr) != v.th) std::snprintf(lv, sizeof lv, "%g", (double)v.th);
+    std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %s to file %s", L.n, v.n_cl,
+                  single, lv, c.out.c_str());
+    logline("INFO", buf);
+  }
   std::snprintf(buf, sizeof buf, "Clustered %zu files took %.3fs", L.n,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   logline("INFO", buf);

@@ -2,7 +2,8 @@
 // its users cluster the TSV of `dist` in another tool).  Two genomes share a cluster when a chain of pairs with ani >= ani_th
 // joins them; rep[i] = the smallest index of i's connected component, cluster[i] = the component's dense id in increasing
 // order of rep.
-//   * hook    : one lane per hit, lock-free union-find over rep[n] (ECL-CC, Jaykrishnan & Burtscher 2018): find both roots
+//   * hook    : one lane per hit, lock-free union-find over rep[n] (ECL-CC, Jaykrishnan & Burtscher 2018; the routines
+//               are in hg_cluster_common.h, which hg_cluster_greedy.hip and hg_cluster_tree.hip share): find both roots
 //               with path halving, hook the larger root under the smaller one with a CAS, on failure go on from what the CAS
 //               returned.  Roots only ever move to smaller indices, so the root of a component is its minimum index.
 //   * finish  : compress (rep[i] = root(i)) + roots per tile -> scan of the tile counts (cluster count) -> dense ids of the
@@ -10,42 +11,12 @@
 #include <algorithm>
 
 #include "hg_block_scan.h"
+#include "hg_cluster_common.h"
 #include "hg_internal.h"
 
 namespace {
 constexpr uint32_t CL_ITEMS = 4, CL_TILE = 256 * CL_ITEMS;  // nodes per workgroup of the finishing kernels
 constexpr size_t CL_DEFAULT_HITS = (size_t)1 << 22;         // first size of hg_cluster_dev's scratch hit list (48 MB)
-
-// Inside the hook kernel other workgroups -- on other CUs, other XCDs -- move rep[] under our feet: a CU's L1 is never
-// refreshed by another CU's stores and the XCDs' L2s are not coherent with each other, so a plain load could return a
-// value that is stale for as long as the line stays cached, and a CAS loop fed by it would spin.  Every access of rep[] in
-// that kernel is therefore an agent-scope atomic (relaxed: each value read is used only for itself -- correctness needs
-// no ordering between locations, see find_root and cluster_hook_kernel).
-__device__ __forceinline__ uint32_t rep_load(uint32_t *rep, uint32_t x) {
-  return __hip_atomic_load(rep + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void rep_store(uint32_t *rep, uint32_t x, uint32_t v) {
-  __hip_atomic_store(rep + x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Invariants of rep[] (they hold for every value any lane can read, stale or fresh):
-//   (1) rep[x] <= x, and rep[x] < x once x is not a root: only a CAS on a root writes a smaller index into it, path
-//       halving writes into non-roots only, and always an ancestor, which is smaller;
-//   (2) a non-root never becomes a root again (nothing writes x into rep[x] after init);
-//   (3) an ancestor stays an ancestor: trees only merge.
-// find_root terminates because x strictly decreases in every step (1).  A root it returns may be stale -- hooked meanwhile
-// -- but is an ancestor of the argument (3); the CAS below finds out.
-__device__ __forceinline__ uint32_t find_root(uint32_t *rep, uint32_t x) {
-  uint32_t p = rep_load(rep, x);
-  while (p != x) {
-    const uint32_t g = rep_load(rep, p);
-    if (g == p) return p;
-    rep_store(rep, x, g);  // path halving: x skips its parent (x is a non-root, g an ancestor of it)
-    x = g;
-    p = rep_load(rep, x);
-  }
-  return x;
-}
 
 __global__ __launch_bounds__(256) void cluster_init_kernel(uint32_t *__restrict__ rep, uint32_t n, uint32_t *__restrict__ res) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -53,10 +24,7 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(uint32_t *__restrict_
   if (blockIdx.x == 0 && threadIdx.x < 2) res[threadIdx.x] = 0u;  // cluster count, error word
 }
 
-// One lane per hit, grid-stride.  Why the union loop terminates: each round either hooks (CAS succeeds: done) or the CAS
-// fails, which means `hi` is no longer a root -- another lane hooked it under a smaller index, which the CAS returns (1).
-// The loop then goes on with the root of that index, which is < hi, in place of hi: a + b strictly decreases every round
-// and is bounded below.  When a == b both ends share an ancestor, and by (3) they stay in one tree.
+// One lane per hit, grid-stride (find_root, hook_roots and why they terminate: hg_cluster_common.h).
 __global__ __launch_bounds__(256) void cluster_hook_kernel(uint32_t *rep, uint32_t n, const hg_ani_hit *__restrict__ hits,
                                                            size_t n_hits, float ani_th, uint32_t *err) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -67,14 +35,7 @@ __global__ __launch_bounds__(256) void cluster_hook_kernel(uint32_t *rep, uint32
       continue;
     }
     if (!(e.ani >= ani_th) || e.ref_idx == e.qry_idx) continue;  // (the side of the threshold exactly as in dist)
-    uint32_t a = find_root(rep, e.ref_idx), b = find_root(rep, e.qry_idx);
-    while (a != b) {
-      const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-      uint32_t seen = hi;
-      if (__hip_atomic_compare_exchange_strong(rep + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        break;
-      a = lo, b = find_root(rep, seen);  // hi was hooked under seen < hi
-    }
+    hook_roots(rep, e.ref_idx, e.qry_idx);
   }
 }
 
@@ -140,11 +101,6 @@ __global__ __launch_bounds__(256) void cluster_member_ids_kernel(const uint32_t 
     const uint32_t r = rep[i];
     if (r != (uint32_t)i) cluster[i] = cluster[r];
   }
-}
-
-inline unsigned grid_for(hg_ctx *c, size_t items) {
-  const size_t want = (items + 255) / 256, most = (size_t)c->n_cu * 16;
-  return (unsigned)std::max<size_t>(1, std::min(want, most));
 }
 
 hg_status check_n(hg_ctx *c, size_t n, const uint32_t *d_rep) {

@@ -45,19 +45,13 @@
 #include <cstring>
 
 #include "hg_block_scan.h"
+#include "hg_cluster_common.h"
 #include "hg_internal.h"
 
 namespace {
 constexpr uint32_t ST_UNDECIDED = 0, ST_REP = 1, ST_MEMBER = 2;
 constexpr uint64_t GR_DEFAULT_ROUNDS = 4;           // rounds queued per readback of the undecided count
 constexpr size_t GR_DEFAULT_HITS = (size_t)1 << 22;  // first size of the scratch hit list (as hg_cluster_dev)
-
-// Any float -> a 32-bit key of the same order (negative values and both zeros included; -0.0f + 0.0f = +0.0f), and back.
-__device__ __forceinline__ uint32_t ani_key(float a) {
-  const uint32_t b = __float_as_uint(a + 0.0f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float key_ani(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 __device__ __forceinline__ uint32_t st_load(const uint32_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -161,11 +155,6 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const uint64_t *__re
     rep[i] = is_rep ? (uint32_t)i : 0xFFFFFFFFu - (uint32_t)b;
     if (ani) ani[i] = is_rep ? 100.0f : key_ani((uint32_t)(b >> 32));
   }
-}
-
-inline unsigned grid_for(hg_ctx *c, size_t items) {
-  const size_t want = (items + 255) / 256, most = (size_t)c->n_cu * 16;
-  return (unsigned)std::max<size_t>(1, std::min(want, most));
 }
 
 hg_status greedy_begin(hg_ctx *c, size_t n, Greedy *g) {

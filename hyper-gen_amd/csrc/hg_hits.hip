@@ -12,12 +12,14 @@
 #include <cstring>
 
 #include "hg_block_scan.h"
+#include "hg_cluster_common.h"
 #include "hg_internal.h"
 
 namespace {
 
 // key extraction for one LSD pass: 0 = enumeration key ref*Q+qry (u64), 1 = ANI bits (u32; ANI >= 0 so the
-// IEEE bit pattern is monotone), 2 = ref index, 3 = query index
+// IEEE bit pattern is monotone), 2 = ref index, 3 = query index, 4 = ANI by its order-preserving key (any sign: the
+// tree order of hg_cluster_tree.hip)
 template <int WHAT>
 __global__ __launch_bounds__(256) void gather_keys_kernel(const hg_ani_hit *__restrict__ hits, const uint32_t *__restrict__ perm,
                                                           uint32_t n, uint64_t Q, uint64_t *__restrict__ k64,
@@ -30,7 +32,8 @@ __global__ __launch_bounds__(256) void gather_keys_kernel(const hg_ani_hit *__re
   if (WHAT == 0) k64[i] = (uint64_t)h.ref_idx * Q + h.qry_idx;
   else if (WHAT == 1) k32[i] = __float_as_uint(h.ani);
   else if (WHAT == 2) k32[i] = h.ref_idx;
-  else k32[i] = h.qry_idx;
+  else if (WHAT == 3) k32[i] = h.qry_idx;
+  else k32[i] = ani_key(h.ani);
 }
 
 __global__ __launch_bounds__(256) void permute_hits_kernel(const hg_ani_hit *__restrict__ in, const uint32_t *__restrict__ perm,
@@ -318,6 +321,42 @@ extern "C" hg_status hg_topk_per_query_dev(hg_ctx *c, const hg_ani_hit *d_hits, 
   hipLaunchKernelGGL(permute_hits_kernel, dim3(grid), dim3(256), 0, c->stream, d_hits, perm, m, w.tmp_hits);
   HG_HIP(c, hipGetLastError());
   hipLaunchKernelGGL(topk_kernel, dim3(grid), dim3(256), 0, c->stream, w.tmp_hits, m, (uint32_t)Q, k, d_out, d_counts);
+  HG_HIP(c, hipGetLastError());
+  return HG_OK;
+}
+
+// hg_cluster_tree.hip's edge order: strongest first = ANI descending, ties by ref_idx (lo) ascending, then qry_idx (hi)
+// ascending.  LSD, every pass stable: hi ascending, lo ascending, ANI key descending; the edges move once, into d_out.
+hg_status hg_sort_tree_edges_dev(hg_ctx *c, const hg_ani_hit *d_in, size_t n, size_t n_nodes, hg_ani_hit *d_out) {
+  if (n == 0) return HG_OK;
+  if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "hit list too long for the device sort");
+  const uint32_t m = (uint32_t)n, grid = (m + 255) / 256;
+  if (m == 1) {
+    HG_HIP(c, hipMemcpyAsync(d_out, d_in, sizeof(hg_ani_hit), hipMemcpyDeviceToDevice, c->stream));
+    return HG_OK;
+  }
+  SortWs w;
+  hg_status s = sort_workspace(c, m, w);
+  if (s != HG_OK) return s;
+  auto *cnt = static_cast<uint32_t *>(w.tmp);
+  const uint32_t idx_bits = bits_for(n_nodes ? n_nodes - 1 : 0);  // (every index is < n_nodes: only the digits it can have)
+  bool f = false;
+  hipLaunchKernelGGL(gather_keys_kernel<3>, dim3(grid), dim3(256), 0, c->stream, d_in, (const uint32_t *)nullptr, m, (uint64_t)0,
+                     (uint64_t *)nullptr, w.k32a, w.va);
+  HG_HIP(c, hipGetLastError());
+  HG_HIP(c, (radix_sort_pairs<uint32_t, false>(c->stream, cnt, w.k32a, w.k32b, w.va, w.vb, m, 0, idx_bits, &f)));
+  uint32_t *perm = f ? w.vb : w.va, *other = f ? w.va : w.vb;
+  hipLaunchKernelGGL(gather_keys_kernel<2>, dim3(grid), dim3(256), 0, c->stream, d_in, perm, m, (uint64_t)0, (uint64_t *)nullptr,
+                     w.k32a, (uint32_t *)nullptr);
+  HG_HIP(c, hipGetLastError());
+  HG_HIP(c, (radix_sort_pairs<uint32_t, false>(c->stream, cnt, w.k32a, w.k32b, perm, other, m, 0, idx_bits, &f)));
+  if (f) std::swap(perm, other);
+  hipLaunchKernelGGL(gather_keys_kernel<4>, dim3(grid), dim3(256), 0, c->stream, d_in, perm, m, (uint64_t)0, (uint64_t *)nullptr,
+                     w.k32a, (uint32_t *)nullptr);
+  HG_HIP(c, hipGetLastError());
+  HG_HIP(c, (radix_sort_pairs<uint32_t, true>(c->stream, cnt, w.k32a, w.k32b, perm, other, m, 0, 32, &f)));
+  if (f) std::swap(perm, other);
+  hipLaunchKernelGGL(permute_hits_kernel, dim3(grid), dim3(256), 0, c->stream, d_in, perm, m, d_out);
   HG_HIP(c, hipGetLastError());
   return HG_OK;
 }

@@ -86,6 +86,8 @@ int hg_device_count(void);
  *                                      0 = the ctx's own size)
  *       "greedy_rounds" = "<n>"       (rounds hg_cluster_greedy* queue before they read the count of undecided nodes back;
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
+ *       "tree_rounds" = "<n>"         (rounds hg_cluster_tree* queue before they read the count of selecting roots back;
+ *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  * Nothing in the library reads environment variables. */
@@ -283,9 +285,10 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
  * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
- * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev}
- * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev (it takes hits), hg_dist_prep_ops_dev, the
+ * hg_cluster_greedy{,_dev}, hg_cluster_tree{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev},
+ * hg_cluster_greedy{,_dev} and hg_cluster_tree{,_dev} accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.
+ * hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev and hg_cluster_tree_hits_dev (they take hits), hg_dist_prep_ops_dev, the
  * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
@@ -490,6 +493,48 @@ hg_status hg_cluster_greedy(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2
                             float ani_th, uint32_t *rep, uint32_t *cluster, float *ani, size_t *n_clusters);
 /* rounds of the last greedy call on this ctx, summed over its blocks (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_greedy_rounds(const hg_ctx *ctx);
+
+/* The single-linkage tree (no reference counterpart): every threshold of single linkage from ONE comparison.  The
+ * maximum-ANI spanning forest of the hit graph at a floor ani_th has at most n - 1 edges -- 12 (n - 1) bytes however many
+ * pairs lie above the floor, where the hit list itself can pass 2^32 entries -- and is an exact summary of it:
+ *   - cut at any t >= ani_th it gives exactly the components of the full graph at t.  Cutting needs no new call:
+ *     hg_cluster_init_dev + hg_cluster_add_hits_dev(d_tree, n_edges, t) + hg_cluster_finish_dev, once per level;
+ *   - its edges, strongest first, are the merge order of single-linkage clustering (the dendrogram).
+ * Which hits count: ani >= ani_th (the float comparison of hg_dist_dev: NaN never counts) and ref_idx != qry_idx.  A hit is
+ * the edge {lo, hi} = {min, max} of its indices: either orientation, duplicates allowed (a pair given with several ANIs has
+ * several edges, the strongest decides).  Edge e is STRONGER than f iff ani(e) > ani(f) as floats (-0 = +0), or the ANIs
+ * are equal and lo(e) < lo(f), or those are equal too and hi(e) < hi(f); edges equal in all three are the same edge.
+ * The tree is what Kruskal builds: the edges strongest first, an edge kept iff it joins two different components.
+ *   d_tree      : *n_edges = n - *n_clusters records {ref_idx = lo, qry_idx = hi, ani}, strongest first;
+ *   rep, cluster: what hg_cluster_dev gives at ani_th (optional: both NULL for the tree alone); *n_clusters is always set.
+ * The result depends on the edge set and its ANI values alone -- not on hit order, block size, rounds per readback or
+ * scheduling.  tree_cap < n - 1: HG_ERR_CAPACITY with *n_edges = n - 1, nothing launched.  n == 0: HG_OK, zero counts;
+ * n >= 2^31: HG_ERR_UNSUPPORTED; NULL d_tree / n_edges / n_clusters, or one of rep / cluster without the other:
+ * HG_ERR_INVALID.  Results are final on return, as for hg_cluster_dev.
+ * On the device (hg_cluster_tree.hip) the tree is resolved as Boruvka rounds over a candidate list: tree_best_ani_kernel and
+ * tree_best_pair_kernel, one lane per candidate -- the strongest edge leaving each component, by an atomic max of the ANI
+ * key and an atomic min of lo << 32 | hi among its ties; tree_select_kernel, one lane per node -- a root emits its edge
+ * (once when both ends chose it); tree_hook_kernel and tree_compress_kernel unite the components.  Every live component
+ * merges in every round: at most ceil(log2 n) + 1 rounds per block.  The host queues "tree_rounds" rounds (hg_ctx_set_debug;
+ * default 4) per readback of the count of selecting roots and stops at 0.
+ *   hg_cluster_tree_hits_dev : a complete hit list of the caller; an index >= n (at any ANI): HG_ERR_INVALID, nothing
+ *                              reported, the next call starts clean.
+ *   hg_cluster_tree_dev      : resident sketches (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT); the symmetric comparison in the row
+ *                              blocks of hg_cluster_dev (scratch list, "pair_limit", "cluster_hit_cap" and its grow path as
+ *                              there).  A block's candidates are the forest of the blocks before it and its own hits -- at most
+ *                              n - 1 edges + one block's hits are ever held.
+ *   hg_cluster_tree          : host arrays in and out, staged through the ctx. */
+hg_status hg_cluster_tree_hits_dev(hg_ctx *ctx, size_t n, const hg_ani_hit *d_hits, size_t n_hits, float ani_th,
+                                   hg_ani_hit *d_tree, size_t tree_cap, size_t *n_edges, uint32_t *d_rep, uint32_t *d_cluster,
+                                   size_t *n_clusters);
+hg_status hg_cluster_tree_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                              float ani_th, hg_ani_hit *d_tree, size_t tree_cap, size_t *n_edges, uint32_t *d_rep,
+                              uint32_t *d_cluster, size_t *n_clusters);
+hg_status hg_cluster_tree(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                          float ani_th, hg_ani_hit *tree, size_t tree_cap, size_t *n_edges, uint32_t *rep, uint32_t *cluster,
+                          size_t *n_clusters);
+/* rounds of the last tree call on this ctx, summed over its blocks (diagnostic; 0 = none yet) */
+uint64_t hg_ctx_cluster_tree_rounds(const hg_ctx *ctx);
 
 /* ---- sketch compression (host side; src/hd.rs:114-232) -------------------------------- */
 uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d);
