@@ -88,6 +88,7 @@ EXPORTS = [
     "hg_sketch_file_read_image", "hg_sketch_file_image", "hg_sketch_file_payload_offset",
     "hg_cluster_init_dev", "hg_cluster_add_hits_dev", "hg_cluster_finish_dev", "hg_cluster_dev", "hg_cluster",
     "hg_cluster_greedy_hits_dev", "hg_cluster_greedy_dev", "hg_cluster_greedy", "hg_ctx_cluster_greedy_rounds",
+    "hg_cluster_setcover_hits_dev", "hg_cluster_setcover_dev", "hg_cluster_setcover", "hg_ctx_cluster_setcover_rounds",
     "hg_cluster_tree_hits_dev", "hg_cluster_tree_dev", "hg_cluster_tree", "hg_ctx_cluster_tree_rounds",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
@@ -275,6 +276,10 @@ def lib():
         "hg_cluster_greedy_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
         "hg_cluster_greedy": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
         "hg_ctx_cluster_greedy_rounds": (C.c_uint64, [vp]),
+        "hg_cluster_setcover_hits_dev": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, vp, vp, C.POINTER(sz)]),
+        "hg_cluster_setcover_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
+        "hg_cluster_setcover": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, C.POINTER(sz)]),
+        "hg_ctx_cluster_setcover_rounds": (C.c_uint64, [vp]),
         "hg_cluster_tree_hits_dev": (C.c_int, [vp, sz, vp, sz, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
         "hg_cluster_tree_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
         "hg_cluster_tree": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, sz, C.POINTER(sz), vp, vp, C.POINTER(sz)]),
@@ -690,6 +695,42 @@ class Context:
     def cluster_greedy_rounds(self):
         """rounds of the last greedy call on this ctx, summed over its blocks (hg_ctx_cluster_greedy_rounds)"""
         return int(lib().hg_ctx_cluster_greedy_rounds(self._h))
+
+    # ---- greedy set-cover clustering (hg_cluster_setcover*) ---------------------------------------
+    def cluster_setcover(self, hv, n2, ksize=21, ani_th=95.0):
+        """hg_cluster_setcover on host sketches: numpy (rep, cluster, ani, n_clusters) -- the undecided sketch with the most
+        undecided neighbours becomes a representative and takes them as its members, until none is left; rep[i] = i for a
+        representative, else its representative; cluster[i] = the dense id of rep[i]; ani[i] = 100 for a
+        representative, else the ANI of (rep[i], i)"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        rep = np.zeros(n, np.uint32)
+        cl = np.zeros(n, np.uint32)
+        ani = np.zeros(n, np.float32)
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_setcover(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th),
+                                           _ptr(rep), _ptr(cl), _ptr(ani), C.byref(nc)))
+        return rep, cl, ani, nc.value
+
+    def cluster_setcover_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani=None, ksize=21, ani_th=95.0):
+        """hg_cluster_setcover_dev on resident sketches (device pointers; d_ani may be None); returns the number of clusters"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_setcover_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep),
+                                               _ptr(d_cluster), _ptr(d_ani or 0), C.byref(nc)))
+        return nc.value
+
+    def cluster_setcover_hits_dev(self, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani=None):
+        """hg_cluster_setcover_hits_dev on a complete device-resident hit list (d_ani may be None); returns the number of
+        clusters; raises HgError(ERR_INVALID) if a hit has an index >= n"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_setcover_hits_dev(self._h, n, _ptr(d_hits or 0), n_hits, C.c_float(ani_th), _ptr(d_rep or 0),
+                                                    _ptr(d_cluster or 0), _ptr(d_ani or 0), C.byref(nc)))
+        return nc.value
+
+    def cluster_setcover_rounds(self):
+        """rounds of the last set-cover call on this ctx (hg_ctx_cluster_setcover_rounds)"""
+        return int(lib().hg_ctx_cluster_setcover_rounds(self._h))
 
     # ---- single-linkage tree (hg_cluster_tree*) ---------------------------------------------------
     def cluster_tree(self, hv, n2, ksize=21, ani_th=95.0, want_clusters=True):

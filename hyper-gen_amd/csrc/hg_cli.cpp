@@ -81,7 +81,8 @@ struct Cli {
   int search_path = 0;  // --search_path auto|hits|topk (search; testing aid): 0 = topk whenever top_n <= HG_SEARCH_TOPK_MAX, 1 = the hit list, 2 = topk
   bool search_path_given = false;
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
-  bool greedy = false, linkage_given = false;     // --linkage single|greedy (cluster)
+  bool greedy = false, linkage_given = false;     // --linkage single|greedy|setcover (cluster)
+  bool setcover = false;
   bool order_size = false, order_given = false;   // --order file|size (cluster --linkage greedy)
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
@@ -101,7 +102,7 @@ Cli parse(int argc, char **argv) {
                 "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
                 "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
                 "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
-                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy]\n"
+                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy|setcover]\n"
                 "                    [--tree {output_tree}] [--levels L1,L2,...]\n\n"
                 "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
                 "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
@@ -119,11 +120,15 @@ Cli parse(int argc, char **argv) {
                 "         once; 1 = every sampled k-mer, the reference's set), --search_path auto|hits|topk [auto] (search:\n"
                 "         topk selects the -n best per query on the device while blocks of the ANI matrix stream past -- memory\n"
                 "         does not grow with the number of pairs above -a; hits builds the thresholded hit list first; auto =\n"
-                "         topk for -n <= 64, hits beyond; both write the same file), --linkage single|greedy [single]\n"
+                "         topk for -n <= 64, hits beyond; both write the same file), --linkage single|greedy|setcover [single]\n"
                 "         (cluster: greedy = one representative per cluster, as dereplication tools choose them -- a sketch is\n"
                 "         a representative unless an earlier representative is within -a of it, else it joins the best such\n"
                 "         one; representatives are pairwise below -a, every member is within -a of its own; one line per\n"
-                "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative),\n"
+                "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative;\n"
+                "         setcover = greedy set cover, as MMseqs2 and Linclust cluster: the sketch with the most still-uncovered\n"
+                "         neighbours within -a becomes a representative and takes them as its members, ties to the first in\n"
+                "         the file, until none is left -- the guarantees and the lines of greedy, the representative chosen by\n"
+                "         coverage instead of file order; it holds the hits of the whole comparison, 12 bytes per pair within -a),\n"
                 "         --order file|size [file] (cluster --linkage greedy: the order the sketches are processed in; size =\n"
                 "         descending hv_norm_2, ties in file order -- the most complete genome of a group represents it;\n"
                 "         cluster ids count the representatives in that order, the lines stay in file order),\n"
@@ -209,9 +214,10 @@ Cli parse(int argc, char **argv) {
         c.search_path_given = true;
         break;
       case '\x04':  // (long form only) cluster only (extension)
-        if (val == "single") c.greedy = false;
-        else if (val == "greedy") c.greedy = true;
-        else die("invalid value '" + val + "' for '--linkage' (single | greedy)");
+        if (val == "single") c.greedy = false, c.setcover = false;
+        else if (val == "greedy") c.greedy = true, c.setcover = false;
+        else if (val == "setcover") c.greedy = false, c.setcover = true;
+        else die("invalid value '" + val + "' for '--linkage' (single | greedy | setcover)");
         c.linkage_given = true;
         break;
       case '\x05':  // (long form only) cluster --linkage greedy only (extension)
@@ -252,6 +258,8 @@ Cli parse(int argc, char **argv) {
   if (c.search_path == 2 && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
   if (c.linkage_given && c.mode != "cluster") die("--linkage is not supported by " + c.mode + ": it chooses how cluster forms its clusters");
+  if (c.order_given && c.mode == "cluster" && c.setcover)
+    die("--order is not supported by cluster --linkage setcover: the order the representatives are chosen in is the rule's own");
   if (c.order_given && !(c.mode == "cluster" && c.greedy))
     die("--order needs cluster --linkage greedy: single-linkage components do not depend on the order of the sketches");
   for (int k = 0; k < 2; ++k) {
@@ -259,6 +267,7 @@ Cli parse(int argc, char **argv) {
     const std::string f = k ? "--levels" : "--tree";
     if (c.mode != "cluster") die(f + " is not supported by " + c.mode + ": it belongs to cluster --linkage single");
     if (c.greedy) die(f + " needs cluster --linkage single: greedy clusters are not nested and have no tree");
+    if (c.setcover) die(f + " needs cluster --linkage single: set-cover clusters are not nested and have no tree");
     if (c.shards) die(f + " is not supported with --shards: cluster runs on the first visible GPU");
   }
   if (c.levels_given && !(c.levels[0] > (c.ani_th_given ? c.ani_th : 95.0f)))
@@ -921,6 +930,9 @@ int run_search(const Cli &c) {
 // offsets of the upload are permuted, nothing is gathered on the device -- and the lines stay in file order:
 // "<file_str>\t<cluster id>\t<file_str of its representative>\t<ANI with it, as dist prints it>\n"; ids count the
 // representatives in processing order.
+// --linkage setcover (hg_cluster_setcover_dev): greedy set cover -- the sketch with the most still-uncovered neighbours
+// becomes a representative and takes them as its members.  The lines are those of greedy, in file order; a representative
+// may stand behind its members in the file.
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.shards) die("--shards is not supported by cluster: it runs on the first visible GPU");
@@ -936,8 +948,8 @@ int run_cluster(const Cli &c) {
   load(c.path, L);
   opener.join();
   DevSet D;
-  std::vector<uint32_t> perm;  // greedy: processing position -> record
-  if (c.greedy) {
+  std::vector<uint32_t> perm;  // greedy, setcover: processing position -> record (setcover: the file order)
+  if (c.greedy || c.setcover) {
     perm.resize(L.n);
     for (size_t i = 0; i < L.n; ++i) perm[i] = (uint32_t)i;
     if (c.order_size) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return L.n2[a] > L.n2[b]; });
@@ -961,15 +973,17 @@ int run_cluster(const Cli &c) {
   };
   std::vector<Level> more;
   std::vector<hg_ani_hit> tree;  // --tree / --levels
-  if (c.greedy) {
+  if (c.greedy || c.setcover) {
     void *d_ani = nullptr;
     ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(float), &d_ani), "alloc");
-    ck(ctx, hg_cluster_greedy_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
-                                  static_cast<uint32_t *>(d_cl), static_cast<float *>(d_ani), &n_cl), "cluster");
+    ck(ctx, (c.setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th,
+                                                                           static_cast<uint32_t *>(d_rep), static_cast<uint32_t *>(d_cl),
+                                                                           static_cast<float *>(d_ani), &n_cl), "cluster");
     ani.resize(L.n);
     ck(ctx, hg_copy_d2h(ctx, ani.data(), d_ani, L.n * sizeof(float)), "download");
     (void)hg_dev_free(ctx, d_ani);
-    debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
+    if (c.setcover) debugf("set-cover resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_setcover_rounds(ctx));
+    else debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
   } else if (c.tree_given || c.levels_given) {
     // one comparison at the floor -a (hg_cluster_tree_dev); every level is a cut of the tree (the step calls of hg_cluster)
     void *d_tree = nullptr;
@@ -1006,7 +1020,8 @@ int run_cluster(const Cli &c) {
   debugf("clusters on the host in %.1f ms", (now_s() - tp) * 1e3);
   std::vector<uint32_t> size(n_cl, 0);
   for (size_t i = 0; i < L.n; ++i) {
-    if (cl[i] >= n_cl || rep[i] > i) die("inconsistent cluster result");
+    // (a set-cover representative may have a larger index than its member)
+    if (cl[i] >= n_cl || (c.setcover ? rep[i] >= L.n : rep[i] > i)) die("inconsistent cluster result");
     ++size[cl[i]];
   }
   size_t singletons = 0;
@@ -1015,7 +1030,7 @@ int run_cluster(const Cli &c) {
     for (size_t i = 0; i < L.n; ++i)
       if (v.cl[i] >= v.n_cl || v.rep[i] > i) die("inconsistent cluster result");
   std::string o;
-  if (c.greedy) {
+  if (c.greedy || c.setcover) {
     std::vector<uint32_t> pos(L.n);  // record -> processing position
     for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
     char num[16];

@@ -1,5 +1,5 @@
 // hg_cluster_common.h -- the device routines the clustering files share (hg_cluster.hip, hg_cluster_greedy.hip,
-// hg_cluster_tree.hip): the lock-free union-find over rep[n], the order-preserving ANI key and the grid of a grid-stride
+// hg_cluster_setcover.hip, hg_cluster_tree.hip): the lock-free union-find over rep[n], the order-preserving ANI key and the grid of a grid-stride
 // launch.  One copy; each file's head comment says how it uses them.
 #pragma once
 #include <algorithm>

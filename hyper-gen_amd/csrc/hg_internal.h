@@ -115,9 +115,11 @@ struct hg_ctx {
   Buf w_sorthits; // keys / permutations / scratch of the device-side hit ordering
   Buf w_clu_res;  // clustering: 16 result words ([0] cluster count, [1] error word of the hook kernel), never regrown
   Buf w_clu;      // clustering: per-tile root counts of the dense-id scan
-  Buf w_clu_hits; // hg_cluster_dev / hg_cluster_greedy_dev: scratch hit list of one row block
+  Buf w_clu_hits; // hg_cluster_dev / hg_cluster_greedy_dev: scratch hit list of one row block; hg_cluster_setcover_dev: the hits of all blocks
   Buf w_grd;      // hg_cluster_greedy*: per-node state -- n 64-bit best words, then n status words, then n blocked marks
   uint64_t greedy_rounds = 0;  // rounds the last greedy call ran, summed over its blocks (hg_ctx_cluster_greedy_rounds)
+  Buf w_setcover; // hg_cluster_setcover*: per-node state -- n 64-bit best words, n m1 words, n m2 words, then n status words, then n degrees
+  uint64_t setcover_rounds = 0;  // rounds the last set-cover call ran (hg_ctx_cluster_setcover_rounds)
   Buf w_tree;     // hg_cluster_tree*: per-node state -- n 64-bit best_pair words, then n comp words, then n best_ani keys -- and two forests of n - 1 edges
   uint64_t tree_rounds = 0;  // rounds the last tree call ran, summed over its blocks (hg_ctx_cluster_tree_rounds)
   Buf w_srch_blk;   // hg_search_topk*: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
@@ -165,6 +167,7 @@ struct hg_ctx {
   int dbg_sort_buckets = 0;
   uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the scratch list of hg_cluster_dev starts with (0: its own size)
   uint64_t dbg_greedy_rounds = 0;  // test hook "greedy_rounds": rounds hg_cluster_greedy* queue per readback of the undecided count (0: its default)
+  uint64_t dbg_setcover_rounds = 0;  // test hook "setcover_rounds": rounds hg_cluster_setcover* queue per readback of the undecided count (0: its default)
   uint64_t dbg_tree_rounds = 0;  // test hook "tree_rounds": rounds hg_cluster_tree* queue per readback of the count of selecting roots (0: its default)
   uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_pair_limit = 0;  // test hook "pair_limit": pairs one kernel launch of a comparison may enumerate (0: 2^32 - 1, the hit counter's reach)
@@ -184,9 +187,10 @@ hg_status hg_ensure_pinned(hg_ctx *ctx, size_t bytes);
 // stream synchronisation.  On return everything queued on the stream before the call has finished.  *out -> the n words.
 hg_status hg_publish_words(hg_ctx *ctx, uint32_t *d_words, uint32_t n, const uint32_t **out, uint32_t zero_n = 0);
 
-// ---- clustering: what hg_cluster.hip, hg_cluster_greedy.hip and hg_cluster_tree.hip share (device routines: hg_cluster_common.h) ----
+// ---- clustering: what hg_cluster.hip, hg_cluster_greedy.hip, hg_cluster_setcover.hip and hg_cluster_tree.hip share (device routines: hg_cluster_common.h) ----
 // The ctx's 16 clustering result words (w_clu_res): [0] cluster count, [1] error word (a hit with an index >= n); the
-// greedy resolution keeps [2], [3] = nodes still undecided after the odd / even rounds and [4] = rounds run behind them;
+// greedy and the set-cover resolution keep [2], [3] = nodes still undecided after the odd / even rounds and [4] = rounds
+// run behind them;
 // the tree resolution [5], [6] = roots that selected an edge in the odd / even rounds, [7] = edges of the forest being
 // written, and counts its rounds in [4] too.
 // All are zero between calls: the call that reads them back clears them behind the copy (hg_publish_words).

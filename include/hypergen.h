@@ -86,6 +86,8 @@ int hg_device_count(void);
  *                                      0 = the ctx's own size)
  *       "greedy_rounds" = "<n>"       (rounds hg_cluster_greedy* queue before they read the count of undecided nodes back;
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
+ *       "setcover_rounds" = "<n>"     (rounds hg_cluster_setcover* queue before they read the count of undecided nodes back;
+ *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "tree_rounds" = "<n>"         (rounds hg_cluster_tree* queue before they read the count of selecting roots back;
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
@@ -285,10 +287,11 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
  * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_tree{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev} and hg_cluster_tree{,_dev} accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.
- * hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev and hg_cluster_tree_hits_dev (they take hits), hg_dist_prep_ops_dev, the
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev} and hg_cluster_tree{,_dev} accept HG_ANI_MASH and
+ * HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
+ * hg_cluster_tree_hits_dev (they take hits), hg_dist_prep_ops_dev, the
  * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
@@ -493,6 +496,58 @@ hg_status hg_cluster_greedy(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2
                             float ani_th, uint32_t *rep, uint32_t *cluster, float *ani, size_t *n_clusters);
 /* rounds of the last greedy call on this ctx, summed over its blocks (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_greedy_rounds(const hg_ctx *ctx);
+
+/* Greedy set-cover clustering (no reference counterpart; the scheme MMseqs2 and Linclust cluster with by default): the
+ * guarantees of hg_cluster_greedy -- representatives pairwise below the threshold, every member at or above it with its own
+ * representative -- with the representative chosen by coverage instead of by position: a star whose centre is the last sketch
+ * is n - 1 greedy clusters and one here, a chain 0 - 1 - 2 two greedy clusters and one here, around sketch 1.
+ * Input: n sketches, hit records {ref_idx, qry_idx, ani} and ani_th.  A record COUNTS iff ani >= ani_th (the float comparison
+ * of hg_dist_dev: NaN never counts) and ref_idx != qry_idx; a counting record is an edge between its two indices, in either
+ * orientation.  An index >= n in any record, at any ANI: HG_ERR_INVALID, nothing reported, the next call on the ctx starts
+ * clean.  U is the set of undecided nodes, at first all of them.  While U is not empty:
+ *   1. deg(v) = the number of counting records with v at one end and the other end in U, for every v in U;
+ *   2. v* = the node of U with the largest deg, ties to the smallest index: it becomes a REPRESENTATIVE;
+ *   3. every u in U with a counting record {v*, u} becomes a MEMBER of v*; ani[u] = the highest ANI among those records;
+ *   4. v* and its new members leave U.
+ * Degrees count records -- a pair given twice counts twice; the symmetric output of hg_dist_dev has each pair once, so there
+ * deg is the number of undecided neighbours, and a list that holds every pair the same number of times resolves identically.
+ * A node of degree 0 is thereby a representative of itself.  A member never covers anybody and never changes representative.
+ *   rep[i]      = i for a representative, its representative for a member (which may have a larger index than i);
+ *   cluster[i]  = the dense id of rep[i]: 0, 1, ... in increasing order of the representatives' indices;
+ *   ani[i]      = 100.0f for a representative, the pair's ANI for a member (optional: may be NULL);
+ *   *n_clusters = the number of representatives.
+ * The result depends on the multiset of counting records alone -- not on hit order, orientation, block sizes, rounds per
+ * readback or scheduling.  n < 2^31 (HG_ERR_UNSUPPORTED beyond); n == 0: HG_OK, *n_clusters = 0; NULL rep / cluster /
+ * n_clusters: HG_ERR_INVALID; HG_ANI_CONTAINMENT: HG_ERR_INVALID as for hg_cluster_dev; results are final on return.
+ * On the device the rule is resolved in rounds over the live records -- both ends undecided -- (hg_cluster_setcover.hip):
+ * setcover_count_kernel, one lane per record, integer atomic adds into deg; setcover_spread_kernel twice, a 64-bit atomic
+ * max per record end -- first of key(v) = deg(v) << 32 | (0xFFFFFFFF - v), then of the maxima so found: the largest key
+ * within two live hops of every node; setcover_select_kernel, one lane per node -- the strict maximum of its two hops is a
+ * representative: the sequential walk chooses it with exactly the cover set it has now, and the nodes chosen in one round
+ * are more than two hops apart; setcover_cover_kernel, one lane per record {representative, undecided}, an atomic max of
+ * (ani, -representative) into the undecided end; setcover_settle_kernel, one lane per node -- covered: member.  The
+ * global maximum is chosen in every round.  The host queues "setcover_rounds" rounds (hg_ctx_set_debug; default 4) per
+ * readback of the undecided count and stops at 0.  Dense groups resolve in a few rounds; the worst case, a path
+ * 0 - 1 - 2 - ..., takes about n / 3 rounds (accepted).  The dense ids come from hg_cluster_finish_dev's kernels.
+ *   hg_cluster_setcover_hits_dev : a complete hit list of the caller, n_hits < 2^32 (HG_ERR_UNSUPPORTED beyond).
+ *   hg_cluster_setcover_dev : resident sketches.  UNLIKE hg_cluster_greedy_dev and hg_cluster_tree_dev it cannot resolve a
+ *                           row block before it has seen them all -- the rule is global: the first representative is the
+ *                           best-covering node of the whole graph.  It runs the symmetric comparison in the row blocks of
+ *                           hg_cluster_dev ("pair_limit" as there), APPENDS every block's hits to one scratch list and
+ *                           resolves once at the end: the list costs 12 bytes per hit above the threshold.
+ *                           "cluster_hit_cap" sets the list's first size; when a block overflows it, the list grows to what
+ *                           is needed, the hits of earlier blocks are kept, and the block runs again.  A total of 2^32 - 1
+ *                           hits or more: HG_ERR_UNSUPPORTED (the hit list does not fit; a higher threshold would).
+ *   hg_cluster_setcover     : host arrays in and out, staged through the ctx. */
+hg_status hg_cluster_setcover_hits_dev(hg_ctx *ctx, size_t n, const hg_ani_hit *d_hits, size_t n_hits, float ani_th,
+                                       uint32_t *d_rep, uint32_t *d_cluster, float *d_ani, size_t *n_clusters);
+hg_status hg_cluster_setcover_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d,
+                                  uint32_t ksize, float ani_th, uint32_t *d_rep, uint32_t *d_cluster, float *d_ani,
+                                  size_t *n_clusters);
+hg_status hg_cluster_setcover(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                              float ani_th, uint32_t *rep, uint32_t *cluster, float *ani, size_t *n_clusters);
+/* rounds of the last set-cover call on this ctx (diagnostic; 0 = none yet) */
+uint64_t hg_ctx_cluster_setcover_rounds(const hg_ctx *ctx);
 
 /* The single-linkage tree (no reference counterpart): every threshold of single linkage from ONE comparison.  The
  * maximum-ANI spanning forest of the hit graph at a floor ani_th has at most n - 1 edges -- 12 (n - 1) bytes however many
