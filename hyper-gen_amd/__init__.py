@@ -661,11 +661,8 @@ class Context:
         self._ck(lib().hg_cluster_finish_dev(self._h, _ptr(d_rep), n, _ptr(d_cluster), C.byref(nc)))
         return nc.value
 
-    # ---- greedy representative clustering (hg_cluster_greedy*) -----------------------------------
-    def cluster_greedy(self, hv, n2, ksize=21, ani_th=95.0):
-        """hg_cluster_greedy on host sketches in processing order: numpy (rep, cluster, ani, n_clusters) -- rep[i] = i for a
-        representative, else the earlier representative with the highest ANI; cluster[i] = the dense id of rep[i];
-        ani[i] = 100 for a representative, else the ANI of (rep[i], i)"""
+    # ---- the three forms of a representative scheme (greedy, set cover), given its C function ----------
+    def _rep_host(self, fn, hv, n2, ksize, ani_th):
         h = np.ascontiguousarray(hv, np.int16)
         nn = np.ascontiguousarray(n2, np.int32)
         n = h.shape[0]
@@ -673,24 +670,36 @@ class Context:
         cl = np.zeros(n, np.uint32)
         ani = np.zeros(n, np.float32)
         nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_greedy(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th),
-                                         _ptr(rep), _ptr(cl), _ptr(ani), C.byref(nc)))
+        self._ck(fn(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th), _ptr(rep), _ptr(cl), _ptr(ani), C.byref(nc)))
         return rep, cl, ani, nc.value
+
+    def _rep_dev(self, fn, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani, ksize, ani_th):
+        nc = C.c_size_t(0)
+        self._ck(fn(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep), _ptr(d_cluster), _ptr(d_ani or 0),
+                    C.byref(nc)))
+        return nc.value
+
+    def _rep_hits_dev(self, fn, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani):
+        nc = C.c_size_t(0)
+        self._ck(fn(self._h, n, _ptr(d_hits or 0), n_hits, C.c_float(ani_th), _ptr(d_rep or 0), _ptr(d_cluster or 0), _ptr(d_ani or 0),
+                    C.byref(nc)))
+        return nc.value
+
+    # ---- greedy representative clustering (hg_cluster_greedy*) -----------------------------------
+    def cluster_greedy(self, hv, n2, ksize=21, ani_th=95.0):
+        """hg_cluster_greedy on host sketches in processing order: numpy (rep, cluster, ani, n_clusters) -- rep[i] = i for a
+        representative, else the earlier representative with the highest ANI; cluster[i] = the dense id of rep[i];
+        ani[i] = 100 for a representative, else the ANI of (rep[i], i)"""
+        return self._rep_host(lib().hg_cluster_greedy, hv, n2, ksize, ani_th)
 
     def cluster_greedy_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani=None, ksize=21, ani_th=95.0):
         """hg_cluster_greedy_dev on resident sketches (device pointers; d_ani may be None); returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_greedy_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep),
-                                             _ptr(d_cluster), _ptr(d_ani or 0), C.byref(nc)))
-        return nc.value
+        return self._rep_dev(lib().hg_cluster_greedy_dev, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani, ksize, ani_th)
 
     def cluster_greedy_hits_dev(self, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani=None):
         """hg_cluster_greedy_hits_dev on a complete device-resident hit list (d_ani may be None); returns the number of
         clusters; raises HgError(ERR_INVALID) if a hit has an index >= n"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_greedy_hits_dev(self._h, n, _ptr(d_hits or 0), n_hits, C.c_float(ani_th), _ptr(d_rep or 0),
-                                                  _ptr(d_cluster or 0), _ptr(d_ani or 0), C.byref(nc)))
-        return nc.value
+        return self._rep_hits_dev(lib().hg_cluster_greedy_hits_dev, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani)
 
     def cluster_greedy_rounds(self):
         """rounds of the last greedy call on this ctx, summed over its blocks (hg_ctx_cluster_greedy_rounds)"""
@@ -702,31 +711,16 @@ class Context:
         undecided neighbours becomes a representative and takes them as its members, until none is left; rep[i] = i for a
         representative, else its representative; cluster[i] = the dense id of rep[i]; ani[i] = 100 for a
         representative, else the ANI of (rep[i], i)"""
-        h = np.ascontiguousarray(hv, np.int16)
-        nn = np.ascontiguousarray(n2, np.int32)
-        n = h.shape[0]
-        rep = np.zeros(n, np.uint32)
-        cl = np.zeros(n, np.uint32)
-        ani = np.zeros(n, np.float32)
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_setcover(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th),
-                                           _ptr(rep), _ptr(cl), _ptr(ani), C.byref(nc)))
-        return rep, cl, ani, nc.value
+        return self._rep_host(lib().hg_cluster_setcover, hv, n2, ksize, ani_th)
 
     def cluster_setcover_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani=None, ksize=21, ani_th=95.0):
         """hg_cluster_setcover_dev on resident sketches (device pointers; d_ani may be None); returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_setcover_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep),
-                                               _ptr(d_cluster), _ptr(d_ani or 0), C.byref(nc)))
-        return nc.value
+        return self._rep_dev(lib().hg_cluster_setcover_dev, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_ani, ksize, ani_th)
 
     def cluster_setcover_hits_dev(self, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani=None):
         """hg_cluster_setcover_hits_dev on a complete device-resident hit list (d_ani may be None); returns the number of
         clusters; raises HgError(ERR_INVALID) if a hit has an index >= n"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_setcover_hits_dev(self._h, n, _ptr(d_hits or 0), n_hits, C.c_float(ani_th), _ptr(d_rep or 0),
-                                                    _ptr(d_cluster or 0), _ptr(d_ani or 0), C.byref(nc)))
-        return nc.value
+        return self._rep_hits_dev(lib().hg_cluster_setcover_hits_dev, n, d_hits, n_hits, ani_th, d_rep, d_cluster, d_ani)
 
     def cluster_setcover_rounds(self):
         """rounds of the last set-cover call on this ctx (hg_ctx_cluster_setcover_rounds)"""

@@ -153,7 +153,7 @@ extern "C" hg_status hg_ctx_set_debug(hg_ctx *c, const char *key, const char *va
   if (k == "dist_tile") c->dbg_dist_tile = v;
   else if (k == "sort_test_buckets") c->dbg_sort_buckets = std::atoi(v.c_str());
   else if (k == "pair_limit") c->dbg_pair_limit = std::strtoull(v.c_str(), nullptr, 10);  // hg_dist_block_dev / hg_hamming_search_block_dev: row blocks from this many pairs on
-  else if (k == "cluster_hit_cap") c->dbg_cluster_hit_cap = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_dev: start the scratch hit list this small (grow path)
+  else if (k == "cluster_hit_cap") c->dbg_cluster_hit_cap = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_row_blocks: start the hit list this small (grow path)
   else if (k == "tree_rounds") c->dbg_tree_rounds = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_tree*: rounds queued per readback of the count of selecting roots
   else if (k == "setcover_rounds") c->dbg_setcover_rounds = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_setcover*: rounds queued per readback of the undecided count
   else if (k == "greedy_rounds") c->dbg_greedy_rounds = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_greedy*: rounds queued per readback of the undecided count

@@ -14,8 +14,8 @@
 //               undecided are counted into a device word;
 //   * assign  : once per block, over ALL its hits: lo a representative -> atomic max of (ani, -lo) into best[hi].  Columns
 //               behind the block get their coverage here, which is the entry condition of the blocks that follow;
-//   * finish  : rep / ani from status and best, then the dense ids with hg_cluster.hip's finishing launches (every
-//               tree has depth 1).
+//   * finish  : rep / ani from status and best (hg_cluster_queue_rep_ani), then the dense ids with hg_cluster.hip's
+//               finishing launches (every tree has depth 1).
 // Every kernel runs to its end on its own: no cooperative launch, no grid-wide barrier, no workgroup waits for another
 // one's store.  The host queues a few rounds, reads the undecided count back (hg_publish_words) and stops at 0; the
 // rounds queued behind the one that reached 0 see that word and return at once.
@@ -49,9 +49,7 @@
 #include "hg_internal.h"
 
 namespace {
-constexpr uint32_t ST_UNDECIDED = 0, ST_REP = 1, ST_MEMBER = 2;
-constexpr uint64_t GR_DEFAULT_ROUNDS = 4;           // rounds queued per readback of the undecided count
-constexpr size_t GR_DEFAULT_HITS = (size_t)1 << 22;  // first size of the scratch hit list (as hg_cluster_dev)
+constexpr uint64_t GR_DEFAULT_ROUNDS = 4;  // rounds queued per readback of the undecided count
 
 __device__ __forceinline__ uint32_t st_load(const uint32_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -61,7 +59,7 @@ __device__ __forceinline__ void st_store(uint32_t *p, uint32_t v) {
 }
 
 struct Greedy {
-  uint64_t *best;     // n: (ani key << 32 | 0xFFFFFFFF - representative) of the best covering representative, 0 = none
+  uint64_t *best;     // n: best_word of the best covering representative, 0 = none
   uint32_t *status;   // n: ST_*
   uint32_t *blocked;  // n: number of the last round that blocked the node
   uint32_t *res;      // the ctx's clustering result words (HG_CLU_*)
@@ -95,12 +93,8 @@ __global__ __launch_bounds__(256) void greedy_mark_kernel(const hg_ani_hit *__re
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x; h < n_hits; h += stride) {
     const hg_ani_hit e = hits[h];
-    if (e.ref_idx >= n || e.qry_idx >= n) {
-      __hip_atomic_store(res + HG_CLU_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      continue;
-    }
-    if (!(e.ani >= ani_th) || e.ref_idx == e.qry_idx) continue;  // (the side of the threshold exactly as in dist)
-    const uint32_t lo = e.ref_idx < e.qry_idx ? e.ref_idx : e.qry_idx, hi = e.ref_idx < e.qry_idx ? e.qry_idx : e.ref_idx;
+    uint32_t lo, hi;
+    if (!hit_edge(e, n, ani_th, res + HG_CLU_ERR, &lo, &hi)) continue;
     if (lo < r0 || hi >= r1) continue;  // (a column behind the block: assign covers it, its own block decides it)
     const uint32_t s_lo = st_load(status + lo);
     if (s_lo == ST_REP) st_store(status + hi, ST_MEMBER);
@@ -134,26 +128,10 @@ __global__ __launch_bounds__(256) void greedy_assign_kernel(const hg_ani_hit *__
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x; h < n_hits; h += stride) {
     const hg_ani_hit e = hits[h];
-    if (e.ref_idx >= n || e.qry_idx >= n) {
-      __hip_atomic_store(res + HG_CLU_ERR, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      continue;
-    }
-    if (!(e.ani >= ani_th) || e.ref_idx == e.qry_idx) continue;
-    const uint32_t lo = e.ref_idx < e.qry_idx ? e.ref_idx : e.qry_idx, hi = e.ref_idx < e.qry_idx ? e.qry_idx : e.ref_idx;
+    uint32_t lo, hi;
+    if (!hit_edge(e, n, ani_th, res + HG_CLU_ERR, &lo, &hi)) continue;
     if (lo < r0 || lo >= r1 || status[lo] != ST_REP) continue;
-    const uint64_t key = (uint64_t)ani_key(e.ani) << 32 | (uint64_t)(0xFFFFFFFFu - lo);
-    (void)__hip_atomic_fetch_max(best + hi, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-__global__ __launch_bounds__(256) void greedy_finish_kernel(const uint64_t *__restrict__ best, const uint32_t *__restrict__ status,
-                                                            uint32_t n, uint32_t *__restrict__ rep, float *__restrict__ ani) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint64_t b = best[i];
-    const bool is_rep = status[i] != ST_MEMBER || b == 0ull;  // (a member always has a best word: the second test only keeps rep[] in range)
-    rep[i] = is_rep ? (uint32_t)i : 0xFFFFFFFFu - (uint32_t)b;
-    if (ani) ani[i] = is_rep ? 100.0f : key_ani((uint32_t)(b >> 32));
+    (void)__hip_atomic_fetch_max(best + hi, best_word(e.ani, lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -201,28 +179,9 @@ hg_status greedy_block(hg_ctx *c, Greedy *g, const hg_ani_hit *d_hits, size_t n_
 
 hg_status greedy_end(hg_ctx *c, Greedy *g, size_t n, uint32_t *d_rep, uint32_t *d_cluster, float *d_ani, size_t *n_clusters) {
   hg_status s;
-  hipLaunchKernelGGL(greedy_finish_kernel, dim3(grid_for(c, n)), dim3(256), 0, c->stream, g->best, g->status, (uint32_t)n, d_rep, d_ani);
-  HG_HIP(c, hipGetLastError());
+  if ((s = hg_cluster_queue_rep_ani(c, g->best, g->status, n, d_rep, d_ani)) != HG_OK) return s;
   if ((s = hg_cluster_queue_ids(c, d_rep, n, d_cluster, g->res)) != HG_OK) return s;
-  // (the publishing kernel clears the words behind its copy: the next clustering on this ctx starts clean)
-  const uint32_t *h_res = nullptr;
-  if ((s = hg_publish_words(c, g->res, HG_CLU_WORDS, &h_res, HG_CLU_WORDS)) != HG_OK) return s;
-  c->greedy_rounds = h_res[HG_CLU_ROUNDS];
-  if (h_res[HG_CLU_ERR]) return hg_fail(c, HG_ERR_INVALID, "a hit given to hg_cluster_greedy_hits_dev had an index >= n");
-  *n_clusters = h_res[HG_CLU_COUNT];
-  return HG_OK;
-}
-
-hg_status check_args(hg_ctx *c, size_t n, size_t *n_clusters) {
-  if (!n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_clusters == NULL");
-  *n_clusters = 0;
-  if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^31");
-  return HG_OK;
-}
-hg_status check_metric(hg_ctx *c) {
-  if (c->ani_metric == HG_ANI_CONTAINMENT)  // (the graph is undirected: HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT)
-    return hg_fail(c, HG_ERR_INVALID, "clustering needs a symmetric ANI metric: HG_ANI_CONTAINMENT is directional");
-  return HG_OK;
+  return hg_cluster_close(c, g->res, &c->greedy_rounds, "hg_cluster_greedy_hits_dev", n_clusters);
 }
 }  // namespace
 
@@ -231,7 +190,7 @@ extern "C" uint64_t hg_ctx_cluster_greedy_rounds(const hg_ctx *c) { return c ? c
 extern "C" hg_status hg_cluster_greedy_hits_dev(hg_ctx *c, size_t n, const hg_ani_hit *d_hits, size_t n_hits, float ani_th,
                                                 uint32_t *d_rep, uint32_t *d_cluster, float *d_ani, size_t *n_clusters) {
   if (!c) return HG_ERR_INVALID;
-  hg_status s = check_args(c, n, n_clusters);
+  hg_status s = hg_cluster_check(c, n, n_clusters, false);
   if (s != HG_OK) return s;
   if (n == 0) return HG_OK;
   if (!d_rep || !d_cluster) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
@@ -247,60 +206,38 @@ extern "C" hg_status hg_cluster_greedy_dev(hg_ctx *c, const int16_t *d_hv, const
                                            uint32_t ksize, float ani_th, uint32_t *d_rep, uint32_t *d_cluster, float *d_ani,
                                            size_t *n_clusters) {
   if (!c) return HG_ERR_INVALID;
-  hg_status s = check_args(c, n, n_clusters);
+  hg_status s = hg_cluster_check(c, n, n_clusters, true);
   if (s != HG_OK) return s;
-  if ((s = check_metric(c)) != HG_OK) return s;
   if (n == 0) return HG_OK;
   if (!d_hv || !d_norm2 || !d_rep || !d_cluster) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
   Greedy g{};
   if ((s = greedy_begin(c, n, &g)) != HG_OK) return s;
-  // The block loop of hg_cluster_dev: rows [r0, r0 + rows) x columns [r0, n) of the symmetric comparison, within the pairs
-  // one launch may count ("pair_limit"), into the ctx's scratch list, which grows to a block's hit count when it overflows
-  // ("cluster_hit_cap": its first size).  Each block is resolved before the next one reuses the list; the last row has no
-  // pairs of its own but is a block all the same (its node is decided like any other).
-  const uint64_t pair_limit = hg_pair_limit(c);
-  const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-  size_t cap = c->dbg_cluster_hit_cap ? (size_t)c->dbg_cluster_hit_cap
-                                      : std::max(c->w_clu_hits.cap / sizeof(hg_ani_hit), (size_t)std::min<uint64_t>(pairs, GR_DEFAULT_HITS));
-  if ((s = hg_ensure(c, c->w_clu_hits, std::max<size_t>(cap, 1) * sizeof(hg_ani_hit))) != HG_OK) return s;
-  for (size_t r0 = 0; r0 < n;) {
-    const size_t cols = n - r0, rows = (size_t)std::min<uint64_t>(cols, std::max<uint64_t>(1, pair_limit / cols));
-    size_t got = 0;
-    while (cols > 1) {
-      s = hg_dist_block_dev(c, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, rows, r0, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, cols, r0,
-                            hv_d, ksize, 1, ani_th, static_cast<hg_ani_hit *>(c->w_clu_hits.p), cap, &got);
-      if (s != HG_ERR_CAPACITY) break;
-      cap = got;  // (a capacity retry: the block ran to the end and counted every hit)
-      if ((s = hg_ensure(c, c->w_clu_hits, cap * sizeof(hg_ani_hit))) != HG_OK) return s;
-    }
-    if (s != HG_OK) return s;
-    if ((s = greedy_block(c, &g, static_cast<const hg_ani_hit *>(c->w_clu_hits.p), got, n, r0, r0 + rows, ani_th)) != HG_OK) return s;
-    r0 += rows;
-  }
+  // Each row block is resolved before the next one reuses the list; the last row has no pairs of its own but is a block
+  // all the same (its node is decided like any other).
+  s = hg_cluster_row_blocks(c, d_hv, d_norm2, n, hv_d, ksize, ani_th, false, nullptr,
+                            [&](const hg_ani_hit *d_hits, size_t got, size_t r0, size_t r1) {
+                              return greedy_block(c, &g, d_hits, got, n, r0, r1, ani_th);
+                            });
+  if (s != HG_OK) return s;
   return greedy_end(c, &g, n, d_rep, d_cluster, d_ani, n_clusters);
 }
 
 extern "C" hg_status hg_cluster_greedy(hg_ctx *c, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
                                        float ani_th, uint32_t *rep, uint32_t *cluster, float *ani, size_t *n_clusters) {
   if (!c) return HG_ERR_INVALID;
-  hg_status s = check_args(c, n, n_clusters);
+  hg_status s = hg_cluster_check(c, n, n_clusters, true);
   if (s != HG_OK) return s;
-  if ((s = check_metric(c)) != HG_OK) return s;
   if (n == 0) return HG_OK;
   if (!hv || !norm2 || !rep || !cluster) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
-  const size_t hb = n * (size_t)hv_d * sizeof(int16_t);
-  if ((s = hg_ensure(c, c->w_hv, hb + 64)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_n2a, n * sizeof(int32_t) + 64)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_ani, 3 * n * sizeof(uint32_t) + 64)) != HG_OK) return s;
-  HG_HIP(c, hipMemcpyAsync(c->w_hv.p, hv, hb, hipMemcpyHostToDevice, c->stream));
-  HG_HIP(c, hipMemcpyAsync(c->w_n2a.p, norm2, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  auto *d_rep = static_cast<uint32_t *>(c->w_ani.p), *d_cluster = d_rep + n;
+  const int16_t *d_hv;
+  const int32_t *d_norm2;
+  uint32_t *d_rep;
+  if ((s = hg_cluster_stage(c, hv, norm2, n, hv_d, 3 * n * sizeof(uint32_t), &d_hv, &d_norm2, &d_rep)) != HG_OK) return s;
+  uint32_t *d_cluster = d_rep + n;
   auto *d_ani = reinterpret_cast<float *>(d_cluster + n);
-  if ((s = hg_cluster_greedy_dev(c, static_cast<const int16_t *>(c->w_hv.p), static_cast<const int32_t *>(c->w_n2a.p), n, hv_d, ksize,
-                                 ani_th, d_rep, d_cluster, d_ani, n_clusters)) != HG_OK)
-    return s;
+  if ((s = hg_cluster_greedy_dev(c, d_hv, d_norm2, n, hv_d, ksize, ani_th, d_rep, d_cluster, d_ani, n_clusters)) != HG_OK) return s;
   HG_HIP(c, hipMemcpyAsync(rep, d_rep, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HG_HIP(c, hipMemcpyAsync(cluster, d_cluster, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (ani) HG_HIP(c, hipMemcpyAsync(ani, d_ani, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -49,9 +49,8 @@
 #include "hg_internal.h"
 
 namespace {
-constexpr uint64_t TR_DEFAULT_ROUNDS = 4;            // rounds queued per readback of the count of selecting roots
-constexpr size_t TR_DEFAULT_HITS = (size_t)1 << 22;  // first size of the scratch hit list (as hg_cluster_dev)
-constexpr uint64_t TR_NONE = ~0ull;                  // best_pair: no selection
+constexpr uint64_t TR_DEFAULT_ROUNDS = 4;  // rounds queued per readback of the count of selecting roots
+constexpr uint64_t TR_NONE = ~0ull;        // best_pair: no selection
 
 struct Tree {
   uint64_t *best_pair;    // n: lo << 32 | hi of the strongest edge leaving the component rooted here, TR_NONE = none
@@ -64,18 +63,9 @@ struct Tree {
   uint32_t round;         // rounds queued so far in this call
 };
 
-// candidate h of the two ranges; false: it does not count.  An index >= n is reported through err (when given).
-__device__ __forceinline__ bool tree_edge(const hg_ani_hit *__restrict__ a, size_t na, const hg_ani_hit *__restrict__ b, size_t h,
-                                          uint32_t n, float ani_th, uint32_t *err, uint32_t *lo, uint32_t *hi, uint32_t *key) {
-  const hg_ani_hit e = h < na ? a[h] : b[h - na];
-  if (e.ref_idx >= n || e.qry_idx >= n) {
-    if (err) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return false;
-  }
-  if (!(e.ani >= ani_th) || e.ref_idx == e.qry_idx) return false;  // (the side of the threshold exactly as in dist)
-  *lo = e.ref_idx < e.qry_idx ? e.ref_idx : e.qry_idx, *hi = e.ref_idx < e.qry_idx ? e.qry_idx : e.ref_idx;
-  *key = ani_key(e.ani);
-  return true;
+// candidate h of the two ranges (which of them counts: hit_edge, hg_cluster_common.h)
+__device__ __forceinline__ hg_ani_hit tree_candidate(const hg_ani_hit *__restrict__ a, size_t na, const hg_ani_hit *__restrict__ b, size_t h) {
+  return h < na ? a[h] : b[h - na];
 }
 
 // call / block entry: singleton components, no selection, an empty new forest; prev_word (the selecting roots "of the
@@ -102,8 +92,10 @@ __global__ __launch_bounds__(256) void tree_best_ani_kernel(const hg_ani_hit *__
   if (left == 0u) return;
   const size_t stride = (size_t)gridDim.x * blockDim.x, total = na + nb;
   for (size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x; h < total; h += stride) {
-    uint32_t lo, hi, key;
-    if (!tree_edge(a, na, b, h, n, ani_th, res + HG_CLU_ERR, &lo, &hi, &key)) continue;
+    const hg_ani_hit e = tree_candidate(a, na, b, h);
+    uint32_t lo, hi;
+    if (!hit_edge(e, n, ani_th, res + HG_CLU_ERR, &lo, &hi)) continue;
+    const uint32_t key = ani_key(e.ani);
     const uint32_t cl = comp[lo], ch = comp[hi];
     if (cl == ch) continue;
     (void)__hip_atomic_fetch_max(best_ani + cl, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -119,8 +111,10 @@ __global__ __launch_bounds__(256) void tree_best_pair_kernel(const hg_ani_hit *_
   if (res[HG_CLU_SELECTING + ((round - 1u) & 1u)] == 0u) return;  // (uniform over the grid: nobody writes that word in this launch)
   const size_t stride = (size_t)gridDim.x * blockDim.x, total = na + nb;
   for (size_t h = (size_t)blockIdx.x * blockDim.x + threadIdx.x; h < total; h += stride) {
-    uint32_t lo, hi, key;
-    if (!tree_edge(a, na, b, h, n, ani_th, nullptr, &lo, &hi, &key)) continue;
+    const hg_ani_hit e = tree_candidate(a, na, b, h);
+    uint32_t lo, hi;
+    if (!hit_edge(e, n, ani_th, nullptr, &lo, &hi)) continue;
+    const uint32_t key = ani_key(e.ani);
     const uint32_t cl = comp[lo], ch = comp[hi];
     if (cl == ch) continue;
     const uint64_t pair = (uint64_t)lo << 32 | hi;
@@ -211,13 +205,9 @@ hg_status tree_begin(hg_ctx *c, size_t n, Tree *g) {
   return tree_queue_init(c, g, n, true);
 }
 
-// the error word was seen: clear the result words for the next call and fail
-hg_status tree_bad_index(hg_ctx *c, Tree *g) {
-  const uint32_t *h_res = nullptr;
-  const hg_status s = hg_publish_words(c, g->res, HG_CLU_WORDS, &h_res, HG_CLU_WORDS);
-  if (s != HG_OK) return s;
-  c->tree_rounds = h_res[HG_CLU_ROUNDS];
-  return hg_fail(c, HG_ERR_INVALID, "a hit given to hg_cluster_tree_hits_dev had an index >= n");
+// the result words back and cleared; a set error word fails the call
+hg_status tree_close(hg_ctx *c, Tree *g, size_t *count) {
+  return hg_cluster_close(c, g->res, &c->tree_rounds, "hg_cluster_tree_hits_dev", count);
 }
 
 // The forest of (carried forest u d_hits[0, n_hits)), from singleton components, into the other forest buffer, which
@@ -253,7 +243,10 @@ hg_status tree_block(hg_ctx *c, Tree *g, const hg_ani_hit *d_hits, size_t n_hits
     if ((s = hg_publish_words(c, g->res, HG_CLU_WORDS, &h_res)) != HG_OK) return s;  // (nothing cleared: the call goes on)
     if (h_res[HG_CLU_SELECTING + (g->round & 1u)] == 0u) break;
   }
-  if (h_res[HG_CLU_ERR]) return tree_bad_index(c, g);
+  if (h_res[HG_CLU_ERR]) {  // (seen without clearing: close the call, which fails it)
+    size_t count;
+    return tree_close(c, g, &count);
+  }
   g->n_forest = std::min<size_t>(h_res[HG_CLU_EDGES], n - 1);
   g->cur ^= 1;
   return HG_OK;
@@ -267,25 +260,21 @@ hg_status tree_end(hg_ctx *c, Tree *g, size_t n, hg_ani_hit *d_tree, size_t *n_e
     HG_HIP(c, hipMemcpyAsync(d_rep, g->comp, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     if ((s = hg_cluster_queue_ids(c, d_rep, n, d_cluster, g->res)) != HG_OK) return s;
   }
-  // (the publishing kernel clears the words behind its copy: the next clustering on this ctx starts clean)
-  const uint32_t *h_res = nullptr;
-  if ((s = hg_publish_words(c, g->res, HG_CLU_WORDS, &h_res, HG_CLU_WORDS)) != HG_OK) return s;
-  c->tree_rounds = h_res[HG_CLU_ROUNDS];
+  size_t count = 0;
+  if ((s = tree_close(c, g, &count)) != HG_OK) return s;  // (no error word here: tree_block saw to it)
   *n_edges = g->n_forest;
-  *n_clusters = d_rep ? (size_t)h_res[HG_CLU_COUNT] : n - g->n_forest;
+  *n_clusters = d_rep ? count : n - g->n_forest;
   return HG_OK;
 }
 
-// the checks every form shares; *done: the call is answered (n == 0, or an error)
+// the checks every form shares (the tree's own around hg_cluster_check); *done: the call is answered (n == 0, or an error)
 hg_status check_args(hg_ctx *c, size_t n, const hg_ani_hit *tree, size_t tree_cap, size_t *n_edges, const uint32_t *rep,
                      const uint32_t *cluster, size_t *n_clusters, bool dist_form, bool *done) {
   *done = true;
   if (!n_edges || !n_clusters) return hg_fail(c, HG_ERR_INVALID, "n_edges == NULL or n_clusters == NULL");
-  *n_edges = 0, *n_clusters = 0;
-  if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "n must be < 2^31");
-  if (dist_form && c->ani_metric == HG_ANI_CONTAINMENT)  // (the graph is undirected: HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT)
-    return hg_fail(c, HG_ERR_INVALID, "clustering needs a symmetric ANI metric: HG_ANI_CONTAINMENT is directional");
-  if (n == 0) return HG_OK;
+  *n_edges = 0;
+  const hg_status s = hg_cluster_check(c, n, n_clusters, dist_form);
+  if (s != HG_OK || n == 0) return s;
   if (!tree) return hg_fail(c, HG_ERR_INVALID, "NULL tree array");
   if ((rep == nullptr) != (cluster == nullptr)) return hg_fail(c, HG_ERR_INVALID, "rep and cluster: both or neither");
   if (tree_cap < n - 1) {
@@ -325,29 +314,12 @@ extern "C" hg_status hg_cluster_tree_dev(hg_ctx *c, const int16_t *d_hv, const i
   HG_ENTER(c);
   Tree g{};
   if ((s = tree_begin(c, n, &g)) != HG_OK) return s;
-  // The block loop of hg_cluster_dev: rows [r0, r0 + rows) x columns [r0, n) of the symmetric comparison, within the pairs
-  // one launch may count ("pair_limit"), into the ctx's scratch list, which grows to a block's hit count when it overflows
-  // ("cluster_hit_cap": its first size).  A block's candidates are the carried forest and its hits; a block without hits
-  // leaves the forest as it is.
-  const uint64_t pair_limit = hg_pair_limit(c);
-  const uint64_t pairs = (uint64_t)n * (n - 1) / 2;
-  size_t cap = c->dbg_cluster_hit_cap ? (size_t)c->dbg_cluster_hit_cap
-                                      : std::max(c->w_clu_hits.cap / sizeof(hg_ani_hit), (size_t)std::min<uint64_t>(pairs, TR_DEFAULT_HITS));
-  if ((s = hg_ensure(c, c->w_clu_hits, std::max<size_t>(cap, 1) * sizeof(hg_ani_hit))) != HG_OK) return s;
-  for (size_t r0 = 0; r0 + 1 < n;) {
-    const size_t cols = n - r0, rows = (size_t)std::min<uint64_t>(cols, std::max<uint64_t>(1, pair_limit / cols));
-    size_t got = 0;
-    for (;;) {
-      s = hg_dist_block_dev(c, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, rows, r0, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, cols, r0,
-                            hv_d, ksize, 1, ani_th, static_cast<hg_ani_hit *>(c->w_clu_hits.p), cap, &got);
-      if (s != HG_ERR_CAPACITY) break;
-      cap = got;  // (a capacity retry: the block ran to the end and counted every hit)
-      if ((s = hg_ensure(c, c->w_clu_hits, cap * sizeof(hg_ani_hit))) != HG_OK) return s;
-    }
-    if (s != HG_OK) return s;
-    if (got && (s = tree_block(c, &g, static_cast<const hg_ani_hit *>(c->w_clu_hits.p), got, n, ani_th)) != HG_OK) return s;
-    r0 += rows;
-  }
+  // A row block's candidates are the carried forest and its hits; a block without hits leaves the forest as it is.
+  s = hg_cluster_row_blocks(c, d_hv, d_norm2, n, hv_d, ksize, ani_th, false, nullptr,
+                            [&](const hg_ani_hit *d_hits, size_t got, size_t, size_t) {
+                              return got ? tree_block(c, &g, d_hits, got, n, ani_th) : HG_OK;
+                            });
+  if (s != HG_OK) return s;
   return tree_end(c, &g, n, d_tree, n_edges, d_rep, d_cluster, n_clusters);
 }
 
@@ -360,16 +332,15 @@ extern "C" hg_status hg_cluster_tree(hg_ctx *c, const int16_t *hv, const int32_t
   if (done) return s;
   if (!hv || !norm2) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
-  const size_t hb = n * (size_t)hv_d * sizeof(int16_t), tb = (n - 1) * sizeof(hg_ani_hit);
-  if ((s = hg_ensure(c, c->w_hv, hb + 64)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_n2a, n * sizeof(int32_t) + 64)) != HG_OK) return s;
-  if ((s = hg_ensure(c, c->w_ani, 2 * n * sizeof(uint32_t) + tb + 64)) != HG_OK) return s;
-  HG_HIP(c, hipMemcpyAsync(c->w_hv.p, hv, hb, hipMemcpyHostToDevice, c->stream));
-  HG_HIP(c, hipMemcpyAsync(c->w_n2a.p, norm2, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  auto *d_rep = static_cast<uint32_t *>(c->w_ani.p), *d_cluster = d_rep + n;
+  const int16_t *d_hv;
+  const int32_t *d_norm2;
+  uint32_t *d_rep;
+  if ((s = hg_cluster_stage(c, hv, norm2, n, hv_d, 2 * n * sizeof(uint32_t) + (n - 1) * sizeof(hg_ani_hit), &d_hv, &d_norm2, &d_rep)) != HG_OK)
+    return s;
+  uint32_t *d_cluster = d_rep + n;
   auto *d_tree = reinterpret_cast<hg_ani_hit *>(d_cluster + n);
-  if ((s = hg_cluster_tree_dev(c, static_cast<const int16_t *>(c->w_hv.p), static_cast<const int32_t *>(c->w_n2a.p), n, hv_d, ksize,
-                               ani_th, d_tree, n - 1, n_edges, rep ? d_rep : nullptr, rep ? d_cluster : nullptr, n_clusters)) != HG_OK)
+  if ((s = hg_cluster_tree_dev(c, d_hv, d_norm2, n, hv_d, ksize, ani_th, d_tree, n - 1, n_edges, rep ? d_rep : nullptr,
+                               rep ? d_cluster : nullptr, n_clusters)) != HG_OK)
     return s;
   if (*n_edges) HG_HIP(c, hipMemcpyAsync(tree, d_tree, *n_edges * sizeof(hg_ani_hit), hipMemcpyDeviceToHost, c->stream));
   if (rep) {

@@ -113,9 +113,10 @@ struct hg_ctx {
   uint32_t i8_sig_r = 0, i8_sig_q = 0, i8_sig_d = 0;
   uint32_t i8_skip = 0;         // calls left that skip the i8 attempt after it was vetoed
   Buf w_sorthits; // keys / permutations / scratch of the device-side hit ordering
-  Buf w_clu_res;  // clustering: 16 result words ([0] cluster count, [1] error word of the hook kernel), never regrown
+  // clustering (hg_cluster*.hip; the declarations they share, the result words among them: hg_cluster_common.h)
+  Buf w_clu_res;  // 16 result words (HG_CLU_*), never regrown
   Buf w_clu;      // clustering: per-tile root counts of the dense-id scan
-  Buf w_clu_hits; // hg_cluster_dev / hg_cluster_greedy_dev: scratch hit list of one row block; hg_cluster_setcover_dev: the hits of all blocks
+  Buf w_clu_hits; // hit list of hg_cluster_row_blocks: one row block of the comparison (reuse), or the hits of all blocks (append: hg_cluster_setcover_dev)
   Buf w_grd;      // hg_cluster_greedy*: per-node state -- n 64-bit best words, then n status words, then n blocked marks
   uint64_t greedy_rounds = 0;  // rounds the last greedy call ran, summed over its blocks (hg_ctx_cluster_greedy_rounds)
   Buf w_setcover; // hg_cluster_setcover*: per-node state -- n 64-bit best words, n m1 words, n m2 words, then n status words, then n degrees
@@ -165,7 +166,7 @@ struct hg_ctx {
   // development / test hooks (hg_ctx_set_debug); never read from the environment
   std::string dbg_dist_tile, dbg_dist_path, dbg_ham_path, dbg_dist_order, dbg_kmer_input, dbg_hostfed, dbg_sketch_path;
   int dbg_sort_buckets = 0;
-  uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the scratch list of hg_cluster_dev starts with (0: its own size)
+  uint64_t dbg_cluster_hit_cap = 0;  // test hook "cluster_hit_cap": hits the list of hg_cluster_row_blocks starts with (0: its own size)
   uint64_t dbg_greedy_rounds = 0;  // test hook "greedy_rounds": rounds hg_cluster_greedy* queue per readback of the undecided count (0: its default)
   uint64_t dbg_setcover_rounds = 0;  // test hook "setcover_rounds": rounds hg_cluster_setcover* queue per readback of the undecided count (0: its default)
   uint64_t dbg_tree_rounds = 0;  // test hook "tree_rounds": rounds hg_cluster_tree* queue per readback of the count of selecting roots (0: its default)
@@ -186,32 +187,6 @@ hg_status hg_ensure_pinned(hg_ctx *ctx, size_t bytes);
 // the host polls that word (and the stream's own completion as a fallback) instead of paying a D2H copy command and a
 // stream synchronisation.  On return everything queued on the stream before the call has finished.  *out -> the n words.
 hg_status hg_publish_words(hg_ctx *ctx, uint32_t *d_words, uint32_t n, const uint32_t **out, uint32_t zero_n = 0);
-
-// ---- clustering: what hg_cluster.hip, hg_cluster_greedy.hip, hg_cluster_setcover.hip and hg_cluster_tree.hip share (device routines: hg_cluster_common.h) ----
-// The ctx's 16 clustering result words (w_clu_res): [0] cluster count, [1] error word (a hit with an index >= n); the
-// greedy and the set-cover resolution keep [2], [3] = nodes still undecided after the odd / even rounds and [4] = rounds
-// run behind them;
-// the tree resolution [5], [6] = roots that selected an edge in the odd / even rounds, [7] = edges of the forest being
-// written, and counts its rounds in [4] too.
-// All are zero between calls: the call that reads them back clears them behind the copy (hg_publish_words).
-enum : uint32_t {
-  HG_CLU_COUNT = 0,
-  HG_CLU_ERR = 1,
-  HG_CLU_UNDECIDED = 2,
-  HG_CLU_ROUNDS = 4,
-  HG_CLU_SELECTING = 5,
-  HG_CLU_EDGES = 7,
-  HG_CLU_WORDS = 8
-};
-hg_status hg_cluster_res(hg_ctx *ctx, uint32_t **out);
-// rep[] (trees of any depth) -> rep[i] = root, d_cluster = dense ids of the roots in index order, res[HG_CLU_COUNT] = their
-// number: the compress / scan / root-id / member-id launches of hg_cluster_finish_dev, stream-ordered, nothing read back.
-hg_status hg_cluster_queue_ids(hg_ctx *ctx, uint32_t *d_rep, size_t n, uint32_t *d_cluster, uint32_t *res);
-
-// The order of a single-linkage tree (hg_hits.hip's stable radix passes: qry_idx ascending, then ref_idx ascending, then
-// ANI descending by its order-preserving key): d_in[0, n) -> d_out[0, n), n < 2^31, every index < n_nodes, stream-ordered.
-// d_out != d_in.
-hg_status hg_sort_tree_edges_dev(hg_ctx *ctx, const hg_ani_hit *d_in, size_t n, size_t n_nodes, hg_ani_hit *d_out);
 
 // RAII bracket: records events around the launches issued while it is alive (no-op unless
 // timing is enabled).
