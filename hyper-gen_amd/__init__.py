@@ -24,6 +24,8 @@ CLI_PATH = os.path.join(_HERE, "hyper-gen")
 LAYOUT_SCALAR, LAYOUT_AVX2 = 0, 1
 GATHER_PEER, GATHER_RCCL = 0, 1
 ANI_MASH, ANI_CONTAINMENT, ANI_MAX_CONTAINMENT = 0, 1, 2  # hg_ctx_set_ani_metric
+PAIRS_MASH, PAIRS_CONTAINMENT, PAIRS_MAX_CONTAINMENT, PAIRS_CONTAINMENT_REF = 1, 2, 4, 8  # columns of hg_ani_pairs (HG_PAIRS_*)
+PAIRS_EMPTY = 0xFFFFFFFF  # ref_idx of an empty slot in a pair list
 NORM_ACGT, NORM_U2T = 0, 1
 (OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_OOM, ERR_CAPACITY, ERR_UNSUPPORTED, ERR_IO,
  ERR_INEXACT) = range(9)
@@ -92,6 +94,7 @@ EXPORTS = [
     "hg_cluster_tree_hits_dev", "hg_cluster_tree_dev", "hg_cluster_tree", "hg_ctx_cluster_tree_rounds",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
+    "hg_ani_pairs_dev", "hg_ani_pairs",
 ]
 SEARCH_TOPK_MAX = 64  # HG_SEARCH_TOPK_MAX
 
@@ -170,6 +173,8 @@ def lib():
                                       vp, vp, vp]),
         "hg_dist_full": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp]),
         "hg_dist_full_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp]),
+        "hg_ani_pairs_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, C.c_uint32, vp, vp]),
+        "hg_ani_pairs": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, C.c_uint32, vp, vp]),
         "hg_dist": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_int, C.c_float,
                               vp, sz, C.POINTER(sz)]),
         "hg_dist_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_int,
@@ -620,6 +625,33 @@ class Context:
         self._ck(lib().hg_search_topk(self._h, _ptr(r) if r.size else None, _ptr(rn) if rn.size else None, r.shape[0], _ptr(q),
                                       _ptr(qn), q.shape[0], q.shape[1], ksize, C.c_float(ani_th), k, _ptr(out), _ptr(cnt)))
         return out, cnt
+
+    def ani_pairs_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, d_pairs, n_pairs, columns, d_ani, d_dot=None):
+        """hg_ani_pairs_dev: the `columns` (PAIRS_* mask) of the n_pairs listed pairs into d_ani (n_pairs x popcount(columns)
+        floats), their wrapped i32 dots into d_dot if given; device pointers, results final on return."""
+        self._ck(lib().hg_ani_pairs_dev(self._h, _ptr(d_ref), _ptr(d_rn), R, _ptr(d_qry), _ptr(d_qn), Q, hv_d, ksize,
+                                        _ptr(d_pairs or 0), n_pairs, columns, _ptr(d_ani or 0), _ptr(d_dot or 0)))  # (None / 0: NULL)
+
+    def ani_pairs(self, ref_hv, ref_n2, qry_hv, qry_n2, pairs, columns, ksize=21, want_dot=False):
+        """hg_ani_pairs on host sketches.  pairs: an ANI_HIT_DTYPE array (its `ani` is ignored) or an (n, 2) integer array of
+        (ref_idx, qry_idx).  Returns the (n, popcount(columns)) float32 array, with want_dot (array, int32 dots)."""
+        r = np.ascontiguousarray(ref_hv, np.int16)
+        q = r if qry_hv is ref_hv else np.ascontiguousarray(qry_hv, np.int16)
+        rn = np.ascontiguousarray(ref_n2, np.int32)
+        qn = rn if qry_n2 is ref_n2 else np.ascontiguousarray(qry_n2, np.int32)
+        pairs = np.asarray(pairs)
+        if pairs.dtype != ANI_HIT_DTYPE:
+            ij = pairs.reshape(-1, 2)
+            pairs = np.zeros(ij.shape[0], ANI_HIT_DTYPE)
+            pairs["ref_idx"], pairs["qry_idx"] = ij[:, 0], ij[:, 1]
+        pairs = np.ascontiguousarray(pairs.ravel())
+        n = pairs.size
+        ani = np.zeros((n, bin(columns).count("1")), np.float32)
+        dot = np.zeros(n, np.int32) if want_dot else None
+        self._ck(lib().hg_ani_pairs(self._h, _ptr(r), _ptr(rn), r.shape[0], _ptr(q), _ptr(qn), q.shape[0], r.shape[1], ksize,
+                                    _ptr(pairs) if n else None, n, columns, _ptr(ani) if ani.size else None,
+                                    _ptr(dot) if want_dot and n else None))
+        return (ani, dot) if want_dot else ani
 
     def dist_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, symmetric, ani_th, d_out, cap):
         n = C.c_size_t(0)

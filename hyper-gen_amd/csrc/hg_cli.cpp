@@ -87,6 +87,10 @@ struct Cli {
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
   bool tree_given = false, levels_given = false;
+  std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
+  bool columns_given = false;
+  std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
+  bool pairs_given = false;
 };
 
 Cli parse(int argc, char **argv) {
@@ -137,7 +141,15 @@ Cli parse(int argc, char **argv) {
                 "         at any threshold >= -a it gives that threshold's clusters, its order is the merge order),\n"
                 "         --levels L1,L2,... (cluster --linkage single: 1 to 8 further thresholds, ascending, above -a, all from\n"
                 "         one comparison at -a; every line of -o becomes file, then for -a and each level the cluster id and\n"
-                "         the file of the cluster's first member)\n");
+                "         the file of the cluster's first member),\n"
+                "         --columns LIST (dist: a comma list out of mash, containment, containment_ref, max_containment; every\n"
+                "         line gets one further field per name, in the order listed -- the pair's ANI under that metric, whatever\n"
+                "         --ani_metric selected the lines; containment_ref = the share of the reference's hashes found in the\n"
+                "         query; runs on the first visible GPU),\n"
+                "         --pairs FILE (dist: evaluate the pairs FILE lists, ref_name<TAB>qry_name[<TAB>anything] per line, names\n"
+                "         as -r and -q carry them -- a dist TSV can be fed back; one line per listed pair in the order of the\n"
+                "         list, ANI under --ani_metric, then the --columns fields; -a is not applied; runs on the first\n"
+                "         visible GPU)\n");
     std::exit(0);
   }
   if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
@@ -147,7 +159,7 @@ Cli parse(int argc, char **argv) {
       {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
       {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
       {"min_count", '\x02'}, {"search_path", '\x03'}, {"linkage", '\x04'}, {"order", '\x05'}, {"tree", '\x06'},
-      {"levels", '\x07'}};
+      {"levels", '\x07'}, {"columns", '\x08'}, {"pairs", '\x0b'}};
   for (int i = 2; i < argc; ++i) {
     std::string a = argv[i], val;
     char key = 0;
@@ -246,6 +258,27 @@ Cli parse(int argc, char **argv) {
         }
         break;
       }
+      case '\x08': {  // (long form only) dist only (extension)
+        static const std::pair<const char *, uint32_t> names[] = {{"mash", HG_PAIRS_MASH}, {"containment", HG_PAIRS_CONTAINMENT},
+                                                                  {"max_containment", HG_PAIRS_MAX_CONTAINMENT}, {"containment_ref", HG_PAIRS_CONTAINMENT_REF}};
+        c.columns.clear(), c.columns_given = true;
+        for (size_t b = 0; b <= val.size();) {
+          const size_t e = std::min(val.find(',', b), val.size());
+          const std::string item = val.substr(b, e - b);
+          uint32_t bit = 0;
+          for (const auto &nm : names)
+            if (item == nm.first) bit = nm.second;
+          if (!bit) die("invalid value '" + val + "' for '--columns' (a comma list out of mash, containment, containment_ref, max_containment)");
+          if (std::find(c.columns.begin(), c.columns.end(), bit) != c.columns.end()) die("invalid value '" + val + "' for '--columns': '" + item + "' is listed twice");
+          c.columns.push_back(bit);
+          b = e + 1;
+        }
+        break;
+      }
+      case '\x0b':  // (long form only) dist only (extension)
+        if (val.empty()) die("invalid value '' for '--pairs' (a file name)");
+        c.pairs_file = val, c.pairs_given = true;
+        break;
       case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
         if (val == "naive") c.pack_naive = true;
         else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
@@ -269,6 +302,12 @@ Cli parse(int argc, char **argv) {
     if (c.greedy) die(f + " needs cluster --linkage single: greedy clusters are not nested and have no tree");
     if (c.setcover) die(f + " needs cluster --linkage single: set-cover clusters are not nested and have no tree");
     if (c.shards) die(f + " is not supported with --shards: cluster runs on the first visible GPU");
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (!(k ? c.pairs_given : c.columns_given)) continue;
+    const std::string f = k ? "--pairs" : "--columns";
+    if (c.mode != "dist") die(f + " is not supported by " + c.mode + (k ? ": it names the pairs dist evaluates" : ": it adds a pair's other metrics to the lines of dist"));
+    if (c.shards) die(f + " is not supported with --shards: dist with --columns or --pairs runs on the first visible GPU");
   }
   if (c.levels_given && !(c.levels[0] > (c.ani_th_given ? c.ani_th : 95.0f)))
     die("invalid value for '--levels': every level must be above -a, the threshold the tree is built at");
@@ -672,6 +711,41 @@ size_t all_hits(hg_multi *multi, const Loaded &R, const DevSet &dR, const Loaded
   return found;
 }
 
+// --pairs FILE: one pair per non-empty line, "ref_name<TAB>qry_name[<TAB>anything]" -- the names are the file_str of -r / -q
+// (a dist TSV can be fed back); with a name that appears twice the first sketch wins.  An unknown name is fatal.
+std::vector<hg_ani_hit> read_pair_list(const std::string &path, const Loaded &R, const Loaded &Q) {
+  std::FILE *f = std::fopen(path.c_str(), "rb");
+  if (!f) die("Opening pair list failed: " + path);
+  std::string text;
+  char chunk[1 << 16];
+  for (size_t got; (got = std::fread(chunk, 1, sizeof chunk, f)) > 0;) text.append(chunk, got);
+  std::fclose(f);
+  std::map<std::string, uint32_t> by_r, by_q;
+  for (size_t i = 0; i < R.n; ++i) by_r.emplace(hg_sketch_file_get(R.f, i)->file_str, (uint32_t)i);  // (emplace keeps the first)
+  for (size_t i = 0; i < Q.n; ++i) by_q.emplace(hg_sketch_file_get(Q.f, i)->file_str, (uint32_t)i);
+  std::vector<hg_ani_hit> list;
+  size_t line_no = 0;
+  for (size_t b = 0; b < text.size();) {
+    const size_t e = std::min(text.find('\n', b), text.size());
+    ++line_no;
+    if (e > b) {
+      const std::string where = "--pairs " + path + ": line " + std::to_string(line_no) + ": ";
+      const size_t t1 = std::min(text.find('\t', b), e);
+      if (t1 == e) die(where + "expected ref_name<TAB>qry_name");
+      const size_t t2 = std::min(text.find('\t', t1 + 1), e);
+      const std::string rn = text.substr(b, t1 - b), qn = text.substr(t1 + 1, t2 - t1 - 1);
+      const auto ir = by_r.find(rn);
+      if (ir == by_r.end()) die(where + "unknown reference name '" + rn + "'");
+      const auto iq = by_q.find(qn);
+      if (iq == by_q.end()) die(where + "unknown query name '" + qn + "'");
+      list.push_back(hg_ani_hit{ir->second, iq->second, 0.0f});
+    }
+    b = e + 1;
+  }
+  if (list.size() > 0xFFFFFFFFull) die("--pairs " + path + ": more than 2^32 - 1 pairs");
+  return list;
+}
+
 int run_dist(const Cli &c) {
   if (c.path_r == "1" || c.path_q == "1" || c.out.empty())
     die("the following required arguments were not provided: --path_r --path_q --out");
@@ -679,12 +753,19 @@ int run_dist(const Cli &c) {
   const bool sym = c.path_r == c.path_q;  // src/dist.rs:13
   // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
   const bool sym_full = sym && c.ani_metric == HG_ANI_CONTAINMENT;
+  // --columns / --pairs: the pairs' further metrics come from one hg_ani_pairs_dev call on the device list, on one GPU
+  const bool one_gpu = c.columns_given || c.pairs_given;
+  const uint32_t metric_bit = c.ani_metric == HG_ANI_MASH ? HG_PAIRS_MASH : c.ani_metric == HG_ANI_CONTAINMENT ? HG_PAIRS_CONTAINMENT : HG_PAIRS_MAX_CONTAINMENT;
+  uint32_t mask = c.pairs_given ? metric_bit : 0u;  // (--pairs: the ANI field itself is a column of the call)
+  for (const uint32_t b : c.columns) mask |= b;
+  const size_t n_cols = (size_t)__builtin_popcount(mask);
+  auto col_at = [&](uint32_t bit) { return (size_t)__builtin_popcount(mask & (bit - 1)); };  // a column's place in a pair's values
   Loaded R, Qs;
   double tp = now_s();
   hg_multi *multi = nullptr;
   std::thread opener([&] {  // the HIP runtime comes up (~0.2 s) while the sketch files are read and decompressed
     const double td = now_s();
-    multi = open_all_devices(c.shards);
+    multi = one_gpu ? open_all_devices(1) : open_all_devices(c.shards);
     ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
     debugf("devices opened in %.1f ms", (now_s() - td) * 1e3);
   });
@@ -708,14 +789,52 @@ int run_dist(const Cli &c) {
   tp = now_s();
   const size_t total = sym_full ? R.n * (R.n - 1) : (sym ? R.n * (Q.n - 1) / 2 : R.n * Q.n);
   HitBuf hits;
-  // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
-  // sort of up to 10^6..10^8 triples on one host core)
-  size_t found = sym_full ? all_hits(multi, R, dR, &R, &dR, c.ani_th, true, hits)
-                         : all_hits(multi, R, dR, sym ? nullptr : &Qs, sym ? nullptr : &dQ, c.ani_th, true, hits);
-  if (sym_full) {  // (the pairs i = j are not written: the order of the rest stays)
+  std::vector<float> cols;  // --columns / --pairs: n_cols values per line, in ascending order of the column bits
+  void *d_list = nullptr;   // ... and the device list they are computed on
+  size_t found = 0;
+  if (c.pairs_given) {
+    const std::vector<hg_ani_hit> list = read_pair_list(c.pairs_file, R, Q);
+    found = list.size();
+    hits.resize(found);
+    if (found) {
+      std::memcpy(hits.p, list.data(), found * sizeof(hg_ani_hit));
+      hg_ctx *ctx = hg_multi_ctx(multi, 0);
+      ck(ctx, hg_dev_alloc(ctx, found * sizeof(hg_ani_hit), &d_list), "alloc");
+      ck(ctx, hg_copy_h2d(ctx, d_list, hits.p, found * sizeof(hg_ani_hit)), "upload");
+    }
+  } else {
+    // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
+    // sort of up to 10^6..10^8 triples on one host core)
+    found = sym_full ? all_hits(multi, R, dR, &R, &dR, c.ani_th, true, hits, one_gpu ? &d_list : nullptr)
+                     : all_hits(multi, R, dR, sym ? nullptr : &Qs, sym ? nullptr : &dQ, c.ani_th, true, hits, one_gpu ? &d_list : nullptr);
+  }
+  if (one_gpu) {  // the columns of the ordered device list, before the download
+    hg_ctx *ctx = hg_multi_ctx(multi, 0);
+    const DevSet &dq = sym ? dR : dQ;
+    if (found) {
+      void *d_cols = nullptr;
+      ck(ctx, hg_dev_alloc(ctx, found * n_cols * sizeof(float), &d_cols), "alloc");
+      ck(ctx, hg_ani_pairs_dev(ctx, dR.hv[0], dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize,
+                               static_cast<const hg_ani_hit *>(d_list), found, mask, static_cast<float *>(d_cols), nullptr), "ani_pairs");
+      cols.resize(found * n_cols);
+      ck(ctx, hg_copy_d2h(ctx, cols.data(), d_cols, found * n_cols * sizeof(float)), "download");
+      ck(ctx, hg_dev_free(ctx, d_cols), "free");
+      if (!c.pairs_given) {
+        hits.resize(found);
+        ck(ctx, hg_copy_d2h(ctx, hits.p, d_list, found * sizeof(hg_ani_hit)), "download");
+      }
+    }
+    if (d_list) ck(ctx, hg_dev_free(ctx, d_list), "free");
+    if (c.pairs_given)
+      for (size_t i = 0; i < found; ++i) hits.p[i].ani = cols[i * n_cols + col_at(metric_bit)];
+  }
+  if (sym_full && !c.pairs_given) {  // (the pairs i = j are not written: the order of the rest stays)
     size_t w = 0;
     for (size_t i = 0; i < found; ++i)
-      if (hits.p[i].ref_idx != hits.p[i].qry_idx) hits.p[w++] = hits.p[i];
+      if (hits.p[i].ref_idx != hits.p[i].qry_idx) {
+        if (n_cols) std::copy_n(cols.begin() + i * n_cols, n_cols, cols.begin() + w * n_cols);
+        hits.p[w++] = hits.p[i];
+      }
     found = w;
   }
   release(multi, dR), release(multi, dQ);
@@ -732,7 +851,7 @@ int run_dist(const Cli &c) {
     auto fmt = [&](size_t t) {
       const size_t lo = found * t / FT, hi = found * (t + 1) / FT;
       size_t need = 0;
-      for (size_t i = lo; i < hi; ++i) need += (size_t)len_r[hits.p[i].ref_idx] + len_q[hits.p[i].qry_idx] + 10;
+      for (size_t i = lo; i < hi; ++i) need += (size_t)len_r[hits.p[i].ref_idx] + len_q[hits.p[i].qry_idx] + 10 + 10 * c.columns.size();
       std::string &o = part[t];
       o.resize(need);
       char *w = &o[0];
@@ -744,6 +863,7 @@ int run_dist(const Cli &c) {
         std::memcpy(w, hg_sketch_file_get(Q.f, h.qry_idx)->file_str, len_q[h.qry_idx]);
         w += len_q[h.qry_idx];
         w += put_ani(w, h.ani);
+        for (const uint32_t b : c.columns) --w, w += put_ani(w, cols[i * n_cols + col_at(b)]);  // (over the line's '\n')
       }
       o.resize((size_t)(w - &o[0]));
     };
@@ -784,7 +904,10 @@ int run_dist(const Cli &c) {
   debugf("TSV written in %.1f ms", (now_s() - tp) * 1e3);
   char buf[512];
   const double perc = total ? 100.0 * found / total : 0.0;
-  if (perc < 5.0) {
+  if (c.pairs_given) {
+    std::snprintf(buf, sizeof buf, "Output %zu listed ANIs to file %s", found, c.out.c_str());
+    logline("INFO", buf);
+  } else if (perc < 5.0) {
     std::snprintf(buf, sizeof buf, "Output ANIs with threshold %.1f are too divergent: %zu of %zu (%.2f%%) ANIs are reported",
                   c.ani_th, found, total, perc);
     logline("WARN", buf);

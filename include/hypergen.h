@@ -292,7 +292,7 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev} and hg_cluster_tree{,_dev} accept HG_ANI_MASH and
  * HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
  * hg_cluster_tree_hits_dev (they take hits), hg_dist_prep_ops_dev, the
- * sort / top-k calls and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
+ * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
 #define HG_ANI_MAX_CONTAINMENT 2
@@ -385,6 +385,39 @@ hg_status hg_sort_ani_hits_staged(hg_ctx *ctx, hg_ani_hit *hits, size_t n, size_
  * d_counts[q] = number of valid entries (<= k).  Device pointers; stream-ordered. */
 hg_status hg_topk_per_query_dev(hg_ctx *ctx, const hg_ani_hit *d_hits, size_t n, size_t Q, uint32_t k,
                                 hg_ani_hit *d_out, uint32_t *d_counts);
+
+/* ANI of listed pairs (no reference counterpart): every metric of pair (ref_idx, qry_idx) of a list, from one exact dot per
+ * pair -- without the R x Q comparison.  ani_pairs_kernel: one wave per pair streams both rows (16-byte loads when
+ * hv_d % 8 == 0, 2-byte loads otherwise; nothing behind a row's end is read), forms the wrapping i32 dot like
+ * dist_skinny_kernel and finishes it with the formulas of hg_ctx_set_ani_metric.
+ *   d_pairs : n_pairs records hg_ani_hit; the `ani` field is ignored, so the output of hg_dist_dev, hg_sort_ani_hits_dev,
+ *             hg_topk_per_query_dev, hg_search_topk* and hg_cluster_tree* goes in as it lies.  Duplicates, any order and
+ *             ref_idx == qry_idx with identical buffers are allowed.  A record with ref_idx == HG_PAIRS_EMPTY is an empty slot
+ *             (the top-k layout's): its floats and its dot are 0.  Any other record with ref_idx >= R or qry_idx >= Q makes the
+ *             call HG_ERR_INVALID (its rows are not read, the outputs' contents are unspecified, the next call starts clean).
+ *   columns : a mask of HG_PAIRS_*, < 16.  d_ani holds n_pairs x popcount(columns) floats, pair-major, a pair's values in
+ *             ascending order of the column bits.  The value of (r, q) under a column is, bit for bit, what hg_dist_full_dev
+ *             writes at [r, q] under the corresponding ctx metric; under HG_PAIRS_CONTAINMENT_REF what it writes at [q, r] with
+ *             the two sets exchanged under HG_ANI_CONTAINMENT.  The call does not depend on hg_ctx_set_ani_metric.
+ *   d_dot   : NULL or n_pairs wrapped i32 dots.  columns == 0 is allowed with d_dot (d_ani may then be NULL); columns == 0
+ *             without d_dot and columns >= 16 are HG_ERR_INVALID.
+ * n_pairs == 0: HG_OK, nothing is written; n_pairs >= 2^32: HG_ERR_UNSUPPORTED; R, Q, hv_d (1..65536) and ksize as for
+ * hg_dist_dev; NULL d_pairs, row or norm pointers with n_pairs > 0: HG_ERR_INVALID.  d_ani and d_dot must not overlap d_pairs.
+ * Inputs are read in stream order on the ctx's stream; results are final on return, as for hg_dist_dev (the error word comes
+ * back the way its hit count does).  With timing on the launch counts under HG_T_DIST.
+ *   hg_ani_pairs : host arrays in and out, staged through the ctx like hg_dist. */
+#define HG_PAIRS_MASH 1u            /* 2 / (1 / J + 1)       = HG_ANI_MASH            */
+#define HG_PAIRS_CONTAINMENT 2u     /* dot / nq              = HG_ANI_CONTAINMENT     */
+#define HG_PAIRS_MAX_CONTAINMENT 4u /* dot / min(nr, nq)     = HG_ANI_MAX_CONTAINMENT */
+#define HG_PAIRS_CONTAINMENT_REF 8u /* dot / nr: the share of the REFERENCE's hashes found in the query
+                                       (HG_ANI_CONTAINMENT with the two sides exchanged)              */
+#define HG_PAIRS_EMPTY 0xFFFFFFFFu  /* ref_idx of an empty slot (the top-k layout's)                   */
+hg_status hg_ani_pairs_dev(hg_ctx *ctx, const int16_t *d_ref_hv, const int32_t *d_ref_norm2, size_t R,
+                           const int16_t *d_qry_hv, const int32_t *d_qry_norm2, size_t Q, uint32_t hv_d, uint32_t ksize,
+                           const hg_ani_hit *d_pairs, size_t n_pairs, uint32_t columns, float *d_ani, int32_t *d_dot);
+hg_status hg_ani_pairs(hg_ctx *ctx, const int16_t *ref_hv, const int32_t *ref_norm2, size_t R, const int16_t *qry_hv,
+                       const int32_t *qry_norm2, size_t Q, uint32_t hv_d, uint32_t ksize, const hg_ani_hit *pairs,
+                       size_t n_pairs, uint32_t columns, float *ani, int32_t *dot);
 
 /* search: exact top-k per query in bounded memory (no reference counterpart, like hg_topk_per_query_dev).  The same result
  * as hg_dist_dev(ani_th) followed by hg_topk_per_query_dev -- per query the k references with the highest ANI among those with
