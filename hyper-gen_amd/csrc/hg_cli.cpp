@@ -7,13 +7,13 @@
 // reproduced (cpu: needletail, u/U -> T; gpu: src/cuda_kernel.cu, ACGTacgt only).
 #include <fcntl.h>
 #include <glob.h>
-#include <unistd.h>
 #include <sched.h>
 #include <unistd.h>
 #include <sys/stat.h>
 
 #include <algorithm>
 #include <atomic>
+#include <bitset>
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
@@ -23,10 +23,12 @@
 #include <cstring>
 #include <ctime>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/hypergen.h"
@@ -67,31 +69,146 @@ void debugf(const char *fmt, ...) {
   _exit(2);  // not exit(): reader threads, or a thread that is bringing the HIP runtime up, may still be running
 }
 
+enum class Linkage { single, greedy, setcover };
+enum class SearchPath { automatic, hits, topk };  // automatic: topk whenever top_n <= HG_SEARCH_TOPK_MAX, else the hit list
+enum : unsigned { SKETCH = 1, DIST = 2, SEARCH = 4, CLUSTER = 8, ANY = 15 };  // subcommands, as bits of Option::modes
+
 struct Cli {
   std::string mode, path = "1", path_r = "1", path_q = "1", out, method = "t1ha2", device = "cpu";
+  unsigned mode_bit = 0;
   bool pack_naive = false;  // --pack_layout naive: the payload layout of reference hosts without AVX2 (src/hd.rs:158-166)
   unsigned shards = 0;      // --shards N (dist / search; testing aid): N shards dealt round the visible devices instead of one each
   unsigned threads = 16, ksize = 21, top_n = 1;
   bool canonical = true;
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
-  float quant_scale = 1.0f, ani_th = 85.0f;
-  bool ani_th_given = false;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
+  float quant_scale = 1.0f, ani_th = 85.0f;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
-  bool min_count_given = false;
-  int search_path = 0;  // --search_path auto|hits|topk (search; testing aid): 0 = topk whenever top_n <= HG_SEARCH_TOPK_MAX, 1 = the hit list, 2 = topk
-  bool search_path_given = false;
+  SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
-  bool greedy = false, linkage_given = false;     // --linkage single|greedy|setcover (cluster)
-  bool setcover = false;
-  bool order_size = false, order_given = false;   // --order file|size (cluster --linkage greedy)
+  Linkage linkage = Linkage::single;  // --linkage single|greedy|setcover (cluster)
+  bool order_size = false;     // --order file|size (cluster --linkage greedy)
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
-  bool tree_given = false, levels_given = false;
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
-  bool columns_given = false;
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
-  bool pairs_given = false;
+  std::bitset<32> given;          // which options the command line carried, by row of `options`
 };
+
+// One option of the command line as it was typed, and the ways its value is read
+struct Arg {
+  std::string flag, val;  // "--thread=4", "-t4" or "-t", and "4"
+  const char *name;       // the option's long name
+  [[noreturn]] void bad(const std::string &tail = "") const { die("invalid value '" + val + "' for '--" + name + "'" + tail); }
+  unsigned long long uint(unsigned long long max, unsigned long long min = 0) const {
+    char *e = nullptr;
+    const unsigned long long v = std::strtoull(val.c_str(), &e, 10);
+    if (val.empty() || *e || v > max || v < min) die("invalid value '" + val + "' for '" + flag + "'");
+    return v;
+  }
+  // the place of the value in a fixed list; the error names the list: " (a | b | c)"
+  size_t choice(std::initializer_list<const char *> names, bool list_them = true) const {
+    std::string list;
+    for (const char *const *n = names.begin(); n != names.end(); ++n) {
+      if (val == *n) return (size_t)(n - names.begin());
+      list += std::string(n == names.begin() ? " (" : " | ") + *n;
+    }
+    bad(list_them ? list + ")" : "");
+  }
+  const std::string &file() const {
+    if (val.empty()) bad(" (a file name)");
+    return val;
+  }
+  std::vector<std::string> items() const {  // of a comma list, empty ones included
+    std::vector<std::string> out;
+    for (size_t b = 0, e; b <= val.size(); b = e + 1) out.push_back(val.substr(b, (e = std::min(val.find(',', b), val.size())) - b));
+    return out;
+  }
+};
+
+void take_levels(Cli &c, const Arg &a) {
+  c.levels.clear();
+  for (const std::string &item : a.items()) {
+    char *end = nullptr;
+    const float v = std::strtof(item.c_str(), &end);
+    if (item.empty() || *end || !(v == v) || item.find_first_not_of("0123456789.+-eE") != std::string::npos)
+      a.bad(" (1 to 8 ANI thresholds, comma-separated, ascending)");
+    if (c.levels.size() == 8) a.bad(": at most 8 levels");
+    if (!c.levels.empty() && !(v > c.levels.back())) a.bad(": the levels must be strictly ascending");
+    c.levels.push_back(v);
+  }
+}
+void take_columns(Cli &c, const Arg &a) {
+  static const std::pair<const char *, uint32_t> names[] = {{"mash", HG_PAIRS_MASH}, {"containment", HG_PAIRS_CONTAINMENT},
+                                                            {"max_containment", HG_PAIRS_MAX_CONTAINMENT}, {"containment_ref", HG_PAIRS_CONTAINMENT_REF}};
+  c.columns.clear();
+  for (const std::string &item : a.items()) {
+    uint32_t bit = 0;
+    for (const auto &nm : names)
+      if (item == nm.first) bit = nm.second;
+    if (!bit) a.bad(" (a comma list out of mash, containment, containment_ref, max_containment)");
+    if (std::find(c.columns.begin(), c.columns.end(), bit) != c.columns.end()) a.bad(": '" + item + "' is listed twice");
+    c.columns.push_back(bit);
+  }
+}
+
+// Every option: long name, short letter (0: none), how its value is taken, the subcommands that accept it, why the others do
+// not ("--name is not supported by <mode>: <why>") and why it does not go with --shards (nullptr: it does).  A subcommand that
+// merely ignores an option accepts it, as the reference's one flat argument struct does (src/utils.rs:42-162).  The restricted
+// rows stand in the order their faults are reported in.
+struct Option {
+  const char *name;
+  char letter;
+  void (*take)(Cli &, const Arg &);
+  unsigned modes = ANY;
+  const char *why = nullptr, *why_shards = nullptr;
+};
+const char *const ONE_GPU_CLUSTER = "cluster runs on the first visible GPU";
+const char *const ONE_GPU_DIST = "dist with --columns or --pairs runs on the first visible GPU";
+const Option options[] = {
+    {"path", 'p', [](Cli &c, const Arg &a) { c.path = a.val; }},
+    {"path_r", 'r', [](Cli &c, const Arg &a) { c.path_r = a.val; }},
+    {"path_q", 'q', [](Cli &c, const Arg &a) { c.path_q = a.val; }},
+    {"out", 'o', [](Cli &c, const Arg &a) { c.out = a.val; }},
+    {"thread", 't', [](Cli &c, const Arg &a) { c.threads = (unsigned)a.uint(255); }},  // u8
+    {"sketch_method", 'm', [](Cli &c, const Arg &a) { c.method = a.val; }},
+    {"canonical", 'C', [](Cli &c, const Arg &a) { c.canonical = a.choice({"false", "true"}, false) == 1; }},
+    {"ksize", 'k', [](Cli &c, const Arg &a) { c.ksize = (unsigned)a.uint(255); }},  // u8
+    {"seed", 'S', [](Cli &c, const Arg &a) { c.seed = a.uint(~0ull); }},
+    {"scaled", 's', [](Cli &c, const Arg &a) { c.scaled = a.uint(~0ull); }},
+    {"hv_d", 'd', [](Cli &c, const Arg &a) { c.hv_d = a.uint(~0ull); }},
+    {"quant_scale", 'Q', [](Cli &c, const Arg &a) { c.quant_scale = std::strtof(a.val.c_str(), nullptr); }},
+    {"ani_th", 'a', [](Cli &c, const Arg &a) { c.ani_th = std::strtof(a.val.c_str(), nullptr); }},
+    {"device", 'D', [](Cli &c, const Arg &a) { c.device = a.val; }},
+    {"top_n", 'n', [](Cli &c, const Arg &a) { c.top_n = (unsigned)a.uint(1u << 20); }},  // (extension: the reference's search is a stub)
+    // (extension) which of the reference's two payload layouts sketch writes
+    {"pack_layout", 'L', [](Cli &c, const Arg &a) { c.pack_naive = a.val != "bitpacker8x" && a.choice({"avx2", "naive"}) == 1; }},
+    {"ani_metric", 0, [](Cli &c, const Arg &a) {
+       static const int metrics[] = {HG_ANI_MASH, HG_ANI_CONTAINMENT, HG_ANI_MAX_CONTAINMENT};
+       c.ani_metric = metrics[a.choice({"mash", "containment", "max_containment"})];
+     }},
+    {"order", 0, [](Cli &c, const Arg &a) { c.order_size = a.choice({"file", "size"}) == 1; }},
+    {"search_path", 0, [](Cli &c, const Arg &a) { c.search_path = SearchPath(a.choice({"auto", "hits", "topk"})); }, SEARCH,
+     "it chooses how search selects its results"},
+    {"linkage", 0, [](Cli &c, const Arg &a) { c.linkage = Linkage(a.choice({"single", "greedy", "setcover"})); }, CLUSTER,
+     "it chooses how cluster forms its clusters"},
+    {"tree", 0, [](Cli &c, const Arg &a) { c.tree_out = a.file(); }, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
+    {"levels", 0, take_levels, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
+    {"columns", 0, take_columns, DIST, "it adds a pair's other metrics to the lines of dist", ONE_GPU_DIST},
+    {"pairs", 0, [](Cli &c, const Arg &a) { c.pairs_file = a.file(); }, DIST, "it names the pairs dist evaluates", ONE_GPU_DIST},
+    {"min_count", 0, [](Cli &c, const Arg &a) { c.min_count = (unsigned)a.uint(0xFFFFFFFFull, 1); }, SKETCH,
+     "the filter needs the k-mer counts, which a sketch no longer has"},
+    // (testing aid: the several-GPU path on fewer GPUs)
+    {"shards", 'G', [](Cli &c, const Arg &a) { c.shards = (unsigned)a.uint(64); }, SKETCH | DIST | SEARCH, "it runs on the first visible GPU"},
+};
+const size_t N_OPTIONS = sizeof options / sizeof options[0];
+static_assert(N_OPTIONS <= 32, "Cli::given has 32 bits");
+
+size_t option_row(const char *name) {
+  for (size_t k = 0; k < N_OPTIONS; ++k)
+    if (!std::strcmp(options[k].name, name)) return k;
+  die(std::string("internal: no option --") + name);
+}
+bool given(const Cli &c, const char *name) { return c.given[option_row(name)]; }
 
 Cli parse(int argc, char **argv) {
   if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
@@ -152,166 +269,60 @@ Cli parse(int argc, char **argv) {
                 "         visible GPU)\n");
     std::exit(0);
   }
-  if (c.mode != "sketch" && c.mode != "dist" && c.mode != "search" && c.mode != "cluster") die("unknown subcommand '" + c.mode + "'");
-  if (c.mode != "sketch") c.method = "fracminhash";
-  static const std::map<std::string, char> longs = {
-      {"path", 'p'}, {"path_r", 'r'}, {"path_q", 'q'}, {"out", 'o'}, {"thread", 't'}, {"sketch_method", 'm'},
-      {"canonical", 'C'}, {"ksize", 'k'}, {"seed", 'S'}, {"scaled", 's'}, {"hv_d", 'd'}, {"quant_scale", 'Q'},
-      {"ani_th", 'a'}, {"device", 'D'}, {"top_n", 'n'}, {"pack_layout", 'L'}, {"shards", 'G'}, {"ani_metric", '\x01'},
-      {"min_count", '\x02'}, {"search_path", '\x03'}, {"linkage", '\x04'}, {"order", '\x05'}, {"tree", '\x06'},
-      {"levels", '\x07'}, {"columns", '\x08'}, {"pairs", '\x0b'}};
+  static const char *const modes[] = {"sketch", "dist", "search", "cluster"};
+  for (unsigned k = 0; k < 4; ++k)
+    if (c.mode == modes[k]) c.mode_bit = 1u << k;
+  if (!c.mode_bit) die("unknown subcommand '" + c.mode + "'");
+  if (c.mode_bit != SKETCH) c.method = "fracminhash";
+  if (c.mode_bit == CLUSTER) c.ani_th = 95.0f;
   for (int i = 2; i < argc; ++i) {
-    std::string a = argv[i], val;
-    char key = 0;
+    Arg a{argv[i], "", nullptr};
+    const Option *o = nullptr;
     bool have_val = false;
-    if (a.rfind("--", 0) == 0) {
-      std::string name = a.substr(2);
-      size_t eq = name.find('=');
-      if (eq != std::string::npos) val = name.substr(eq + 1), name = name.substr(0, eq), have_val = true;
-      auto it = longs.find(name);
-      if (it == longs.end()) die("unexpected argument '" + a + "'");
-      key = it->second;
-    } else if (a.size() >= 2 && a[0] == '-') {
-      key = a[1];
-      if (a.size() > 2) val = a.substr(a[2] == '=' ? 3 : 2), have_val = true;
+    if (a.flag.rfind("--", 0) == 0) {
+      std::string name = a.flag.substr(2);
+      const size_t eq = name.find('=');
+      if (eq != std::string::npos) a.val = name.substr(eq + 1), name = name.substr(0, eq), have_val = true;
+      for (const Option &x : options)
+        if (name == x.name) o = &x;
+      if (!o) die("unexpected argument '" + a.flag + "'");
+    } else if (a.flag.size() >= 2 && a.flag[0] == '-') {
+      for (const Option &x : options)
+        if (a.flag[1] == x.letter) o = &x;
+      if (a.flag.size() > 2) a.val = a.flag.substr(a.flag[2] == '=' ? 3 : 2), have_val = true;
     } else {
-      die("unexpected argument '" + a + "'");
+      die("unexpected argument '" + a.flag + "'");
     }
     if (!have_val) {
-      if (i + 1 >= argc) die("a value is required for '" + a + "'");
-      val = argv[++i];
+      if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
+      a.val = argv[++i];
     }
-    auto u = [&](unsigned long long max) {
-      char *e = nullptr;
-      unsigned long long v = std::strtoull(val.c_str(), &e, 10);
-      if (val.empty() || *e || v > max) die("invalid value '" + val + "' for '" + a + "'");
-      return v;
-    };
-    switch (key) {
-      case 'p': c.path = val; break;
-      case 'r': c.path_r = val; break;
-      case 'q': c.path_q = val; break;
-      case 'o': c.out = val; break;
-      case 't': c.threads = (unsigned)u(255); break;  // u8
-      case 'm': c.method = val; break;
-      case 'C':
-        if (val == "true") c.canonical = true;
-        else if (val == "false") c.canonical = false;
-        else die("invalid value '" + val + "' for '--canonical'");
-        break;
-      case 'k': c.ksize = (unsigned)u(255); break;  // u8
-      case 'S': c.seed = u(~0ull); break;
-      case 's': c.scaled = u(~0ull); break;
-      case 'd': c.hv_d = u(~0ull); break;
-      case 'Q': c.quant_scale = std::strtof(val.c_str(), nullptr); break;
-      case 'a': c.ani_th = std::strtof(val.c_str(), nullptr), c.ani_th_given = true; break;
-      case 'D': c.device = val; break;
-      case 'n': c.top_n = (unsigned)u(1u << 20); break;  // search only (extension: the reference's search is a stub)
-      case 'G': c.shards = (unsigned)u(64); break;
-      case '\x01':  // (long form only)
-        if (val == "mash") c.ani_metric = HG_ANI_MASH;
-        else if (val == "containment") c.ani_metric = HG_ANI_CONTAINMENT;
-        else if (val == "max_containment") c.ani_metric = HG_ANI_MAX_CONTAINMENT;
-        else die("invalid value '" + val + "' for '--ani_metric' (mash | containment | max_containment)");
-        break;  // dist / search only (cluster rejects it) (testing aid: the several-GPU path on fewer GPUs)
-      case '\x02':  // (long form only) sketch only (extension)
-        c.min_count = (unsigned)u(0xFFFFFFFFull), c.min_count_given = true;
-        if (c.min_count == 0) die("invalid value '" + val + "' for '" + a + "'");
-        break;
-      case '\x03':  // (long form only) search only (testing aid)
-        if (val == "auto") c.search_path = 0;
-        else if (val == "hits") c.search_path = 1;
-        else if (val == "topk") c.search_path = 2;
-        else die("invalid value '" + val + "' for '--search_path' (auto | hits | topk)");
-        c.search_path_given = true;
-        break;
-      case '\x04':  // (long form only) cluster only (extension)
-        if (val == "single") c.greedy = false, c.setcover = false;
-        else if (val == "greedy") c.greedy = true, c.setcover = false;
-        else if (val == "setcover") c.greedy = false, c.setcover = true;
-        else die("invalid value '" + val + "' for '--linkage' (single | greedy | setcover)");
-        c.linkage_given = true;
-        break;
-      case '\x05':  // (long form only) cluster --linkage greedy only (extension)
-        if (val == "file") c.order_size = false;
-        else if (val == "size") c.order_size = true;
-        else die("invalid value '" + val + "' for '--order' (file | size)");
-        c.order_given = true;
-        break;
-      case '\x06':  // (long form only) cluster --linkage single only (extension)
-        if (val.empty()) die("invalid value '' for '--tree' (a file name)");
-        c.tree_out = val, c.tree_given = true;
-        break;
-      case '\x07': {  // (long form only) cluster --linkage single only (extension)
-        c.levels.clear(), c.levels_given = true;
-        for (size_t b = 0; b <= val.size();) {
-          const size_t e = std::min(val.find(',', b), val.size());
-          const std::string item = val.substr(b, e - b);
-          char *end = nullptr;
-          const float v = std::strtof(item.c_str(), &end);
-          if (item.empty() || *end || !(v == v) || item.find_first_not_of("0123456789.+-eE") != std::string::npos)
-            die("invalid value '" + val + "' for '--levels' (1 to 8 ANI thresholds, comma-separated, ascending)");
-          if (c.levels.size() == 8) die("invalid value '" + val + "' for '--levels': at most 8 levels");
-          if (!c.levels.empty() && !(v > c.levels.back())) die("invalid value '" + val + "' for '--levels': the levels must be strictly ascending");
-          c.levels.push_back(v);
-          b = e + 1;
-        }
-        break;
-      }
-      case '\x08': {  // (long form only) dist only (extension)
-        static const std::pair<const char *, uint32_t> names[] = {{"mash", HG_PAIRS_MASH}, {"containment", HG_PAIRS_CONTAINMENT},
-                                                                  {"max_containment", HG_PAIRS_MAX_CONTAINMENT}, {"containment_ref", HG_PAIRS_CONTAINMENT_REF}};
-        c.columns.clear(), c.columns_given = true;
-        for (size_t b = 0; b <= val.size();) {
-          const size_t e = std::min(val.find(',', b), val.size());
-          const std::string item = val.substr(b, e - b);
-          uint32_t bit = 0;
-          for (const auto &nm : names)
-            if (item == nm.first) bit = nm.second;
-          if (!bit) die("invalid value '" + val + "' for '--columns' (a comma list out of mash, containment, containment_ref, max_containment)");
-          if (std::find(c.columns.begin(), c.columns.end(), bit) != c.columns.end()) die("invalid value '" + val + "' for '--columns': '" + item + "' is listed twice");
-          c.columns.push_back(bit);
-          b = e + 1;
-        }
-        break;
-      }
-      case '\x0b':  // (long form only) dist only (extension)
-        if (val.empty()) die("invalid value '' for '--pairs' (a file name)");
-        c.pairs_file = val, c.pairs_given = true;
-        break;
-      case 'L':  // sketch only (extension): which of the reference's two payload layouts to write
-        if (val == "naive") c.pack_naive = true;
-        else if (val == "avx2" || val == "bitpacker8x") c.pack_naive = false;
-        else die("invalid value '" + val + "' for '--pack_layout' (avx2 | naive)");
-        break;
-      default: die("unexpected argument '" + a + "'");
-    }
+    if (!o) die("unexpected argument '" + a.flag + "'");  // (an unknown letter: after its value, as ever)
+    a.name = o->name;
+    o->take(c, a);
+    c.given.set((size_t)(o - options));
   }
-  if (c.search_path_given && c.mode != "search") die("--search_path is not supported by " + c.mode + ": it chooses how search selects its results");
-  if (c.search_path == 2 && c.top_n > HG_SEARCH_TOPK_MAX)
+  if (!c.shards) c.given.reset(option_row("shards"));  // --shards 0 is the default
+  for (size_t k = 0; k < N_OPTIONS; ++k) {
+    if (!c.given[k]) continue;
+    const std::string f = std::string("--") + options[k].name;
+    if (!(options[k].modes & c.mode_bit)) die(f + " is not supported by " + c.mode + ": " + options[k].why);
+    if (options[k].why_shards && c.shards) die(f + " is not supported with --shards: " + options[k].why_shards);
+  }
+  // what an option needs of the others
+  if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
-  if (c.linkage_given && c.mode != "cluster") die("--linkage is not supported by " + c.mode + ": it chooses how cluster forms its clusters");
-  if (c.order_given && c.mode == "cluster" && c.setcover)
+  if (given(c, "order") && c.mode_bit == CLUSTER && c.linkage == Linkage::setcover)
     die("--order is not supported by cluster --linkage setcover: the order the representatives are chosen in is the rule's own");
-  if (c.order_given && !(c.mode == "cluster" && c.greedy))
+  if (given(c, "order") && !(c.mode_bit == CLUSTER && c.linkage == Linkage::greedy))
     die("--order needs cluster --linkage greedy: single-linkage components do not depend on the order of the sketches");
-  for (int k = 0; k < 2; ++k) {
-    if (!(k ? c.levels_given : c.tree_given)) continue;
-    const std::string f = k ? "--levels" : "--tree";
-    if (c.mode != "cluster") die(f + " is not supported by " + c.mode + ": it belongs to cluster --linkage single");
-    if (c.greedy) die(f + " needs cluster --linkage single: greedy clusters are not nested and have no tree");
-    if (c.setcover) die(f + " needs cluster --linkage single: set-cover clusters are not nested and have no tree");
-    if (c.shards) die(f + " is not supported with --shards: cluster runs on the first visible GPU");
-  }
-  for (int k = 0; k < 2; ++k) {
-    if (!(k ? c.pairs_given : c.columns_given)) continue;
-    const std::string f = k ? "--pairs" : "--columns";
-    if (c.mode != "dist") die(f + " is not supported by " + c.mode + (k ? ": it names the pairs dist evaluates" : ": it adds a pair's other metrics to the lines of dist"));
-    if (c.shards) die(f + " is not supported with --shards: dist with --columns or --pairs runs on the first visible GPU");
-  }
-  if (c.levels_given && !(c.levels[0] > (c.ani_th_given ? c.ani_th : 95.0f)))
+  if ((given(c, "tree") || given(c, "levels")) && c.linkage != Linkage::single)
+    die(std::string(given(c, "tree") ? "--tree" : "--levels") + " needs cluster --linkage single: " +
+        (c.linkage == Linkage::greedy ? "greedy" : "set-cover") + " clusters are not nested and have no tree");
+  if (given(c, "levels") && !(c.levels[0] > c.ani_th))
     die("invalid value for '--levels': every level must be above -a, the threshold the tree is built at");
-  if (c.min_count_given && c.mode != "sketch") die("--min_count is not supported by " + c.mode + ": the filter needs the k-mer counts, which a sketch no longer has");
+  if (c.mode_bit == CLUSTER && c.ani_metric == HG_ANI_CONTAINMENT)
+    die("--ani_metric containment is not supported by cluster: it is directional (mash | max_containment)");
   return c;
 }
 
@@ -324,7 +335,7 @@ void ckm(hg_multi *m, hg_status s, const char *what) {
 
 // every GPU the process can see (HIP_VISIBLE_DEVICES narrows it); the reference opens device 0 only
 // (src/sketch_cuda.rs:52)
-hg_multi *open_all_devices(unsigned shards = 0) {
+hg_multi *open_all_devices(unsigned shards) {
   const int n = hg_device_count();
   if (n <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
   // (--shards N: N shards dealt round the devices -- repeated ids run several shards on one GPU, which is how the
@@ -335,11 +346,6 @@ hg_multi *open_all_devices(unsigned shards = 0) {
   if (hg_multi_create(ids.data(), (int)ids.size(), &m) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
   return m;
 }
-
-// Reader thread -> the CPUs of the NUMA node its device hangs off (the thread's page-locked buffers lie there wherever
-// the thread runs: filling and packing them from that socket is ~1.5x faster, and the DMA engine fetches them ~25 %
-// faster than from the other one).  Best effort.
-void bind_thread_to_node(int node, size_t threads_sharing) { (void)hg_bind_thread_to_numa_node(node, (unsigned)threads_sharing); }
 
 // get_fasta_files (src/utils.rs:208-221): *.fna, *.fa, *.fasta, in that order
 std::vector<std::string> fasta_files(const std::string &dir) {
@@ -360,7 +366,7 @@ int run_sketch(const Cli &c) {
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   if (c.scaled == 0) die("scaled must be >= 1");
   if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
   if (c.hv_d % 256)  // the reference packs whole 256-blocks only (src/hd.rs:147) and says nothing; same bytes here
@@ -413,7 +419,10 @@ int run_sketch(const Cli &c) {
   std::atomic<size_t> n_packed{0};
   const uint32_t pack_flags = HG_READ_PACK2 | (p.norm_mode == HG_NORM_U2T ? HG_READ_PACK2_U2T : 0u);
   auto reader = [&](size_t tid) {
-    bind_thread_to_node(dev_node[tid % dev_node.size()], T);
+    // Reader thread -> the CPUs of the NUMA node its device hangs off (the thread's page-locked buffers lie there wherever
+    // the thread runs: filling and packing them from that socket is ~1.5x faster, and the DMA engine fetches them ~25 %
+    // faster than from the other one).  Best effort.
+    (void)hg_bind_thread_to_numa_node(dev_node[tid % dev_node.size()], (unsigned)T);
     size_t k = 0;
     for (size_t i; (i = next.fetch_add(1)) < n; k = (k + 1) % S) {
       Slot &sl = slots[tid * S + k];
@@ -495,7 +504,7 @@ int run_sketch(const Cli &c) {
   debugf("collector: waited %.1f ms for results, sketch compression %.1f ms; readers: %.2f ms per file and thread, "
          "%zu of %zu files sent 2-bit packed", t_wait * 1e3, t_pack * 1e3, n ? read_ns.load() / 1e6 / n : 0.0,
          n_packed.load(), n);
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const double secs = now_s() - t0;
   char buf[256];
   std::snprintf(buf, sizeof buf, "Sketching %zu files took %.2fs - Speed: %.1f files/s", n, secs, n / std::max(secs, 1e-9));
   logline("INFO", buf);
@@ -511,6 +520,38 @@ int run_sketch(const Cli &c) {
   return 0;
 }
 
+// fn(0) .. fn(n - 1) side by side: fn(0) on this thread, a thread each for the others
+template <class F>
+void parallel(size_t n, F fn) {
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < n; ++t) th.emplace_back([&fn, t] { fn(t); });
+  fn(0);
+  for (auto &t : th) t.join();
+}
+
+// One hg_dev_alloc allocation of n elements of T, freed with the object
+template <class T>
+class DevBuf {
+  hg_ctx *ctx;
+  T *p = nullptr;
+
+ public:
+  explicit DevBuf(hg_ctx *c) : ctx(c) {}  // (empty: alloc() or a move fills it)
+  DevBuf(hg_ctx *c, size_t n) : ctx(c) { alloc(n); }
+  DevBuf &operator=(DevBuf &&o) noexcept { return std::swap(ctx, o.ctx), std::swap(p, o.p), *this; }
+  ~DevBuf() { if (p) (void)hg_dev_free(ctx, p); }
+  void alloc(size_t n) {  // (what it held is freed first)
+    if (p) ck(ctx, hg_dev_free(ctx, release()), "free");
+    void *v = nullptr;
+    ck(ctx, hg_dev_alloc(ctx, n * sizeof(T), &v), "alloc");
+    p = static_cast<T *>(v);
+  }
+  T *get() const { return p; }
+  T *release() { return std::exchange(p, nullptr); }  // (the caller frees it)
+  void upload(const T *host, size_t n) { ck(ctx, hg_copy_h2d(ctx, p, host, n * sizeof(T)), "upload"); }
+  void download(T *host, size_t n) const { ck(ctx, hg_copy_d2h(ctx, host, p, n * sizeof(T)), "download"); }
+};
+
 // A loaded .sketch file: the records (names, norms, widths) on the host, the bit-packed payloads still inside the file
 // image.  decompress_file_sketch (src/hd.rs:171-180) happens on the device: the image's payload bytes go over the link as
 // they are (4.6 KB per sketch at 9 bits against 8 KB of int16) and hg_hv_unpack_batch_dev decodes them into the matrix
@@ -520,9 +561,14 @@ struct Loaded {
   std::vector<int32_t> n2;
   std::vector<uint64_t> off;     // payload offsets in the image
   std::vector<uint8_t> q, lay;   // quantisation bits, payload layout (BitPacker8x / the non-AVX2 one) per record
+  std::vector<uint32_t> len;     // strlen of the record's file_str: looked up once per file, not once per output line
   size_t n = 0;
   uint64_t hv_d = 0;
   uint8_t ksize = 0;
+  size_t put_name(char *w, size_t i) const {  // record i's file_str at w
+    std::memcpy(w, hg_sketch_file_get(f, i)->file_str, len[i]);
+    return len[i];
+  }
 };
 
 void load(const std::string &path, Loaded &L) {
@@ -534,7 +580,7 @@ void load(const std::string &path, Loaded &L) {
   L.hv_d = r0->hv_d, L.ksize = r0->ksize;
   // validate before sizing anything from the file's own numbers
   if (L.hv_d == 0 || L.hv_d > 65536) die("unsupported HV dimension in " + path);
-  L.n2.resize(L.n), L.off.resize(L.n), L.q.resize(L.n), L.lay.resize(L.n);
+  L.n2.resize(L.n), L.off.resize(L.n), L.q.resize(L.n), L.lay.resize(L.n), L.len.resize(L.n);
   for (size_t i = 0; i < L.n; ++i) {
     const hg_file_sketch *r = hg_sketch_file_get(L.f, i);
     if (r->hv_quant_bits < 1 || r->hv_quant_bits > 16) die("corrupt sketch record (quantisation bits) in " + path);
@@ -543,6 +589,7 @@ void load(const std::string &path, Loaded &L) {
     const int lay = hg_hv_payload_layout((uint32_t)L.hv_d, r->hv_quant_bits, (size_t)r->hv_len * 2);
     if (lay < 0) die("corrupt sketch payload in " + path);
     L.n2[i] = r->hv_norm_2, L.off[i] = hg_sketch_file_payload_offset(L.f, i), L.q[i] = r->hv_quant_bits, L.lay[i] = (uint8_t)lay;
+    L.len[i] = (uint32_t)std::strlen(r->file_str);
   }
 }
 
@@ -564,12 +611,12 @@ void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false, con
   D.hv.assign(ns, nullptr), D.n2.assign(ns, nullptr), D.rows.assign(ns, 0);
   size_t img_bytes = 0;
   const uint8_t *img = hg_sketch_file_image(L.f, &img_bytes);
-  auto work = [&](int s) {
+  parallel((size_t)ns, [&](size_t s) {
     size_t lo = 0, hi = 0;
-    hg_shard_range(L.n, s, ns, &lo, &hi);
+    hg_shard_range(L.n, (int)s, ns, &lo, &hi);
     if (whole) lo = 0, hi = L.n;
     if (hi == lo) return;
-    hg_ctx *ctx = hg_multi_ctx(m, s);
+    hg_ctx *ctx = hg_multi_ctx(m, (int)s);
     const uint64_t b0 = L.off[lo], b1 = L.off[hi - 1] + 2 * hg_sketch_file_get(L.f, hi - 1)->hv_len;
     if (b1 > img_bytes || b0 > b1) die("corrupt sketch payload");
     std::vector<uint64_t> rel(hi - lo);
@@ -586,21 +633,14 @@ void to_devices(hg_multi *m, const Loaded &L, DevSet &D, bool whole = false, con
     }
     const int32_t *n2_src = perm ? p_n2.data() : L.n2.data() + lo;
     const uint8_t *q_src = perm ? p_q.data() : L.q.data() + lo, *lay_src = perm ? p_lay.data() : L.lay.data() + lo;
-    void *d_img = nullptr, *d_hv = nullptr, *d_n2 = nullptr;
-    ck(ctx, hg_dev_alloc(ctx, b1 - b0, &d_img), "alloc");
-    ck(ctx, hg_dev_alloc(ctx, (hi - lo) * L.hv_d * sizeof(int16_t), &d_hv), "alloc");
-    ck(ctx, hg_dev_alloc(ctx, (hi - lo) * sizeof(int32_t), &d_n2), "alloc");
-    ck(ctx, hg_copy_h2d(ctx, d_img, img + b0, b1 - b0), "upload");
-    ck(ctx, hg_copy_h2d(ctx, d_n2, n2_src, (hi - lo) * sizeof(int32_t)), "upload");
-    ck(ctx, hg_hv_unpack_batch_dev(ctx, static_cast<const uint8_t *>(d_img), b1 - b0, rel.data(), q_src, lay_src,
-                                   hi - lo, (uint32_t)L.hv_d, static_cast<int16_t *>(d_hv)), "unpack");
-    ck(ctx, hg_dev_free(ctx, d_img), "free");
-    D.hv[s] = static_cast<const int16_t *>(d_hv), D.n2[s] = static_cast<const int32_t *>(d_n2), D.rows[s] = hi - lo;
-  };
-  std::vector<std::thread> th;
-  for (int s = 1; s < ns; ++s) th.emplace_back(work, s);
-  work(0);
-  for (auto &t : th) t.join();
+    DevBuf<uint8_t> d_img(ctx, b1 - b0);
+    DevBuf<int16_t> d_hv(ctx, (hi - lo) * L.hv_d);
+    DevBuf<int32_t> d_n2(ctx, hi - lo);
+    d_img.upload(img + b0, b1 - b0);
+    d_n2.upload(n2_src, hi - lo);
+    ck(ctx, hg_hv_unpack_batch_dev(ctx, d_img.get(), b1 - b0, rel.data(), q_src, lay_src, hi - lo, (uint32_t)L.hv_d, d_hv.get()), "unpack");
+    D.hv[s] = d_hv.release(), D.n2[s] = d_n2.release(), D.rows[s] = hi - lo;
+  });
 }
 void release(hg_multi *m, DevSet &D) {
   for (size_t s = 0; s < D.hv.size(); ++s) {
@@ -653,39 +693,37 @@ struct HitBuf {
 // in dump_ani_file's order (src/utils.rs:262-269).  With one device the hits stay there until they are ordered (dist ->
 // radix passes -> one download); with several, the shards' lists meet on the host and go through device 0 for the order.
 // d_keep != nullptr: the list is wanted on device 0 (for hg_topk_per_query_dev), not on the host: *d_keep receives it
-// (hg_dev_free it) and `hits` stays empty.
+// and `hits` stays empty.
 size_t all_hits(hg_multi *multi, const Loaded &R, const DevSet &dR, const Loaded *Q, const DevSet *dQ, float ani_th, bool order,
-                HitBuf &hits, void **d_keep = nullptr) {
+                HitBuf &hits, DevBuf<hg_ani_hit> *d_keep = nullptr) {
   const bool sym = Q == nullptr;
   const size_t qn = sym ? R.n : Q->n, total = sym ? R.n * (R.n - 1) / 2 : R.n * qn;
   size_t cap = std::max<size_t>(1024, total / 16), found = 0;
   const double t_in = now_s();
+  hg_ctx *ctx = hg_multi_ctx(multi, 0);
   if (hg_multi_size(multi) == 1) {
-    hg_ctx *ctx = hg_multi_ctx(multi, 0);
-    void *d_hits = nullptr;
+    DevBuf<hg_ani_hit> d_hits(ctx);
     for (;;) {
-      ck(ctx, hg_dev_alloc(ctx, cap * sizeof(hg_ani_hit), &d_hits), "alloc");
+      d_hits.alloc(cap);
       const hg_status s = hg_dist_dev(ctx, dR.hv[0], dR.n2[0], R.n, sym ? dR.hv[0] : dQ->hv[0], sym ? dR.n2[0] : dQ->n2[0], qn,
-                                      (uint32_t)R.hv_d, R.ksize, sym, ani_th, static_cast<hg_ani_hit *>(d_hits), cap, &found);
+                                      (uint32_t)R.hv_d, R.ksize, sym, ani_th, d_hits.get(), cap, &found);
       if (s != HG_ERR_CAPACITY) {
         ck(ctx, s, "dist");
         break;
       }
-      ck(ctx, hg_dev_free(ctx, d_hits), "free");
       cap = found;
     }
     const double t1 = now_s();
-    if (order) ck(ctx, hg_sort_ani_hits_dev(ctx, static_cast<hg_ani_hit *>(d_hits), found, qn), "sort");
+    if (order) ck(ctx, hg_sort_ani_hits_dev(ctx, d_hits.get(), found, qn), "sort");
     if (d_keep) {
-      *d_keep = d_hits;
+      *d_keep = std::move(d_hits);
       debugf("  dist on the device %.1f ms", (t1 - t_in) * 1e3);
       return found;
     }
     if (order) ck(ctx, hg_ctx_sync(ctx), "sort");
     const double t2 = now_s();
     hits.resize(found);
-    if (found) ck(ctx, hg_copy_d2h(ctx, hits.p, d_hits, found * sizeof(hg_ani_hit)), "download");
-    ck(ctx, hg_dev_free(ctx, d_hits), "free");
+    if (found) d_hits.download(hits.p, found);
     debugf("  dist on the device %.1f ms, order %.1f ms, download %.1f ms", (t1 - t_in) * 1e3, (t2 - t1) * 1e3, (now_s() - t2) * 1e3);
     return found;
   }
@@ -702,11 +740,10 @@ size_t all_hits(hg_multi *multi, const Loaded &R, const DevSet &dR, const Loaded
     cap = found;
   }
   hits.n = found;
-  hg_ctx *ctx0 = hg_multi_ctx(multi, 0);
-  if (order) ck(ctx0, hg_sort_ani_hits_staged(ctx0, hits.p, found, qn), "sort");
+  if (order) ck(ctx, hg_sort_ani_hits_staged(ctx, hits.p, found, qn), "sort");
   if (d_keep) {
-    ck(ctx0, hg_dev_alloc(ctx0, std::max<size_t>(found, 1) * sizeof(hg_ani_hit), d_keep), "alloc");
-    if (found) ck(ctx0, hg_copy_h2d(ctx0, *d_keep, hits.p, found * sizeof(hg_ani_hit)), "upload");
+    *d_keep = DevBuf<hg_ani_hit>(ctx, std::max<size_t>(found, 1));
+    if (found) d_keep->upload(hits.p, found);
   }
   return found;
 }
@@ -746,89 +783,162 @@ std::vector<hg_ani_hit> read_pair_list(const std::string &path, const Loaded &R,
   return list;
 }
 
+// "<file_str of A's record a>\t<file_str of B's record b>\t<ani>\n" ("{}\t{}\t{:.3}\n", src/utils.rs:277-282) at w: two memcpy and
+// put_ani, at most A.len[a] + B.len[b] + 10 bytes
+inline size_t put_line(char *w, const Loaded &A, size_t a, const Loaded &B, size_t b, float ani) {
+  char *const w0 = w;
+  w += A.put_name(w, a);
+  *w++ = '\t';
+  w += B.put_name(w, b);
+  w += put_ani(w, ani);
+  return (size_t)(w - w0);
+}
+inline size_t put_u32(char *o, uint32_t v) {  // decimal, at most 10 digits
+  char tmp[10];
+  size_t n = 0, k = 0;
+  do tmp[n++] = (char)('0' + v % 10), v /= 10;
+  while (v);
+  while (n) o[k++] = tmp[--n];
+  return k;
+}
+
+// One TSV file of `items` items: put(i, w) writes item i at w and returns its bytes, at most bound(i) of them.  -t threads
+// format contiguous ranges of the items, one part per 4096 items at the most, and every part then goes to its own offset of
+// the file: the copies into the page cache run side by side.  Returns the size of the file.
+template <class Bound, class Put>
+size_t write_tsv(const std::string &path, unsigned threads, size_t items, Bound bound, Put put, const char *failed) {
+  double tp = now_s();
+  const size_t FT = std::max<size_t>(1, std::min<size_t>(threads, items / 4096 + 1));
+  std::vector<std::string> part(FT);
+  parallel(FT, [&](size_t t) {
+    const size_t lo = items * t / FT, hi = items * (t + 1) / FT;
+    size_t need = 0;
+    for (size_t i = lo; i < hi; ++i) need += bound(i);
+    std::string &o = part[t];
+    o.resize(need);
+    char *w = &o[0];
+    for (size_t i = lo; i < hi; ++i) w += put(i, w);
+    o.resize((size_t)(w - &o[0]));
+  });
+  std::vector<size_t> at(FT + 1, 0);
+  for (size_t t = 0; t < FT; ++t) at[t + 1] = at[t] + part[t].size();
+  debugf("TSV formatted (%.1f MB) in %.1f ms", at[FT] / 1e6, (now_s() - tp) * 1e3);
+  tp = now_s();
+  const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+  if (fd < 0) die(failed);
+  std::atomic<bool> bad{false};
+  parallel(FT, [&](size_t t) {
+    const char *p = part[t].data();
+    size_t left = part[t].size(), off = at[t];
+    while (left) {
+      const ssize_t w = ::pwrite(fd, p, left, (off_t)off);
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) {
+        bad = true;
+        return;
+      }
+      p += w, off += (size_t)w, left -= (size_t)w;
+    }
+  });
+  if (::close(fd) != 0 || bad) die(failed);
+  debugf("TSV written in %.1f ms", (now_s() - tp) * 1e3);
+  return at[FT];
+}
+
+// What dist, search and cluster work on: the devices, one sketch file or two, and their rows on the devices (the caller's
+// to_devices fills dR / dQ).  The devices are opened on a thread of their own -- the HIP runtime comes up (~0.2 s) while the
+// files are read and parsed, two of them side by side.  (die() leaves through _exit: nothing is torn down on that path.)
+struct Session {
+  hg_multi *multi = nullptr;
+  Loaded R, Q2;  // Q2: the second file, where there is one
+  const bool two;
+  DevSet dR, dQ;
+  Session(unsigned shards, int ani_metric, const std::string &path_r, const std::string *path_q = nullptr) : two(path_q != nullptr) {
+    const double tp = now_s();
+    std::thread opener([&] {
+      multi = open_all_devices(shards);
+      ckm(multi, hg_multi_set_ani_metric(multi, ani_metric), "ani_metric");
+      debugf("devices opened in %.1f ms", (now_s() - tp) * 1e3);
+    });
+    std::thread second;
+    if (two) second = std::thread([&] { load(*path_q, Q2); });
+    load(path_r, R);
+    if (two) second.join();
+    debugf("sketch files loaded in %.1f ms", (now_s() - tp) * 1e3);
+    opener.join();
+    if (R.ksize != Q().ksize) die("Ref and query sketches use different kmer sizes!");
+    if (R.hv_d != Q().hv_d) die("Ref and query sketches use different HV dimensions!");
+  }
+  Session(const Session &) = delete;
+  ~Session() {
+    release(multi, dR), release(multi, dQ);
+    hg_sketch_file_free(R.f);
+    if (two) hg_sketch_file_free(Q2.f);
+    hg_multi_destroy(multi);
+  }
+  const Loaded &Q() const { return two ? Q2 : R; }  // the query side: the one file against itself without a second
+};
+
 int run_dist(const Cli &c) {
   if (c.path_r == "1" || c.path_q == "1" || c.out.empty())
     die("the following required arguments were not provided: --path_r --path_q --out");
-  const auto t0 = std::chrono::steady_clock::now();
+  const double t0 = now_s();
   const bool sym = c.path_r == c.path_q;  // src/dist.rs:13
   // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
   const bool sym_full = sym && c.ani_metric == HG_ANI_CONTAINMENT;
   // --columns / --pairs: the pairs' further metrics come from one hg_ani_pairs_dev call on the device list, on one GPU
-  const bool one_gpu = c.columns_given || c.pairs_given;
+  const bool pairs = given(c, "pairs"), one_gpu = pairs || given(c, "columns");
   const uint32_t metric_bit = c.ani_metric == HG_ANI_MASH ? HG_PAIRS_MASH : c.ani_metric == HG_ANI_CONTAINMENT ? HG_PAIRS_CONTAINMENT : HG_PAIRS_MAX_CONTAINMENT;
-  uint32_t mask = c.pairs_given ? metric_bit : 0u;  // (--pairs: the ANI field itself is a column of the call)
+  uint32_t mask = pairs ? metric_bit : 0u;  // (--pairs: the ANI field itself is a column of the call)
   for (const uint32_t b : c.columns) mask |= b;
   const size_t n_cols = (size_t)__builtin_popcount(mask);
   auto col_at = [&](uint32_t bit) { return (size_t)__builtin_popcount(mask & (bit - 1)); };  // a column's place in a pair's values
-  Loaded R, Qs;
+  Session s(one_gpu ? 1 : c.shards, c.ani_metric, c.path_r, sym ? nullptr : &c.path_q);
+  const Loaded &R = s.R, &Q = s.Q();
+  const DevSet &dq = sym ? s.dR : s.dQ;
   double tp = now_s();
-  hg_multi *multi = nullptr;
-  std::thread opener([&] {  // the HIP runtime comes up (~0.2 s) while the sketch files are read and decompressed
-    const double td = now_s();
-    multi = one_gpu ? open_all_devices(1) : open_all_devices(c.shards);
-    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
-    debugf("devices opened in %.1f ms", (now_s() - td) * 1e3);
-  });
-  {  // two files are read and parsed side by side
-    std::thread second;
-    if (!sym) second = std::thread([&] { load(c.path_q, Qs); });
-    load(c.path_r, R);
-    if (second.joinable()) second.join();
-  }
-  debugf("sketch files loaded in %.1f ms", (now_s() - tp) * 1e3);
-  opener.join();
-  const Loaded &Q = sym ? R : Qs;
-  if (R.ksize != Q.ksize) die("Ref and query sketches use different kmer sizes!");
-  if (R.hv_d != Q.hv_d) die("Ref and query sketches use different HV dimensions!");
-  tp = now_s();
-  DevSet dR, dQ;
-  to_devices(multi, R, dR);
-  if (!sym) to_devices(multi, Qs, dQ);
+  to_devices(s.multi, R, s.dR);
+  if (!sym) to_devices(s.multi, Q, s.dQ);
   debugf("payloads uploaded and decompressed on the device(s) in %.1f ms", (now_s() - tp) * 1e3);
   logline("INFO", "Computing ANI..");
   tp = now_s();
   const size_t total = sym_full ? R.n * (R.n - 1) : (sym ? R.n * (Q.n - 1) / 2 : R.n * Q.n);
   HitBuf hits;
   std::vector<float> cols;  // --columns / --pairs: n_cols values per line, in ascending order of the column bits
-  void *d_list = nullptr;   // ... and the device list they are computed on
   size_t found = 0;
-  if (c.pairs_given) {
-    const std::vector<hg_ani_hit> list = read_pair_list(c.pairs_file, R, Q);
-    found = list.size();
-    hits.resize(found);
-    if (found) {
-      std::memcpy(hits.p, list.data(), found * sizeof(hg_ani_hit));
-      hg_ctx *ctx = hg_multi_ctx(multi, 0);
-      ck(ctx, hg_dev_alloc(ctx, found * sizeof(hg_ani_hit), &d_list), "alloc");
-      ck(ctx, hg_copy_h2d(ctx, d_list, hits.p, found * sizeof(hg_ani_hit)), "upload");
+  {
+    hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+    DevBuf<hg_ani_hit> d_list(ctx);  // ... and the device list they are computed on
+    if (pairs) {
+      const std::vector<hg_ani_hit> list = read_pair_list(c.pairs_file, R, Q);
+      found = list.size();
+      hits.resize(found);
+      if (found) {
+        std::memcpy(hits.p, list.data(), found * sizeof(hg_ani_hit));
+        d_list.alloc(found);
+        d_list.upload(hits.p, found);
+      }
+    } else {
+      // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
+      // sort of up to 10^6..10^8 triples on one host core)
+      const bool full = sym_full || !sym;
+      found = all_hits(s.multi, R, s.dR, full ? &Q : nullptr, full ? &dq : nullptr, c.ani_th, true, hits, one_gpu ? &d_list : nullptr);
     }
-  } else {
-    // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
-    // sort of up to 10^6..10^8 triples on one host core)
-    found = sym_full ? all_hits(multi, R, dR, &R, &dR, c.ani_th, true, hits, one_gpu ? &d_list : nullptr)
-                     : all_hits(multi, R, dR, sym ? nullptr : &Qs, sym ? nullptr : &dQ, c.ani_th, true, hits, one_gpu ? &d_list : nullptr);
-  }
-  if (one_gpu) {  // the columns of the ordered device list, before the download
-    hg_ctx *ctx = hg_multi_ctx(multi, 0);
-    const DevSet &dq = sym ? dR : dQ;
-    if (found) {
-      void *d_cols = nullptr;
-      ck(ctx, hg_dev_alloc(ctx, found * n_cols * sizeof(float), &d_cols), "alloc");
-      ck(ctx, hg_ani_pairs_dev(ctx, dR.hv[0], dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize,
-                               static_cast<const hg_ani_hit *>(d_list), found, mask, static_cast<float *>(d_cols), nullptr), "ani_pairs");
+    if (one_gpu && found) {  // the columns of the ordered device list, before the download
+      DevBuf<float> d_cols(ctx, found * n_cols);
+      ck(ctx, hg_ani_pairs_dev(ctx, s.dR.hv[0], s.dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize, d_list.get(), found,
+                               mask, d_cols.get(), nullptr), "ani_pairs");
       cols.resize(found * n_cols);
-      ck(ctx, hg_copy_d2h(ctx, cols.data(), d_cols, found * n_cols * sizeof(float)), "download");
-      ck(ctx, hg_dev_free(ctx, d_cols), "free");
-      if (!c.pairs_given) {
+      d_cols.download(cols.data(), cols.size());
+      if (pairs) {
+        for (size_t i = 0; i < found; ++i) hits.p[i].ani = cols[i * n_cols + col_at(metric_bit)];
+      } else {
         hits.resize(found);
-        ck(ctx, hg_copy_d2h(ctx, hits.p, d_list, found * sizeof(hg_ani_hit)), "download");
+        d_list.download(hits.p, found);
       }
     }
-    if (d_list) ck(ctx, hg_dev_free(ctx, d_list), "free");
-    if (c.pairs_given)
-      for (size_t i = 0; i < found; ++i) hits.p[i].ani = cols[i * n_cols + col_at(metric_bit)];
   }
-  if (sym_full && !c.pairs_given) {  // (the pairs i = j are not written: the order of the rest stays)
+  if (sym_full && !pairs) {  // (the pairs i = j are not written: the order of the rest stays)
     size_t w = 0;
     for (size_t i = 0; i < found; ++i)
       if (hits.p[i].ref_idx != hits.p[i].qry_idx) {
@@ -837,74 +947,20 @@ int run_dist(const Cli &c) {
       }
     found = w;
   }
-  release(multi, dR), release(multi, dQ);
   debugf("ANI matrix (%zu hits), ordered, on the host in %.1f ms", found, (now_s() - tp) * 1e3);
-  tp = now_s();
-  // "{}\t{}\t{:.3}\n" (src/utils.rs:277-282), formatted by -t threads over contiguous ranges of the ordered hits: the
-  // paths' lengths are looked up once per file, a line is two memcpy and put_ani
-  const size_t FT = std::max<size_t>(1, std::min<size_t>(c.threads, found / 4096 + 1));
-  std::vector<std::string> part(FT);
-  {
-    std::vector<uint32_t> len_r(R.n), len_q(Q.n);
-    for (size_t i = 0; i < R.n; ++i) len_r[i] = (uint32_t)std::strlen(hg_sketch_file_get(R.f, i)->file_str);
-    for (size_t i = 0; i < Q.n; ++i) len_q[i] = (uint32_t)std::strlen(hg_sketch_file_get(Q.f, i)->file_str);
-    auto fmt = [&](size_t t) {
-      const size_t lo = found * t / FT, hi = found * (t + 1) / FT;
-      size_t need = 0;
-      for (size_t i = lo; i < hi; ++i) need += (size_t)len_r[hits.p[i].ref_idx] + len_q[hits.p[i].qry_idx] + 10 + 10 * c.columns.size();
-      std::string &o = part[t];
-      o.resize(need);
-      char *w = &o[0];
-      for (size_t i = lo; i < hi; ++i) {
-        const hg_ani_hit &h = hits.p[i];
-        std::memcpy(w, hg_sketch_file_get(R.f, h.ref_idx)->file_str, len_r[h.ref_idx]);
-        w += len_r[h.ref_idx];
-        *w++ = '\t';
-        std::memcpy(w, hg_sketch_file_get(Q.f, h.qry_idx)->file_str, len_q[h.qry_idx]);
-        w += len_q[h.qry_idx];
-        w += put_ani(w, h.ani);
-        for (const uint32_t b : c.columns) --w, w += put_ani(w, cols[i * n_cols + col_at(b)]);  // (over the line's '\n')
-      }
-      o.resize((size_t)(w - &o[0]));
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < FT; ++t) th.emplace_back(fmt, t);
-    fmt(0);
-    for (auto &t : th) t.join();
-  }
-  size_t tsv_bytes = 0;
-  for (const auto &o : part) tsv_bytes += o.size();
-  debugf("TSV formatted (%.1f MB) in %.1f ms", tsv_bytes / 1e6, (now_s() - tp) * 1e3);
-  tp = now_s();
-  {  // every formatter's part goes to its own offset of the file: the copies into the page cache run side by side
-    const int fd = ::open(c.out.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
-    if (fd < 0) die("Dump ANI file failed!");
-    std::vector<size_t> at(FT + 1, 0);
-    for (size_t t = 0; t < FT; ++t) at[t + 1] = at[t] + part[t].size();
-    std::atomic<bool> bad{false};
-    auto put = [&](size_t t) {
-      const char *p = part[t].data();
-      size_t left = part[t].size(), off = at[t];
-      while (left) {
-        const ssize_t w = ::pwrite(fd, p, left, (off_t)off);
-        if (w < 0 && errno == EINTR) continue;
-        if (w <= 0) {
-          bad = true;
-          return;
-        }
-        p += w, off += (size_t)w, left -= (size_t)w;
-      }
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < FT; ++t) th.emplace_back(put, t);
-    put(0);
-    for (auto &t : th) t.join();
-    if (::close(fd) != 0 || bad) die("Dump ANI file failed!");
-  }
-  debugf("TSV written in %.1f ms", (now_s() - tp) * 1e3);
+  // one line per hit, in the order of the hits; --columns: one further field each, over the line's '\n'
+  write_tsv(c.out, c.threads, found,
+            [&](size_t i) { return (size_t)R.len[hits.p[i].ref_idx] + Q.len[hits.p[i].qry_idx] + 10 + 10 * c.columns.size(); },
+            [&](size_t i, char *w) {
+              const hg_ani_hit &h = hits.p[i];
+              size_t k = put_line(w, R, h.ref_idx, Q, h.qry_idx, h.ani);
+              for (const uint32_t b : c.columns) --k, k += put_ani(w + k, cols[i * n_cols + col_at(b)]);
+              return k;
+            },
+            "Dump ANI file failed!");
   char buf[512];
   const double perc = total ? 100.0 * found / total : 0.0;
-  if (c.pairs_given) {
+  if (pairs) {
     std::snprintf(buf, sizeof buf, "Output %zu listed ANIs to file %s", found, c.out.c_str());
     logline("INFO", buf);
   } else if (perc < 5.0) {
@@ -915,12 +971,8 @@ int run_dist(const Cli &c) {
     std::snprintf(buf, sizeof buf, "Output %zu of %zu ANIs above threshold %.1f to file %s", found, total, c.ani_th, c.out.c_str());
     logline("INFO", buf);
   }
-  std::snprintf(buf, sizeof buf, "Computed ANIs for %zu ref files and %zu query files took %.3fs", R.n, Q.n,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  std::snprintf(buf, sizeof buf, "Computed ANIs for %zu ref files and %zu query files took %.3fs", R.n, Q.n, now_s() - t0);
   logline("INFO", buf);
-  hg_sketch_file_free(R.f);
-  if (!sym) hg_sketch_file_free(Qs.f);
-  hg_multi_destroy(multi);
   return 0;
 }
 
@@ -930,119 +982,55 @@ int run_dist(const Cli &c) {
 // Without -r / -q / -o it stays the reference's no-op.
 int run_search(const Cli &c) {
   if (c.path_r == "1" || c.path_q == "1" || c.out.empty()) return 0;
-  const auto t0 = std::chrono::steady_clock::now();
-  Loaded R, Q;
-  hg_multi *multi = nullptr;
+  const double t0 = now_s();
+  Session s(c.shards, c.ani_metric, c.path_r, &c.path_q);
+  const Loaded &R = s.R, &Q = s.Q2;
   double tp = now_s();
-  std::thread opener([&] {  // the HIP runtime comes up while the files are read
-    const double td = now_s();
-    multi = open_all_devices(c.shards);
-    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
-    debugf("devices opened in %.1f ms", (now_s() - td) * 1e3);
-  });
-  {  // the two files are read and parsed side by side
-    std::thread second([&] { load(c.path_q, Q); });
-    load(c.path_r, R);
-    second.join();
-  }
-  debugf("sketch files loaded in %.1f ms", (now_s() - tp) * 1e3);
-  opener.join();
-  if (R.ksize != Q.ksize) die("Ref and query sketches use different kmer sizes!");
-  if (R.hv_d != Q.hv_d) die("Ref and query sketches use different HV dimensions!");
-  tp = now_s();
   const uint32_t k = std::max(1u, c.top_n);
   // The fused path (hg_search_topk_multi_dev): the k best per query are selected on the device while blocks of the ANI
   // matrix stream past -- no hit list, memory does not depend on how many pairs lie above the threshold.  Every shard keeps
   // its reference rows and holds ALL queries.  -n beyond HG_SEARCH_TOPK_MAX (or --search_path hits) takes the hit list.
-  const bool fused = c.search_path == 2 || (c.search_path == 0 && k <= HG_SEARCH_TOPK_MAX);
-  DevSet dR, dQ;
-  to_devices(multi, R, dR);
-  to_devices(multi, Q, dQ, fused);
+  const bool fused = c.search_path == SearchPath::topk || (c.search_path == SearchPath::automatic && k <= HG_SEARCH_TOPK_MAX);
+  to_devices(s.multi, R, s.dR);
+  to_devices(s.multi, Q, s.dQ, fused);
   debugf("payloads uploaded and decompressed on the device(s) in %.1f ms", (now_s() - tp) * 1e3);
   logline("INFO", "Searching..");
   tp = now_s();
   std::vector<hg_ani_hit> best(Q.n * (size_t)k);
   std::vector<uint32_t> cnt(Q.n);
   if (fused) {
-    ckm(multi, hg_search_topk_multi_dev(multi, dR.hv.data(), dR.n2.data(), dR.rows.data(), dQ.hv.data(), dQ.n2.data(), Q.n,
-                                        (uint32_t)R.hv_d, R.ksize, c.ani_th, k, best.data(), cnt.data()), "search");
-    release(multi, dR), release(multi, dQ);
+    ckm(s.multi, hg_search_topk_multi_dev(s.multi, s.dR.hv.data(), s.dR.n2.data(), s.dR.rows.data(), s.dQ.hv.data(), s.dQ.n2.data(), Q.n,
+                                          (uint32_t)R.hv_d, R.ksize, c.ani_th, k, best.data(), cnt.data()), "search");
     debugf("top-%u per query, selected block by block, in %.1f ms", k, (now_s() - tp) * 1e3);
   } else {
     HitBuf hits;
-    void *d_hits = nullptr, *d_out = nullptr, *d_cnt = nullptr;
-    const size_t found = all_hits(multi, R, dR, &Q, &dQ, c.ani_th, false, hits, &d_hits);
-    release(multi, dR), release(multi, dQ);
+    hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+    DevBuf<hg_ani_hit> d_hits(ctx);
+    const size_t found = all_hits(s.multi, R, s.dR, &Q, &s.dQ, c.ani_th, false, hits, &d_hits);
     debugf("ANI matrix (%zu hits) in %.1f ms", found, (now_s() - tp) * 1e3);
     tp = now_s();
-    hg_ctx *ctx = hg_multi_ctx(multi, 0);
-    ck(ctx, hg_dev_alloc(ctx, Q.n * (size_t)k * sizeof(hg_ani_hit), &d_out), "alloc");
-    ck(ctx, hg_dev_alloc(ctx, Q.n * sizeof(uint32_t), &d_cnt), "alloc");
-    ck(ctx, hg_topk_per_query_dev(ctx, static_cast<hg_ani_hit *>(d_hits), found, Q.n, k, static_cast<hg_ani_hit *>(d_out),
-                                  static_cast<uint32_t *>(d_cnt)), "top-k");
-    ck(ctx, hg_copy_d2h(ctx, best.data(), d_out, best.size() * sizeof(hg_ani_hit)), "download");
-    ck(ctx, hg_copy_d2h(ctx, cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t)), "download");
-    hg_dev_free(ctx, d_hits), hg_dev_free(ctx, d_out), hg_dev_free(ctx, d_cnt);
+    DevBuf<hg_ani_hit> d_out(ctx, best.size());
+    DevBuf<uint32_t> d_cnt(ctx, cnt.size());
+    ck(ctx, hg_topk_per_query_dev(ctx, d_hits.get(), found, Q.n, k, d_out.get(), d_cnt.get()), "top-k");
+    d_out.download(best.data(), best.size());
+    d_cnt.download(cnt.data(), cnt.size());
     debugf("top-%u per query in %.1f ms", k, (now_s() - tp) * 1e3);
   }
   tp = now_s();
-  // "query<TAB>reference<TAB>ani" per result, queries in file order, best first; formatted by -t threads over contiguous
-  // ranges of the queries (like dist's lines: two memcpy and put_ani per line)
-  std::vector<size_t> first(Q.n + 1, 0);  // results in front of query q
-  for (size_t q = 0; q < Q.n; ++q) first[q + 1] = first[q] + std::min<uint32_t>(cnt[q], k);
-  const size_t reported = first[Q.n];
-  const size_t FT = std::max<size_t>(1, std::min<size_t>(c.threads, reported / 4096 + 1));
-  std::vector<std::string> part(FT);
-  {
-    std::vector<uint32_t> len_r(R.n), len_q(Q.n);
-    for (size_t i = 0; i < R.n; ++i) len_r[i] = (uint32_t)std::strlen(hg_sketch_file_get(R.f, i)->file_str);
-    for (size_t i = 0; i < Q.n; ++i) len_q[i] = (uint32_t)std::strlen(hg_sketch_file_get(Q.f, i)->file_str);
-    auto fmt = [&](size_t t) {
-      const size_t q_lo = Q.n * t / FT, q_hi = Q.n * (t + 1) / FT;
-      size_t need = 0;
-      for (size_t q = q_lo; q < q_hi; ++q)
-        for (size_t r = 0; r < first[q + 1] - first[q]; ++r) need += (size_t)len_q[q] + len_r[best[q * k + r].ref_idx] + 10;
-      std::string &o = part[t];
-      o.resize(need);
-      char *w = &o[0];
-      for (size_t q = q_lo; q < q_hi; ++q) {
-        const char *qs = hg_sketch_file_get(Q.f, q)->file_str;
-        for (size_t r = 0; r < first[q + 1] - first[q]; ++r) {
-          const hg_ani_hit &h = best[q * k + r];
-          std::memcpy(w, qs, len_q[q]);
-          w += len_q[q];
-          *w++ = '\t';
-          std::memcpy(w, hg_sketch_file_get(R.f, h.ref_idx)->file_str, len_r[h.ref_idx]);
-          w += len_r[h.ref_idx];
-          w += put_ani(w, h.ani);
-        }
-      }
-      o.resize((size_t)(w - &o[0]));
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < FT; ++t) th.emplace_back(fmt, t);
-    fmt(0);
-    for (auto &t : th) t.join();
-  }
-  debugf("TSV formatted in %.1f ms", (now_s() - tp) * 1e3);
-  size_t tsv_bytes = 0;
-  FILE *f = std::fopen(c.out.c_str(), "wb");
-  if (!f) die("Dump search file failed!");
-  for (const auto &o : part) {
-    if (o.size() && std::fwrite(o.data(), 1, o.size(), f) != o.size()) die("Dump search file failed!");
-    tsv_bytes += o.size();
-  }
-  if (std::fclose(f) != 0) die("Dump search file failed!");
+  std::vector<size_t> at;  // the place in `best` of every result to report: queries in file order, best first
+  for (size_t q = 0; q < Q.n; ++q)
+    for (size_t r = 0; r < std::min<uint32_t>(cnt[q], k); ++r) at.push_back(q * k + r);
+  const size_t tsv_bytes = write_tsv(c.out, c.threads, at.size(),
+                                     [&](size_t i) { return (size_t)Q.len[at[i] / k] + R.len[best[at[i]].ref_idx] + 10; },
+                                     [&](size_t i, char *w) { return put_line(w, Q, at[i] / k, R, best[at[i]].ref_idx, best[at[i]].ani); },
+                                     "Dump search file failed!");
   debugf("TSV formatted and written (%.1f MB) in %.1f ms", tsv_bytes / 1e6, (now_s() - tp) * 1e3);
   char buf[256];
   std::snprintf(buf, sizeof buf, "Searched %zu queries against %zu references: %zu results (top %u, ANI >= %.1f) took %.3fs",
-                Q.n, R.n, reported, k, c.ani_th, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+                Q.n, R.n, at.size(), k, c.ani_th, now_s() - t0);
   logline("INFO", buf);
-  hg_sketch_file_free(R.f), hg_sketch_file_free(Q.f);
-  hg_multi_destroy(multi);
   return 0;
 }
-
 
 // `cluster` (an extension: the reference has no such subcommand): single-linkage clusters of the sketches of one file at an
 // ANI threshold, computed where the hits are (hg_cluster_dev: the symmetric comparison in row blocks, each block's hits
@@ -1058,34 +1046,23 @@ int run_search(const Cli &c) {
 // may stand behind its members in the file.
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
-  if (c.shards) die("--shards is not supported by cluster: it runs on the first visible GPU");
-  if (c.ani_metric == HG_ANI_CONTAINMENT) die("--ani_metric containment is not supported by cluster: it is directional (mash | max_containment)");
-  const float th = c.ani_th_given ? c.ani_th : 95.0f;
-  const auto t0 = std::chrono::steady_clock::now();
-  Loaded L;
-  hg_multi *multi = nullptr;
-  std::thread opener([&] {  // (the HIP runtime comes up while the file is read)
-    multi = open_all_devices(1);
-    ckm(multi, hg_multi_set_ani_metric(multi, c.ani_metric), "ani_metric");
-  });
-  load(c.path, L);
-  opener.join();
-  DevSet D;
-  std::vector<uint32_t> perm;  // greedy, setcover: processing position -> record (setcover: the file order)
-  if (c.greedy || c.setcover) {
-    perm.resize(L.n);
-    for (size_t i = 0; i < L.n; ++i) perm[i] = (uint32_t)i;
-    if (c.order_size) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return L.n2[a] > L.n2[b]; });
-  }
-  to_devices(multi, L, D, false, c.order_size ? &perm : nullptr);
+  const float th = c.ani_th;
+  const bool setcover = c.linkage == Linkage::setcover, with_reps = c.linkage != Linkage::single;  // (greedy, setcover)
+  const double t0 = now_s();
+  Session s(1, c.ani_metric, c.path);
+  const Loaded &L = s.R;
+  std::vector<uint32_t> perm(L.n);  // processing position -> record: the file order unless --order size (greedy only)
+  for (size_t i = 0; i < L.n; ++i) perm[i] = (uint32_t)i;
+  if (c.order_size) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return L.n2[a] > L.n2[b]; });
+  to_devices(s.multi, L, s.dR, false, c.order_size ? &perm : nullptr);
+  const int16_t *hv = s.dR.hv[0];
+  const int32_t *n2 = s.dR.n2[0];
   char buf[512];
   std::snprintf(buf, sizeof buf, "Clustering %zu genomes at ANI threshold %.1f..", L.n, th);
   logline("INFO", buf);
-  double tp = now_s();
-  hg_ctx *ctx = hg_multi_ctx(multi, 0);
-  void *d_rep = nullptr, *d_cl = nullptr;
-  ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_rep), "alloc");
-  ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_cl), "alloc");
+  const double tp = now_s();
+  hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+  DevBuf<uint32_t> d_rep(ctx, L.n), d_cl(ctx, L.n);
   size_t n_cl = 0;
   std::vector<uint32_t> rep(L.n), cl(L.n);
   std::vector<float> ani;
@@ -1096,106 +1073,81 @@ int run_cluster(const Cli &c) {
   };
   std::vector<Level> more;
   std::vector<hg_ani_hit> tree;  // --tree / --levels
-  if (c.greedy || c.setcover) {
-    void *d_ani = nullptr;
-    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(float), &d_ani), "alloc");
-    ck(ctx, (c.setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th,
-                                                                           static_cast<uint32_t *>(d_rep), static_cast<uint32_t *>(d_cl),
-                                                                           static_cast<float *>(d_ani), &n_cl), "cluster");
+  if (with_reps) {
+    DevBuf<float> d_ani(ctx, L.n);
+    ck(ctx, (setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(),
+                                                                         d_cl.get(), d_ani.get(), &n_cl), "cluster");
     ani.resize(L.n);
-    ck(ctx, hg_copy_d2h(ctx, ani.data(), d_ani, L.n * sizeof(float)), "download");
-    (void)hg_dev_free(ctx, d_ani);
-    if (c.setcover) debugf("set-cover resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_setcover_rounds(ctx));
+    d_ani.download(ani.data(), L.n);
+    if (setcover) debugf("set-cover resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_setcover_rounds(ctx));
     else debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
-  } else if (c.tree_given || c.levels_given) {
+  } else if (given(c, "tree") || given(c, "levels")) {
     // one comparison at the floor -a (hg_cluster_tree_dev); every level is a cut of the tree (the step calls of hg_cluster)
-    void *d_tree = nullptr;
+    DevBuf<hg_ani_hit> d_tree(ctx, std::max<size_t>(L.n, 2));
     size_t n_edges = 0;
-    ck(ctx, hg_dev_alloc(ctx, std::max<size_t>(L.n, 2) * sizeof(hg_ani_hit), &d_tree), "alloc");
-    ck(ctx, hg_cluster_tree_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<hg_ani_hit *>(d_tree),
-                                L.n ? L.n - 1 : 0, &n_edges, static_cast<uint32_t *>(d_rep), static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
+    ck(ctx, hg_cluster_tree_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_tree.get(), L.n ? L.n - 1 : 0, &n_edges, d_rep.get(),
+                                d_cl.get(), &n_cl), "cluster");
     debugf("tree of %zu edges in %llu rounds", n_edges, (unsigned long long)hg_ctx_cluster_tree_rounds(ctx));
     tree.resize(n_edges);
-    if (n_edges) ck(ctx, hg_copy_d2h(ctx, tree.data(), d_tree, n_edges * sizeof(hg_ani_hit)), "download");
-    void *d_rep2 = nullptr, *d_cl2 = nullptr;
-    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_rep2), "alloc");
-    ck(ctx, hg_dev_alloc(ctx, L.n * sizeof(uint32_t), &d_cl2), "alloc");
+    if (n_edges) d_tree.download(tree.data(), n_edges);
+    DevBuf<uint32_t> d_rep2(ctx, L.n), d_cl2(ctx, L.n);  // (one pair of buffers for all levels)
     for (const float t : c.levels) {
       Level v;
       v.th = t, v.rep.resize(L.n), v.cl.resize(L.n);
-      auto *r2 = static_cast<uint32_t *>(d_rep2);
-      ck(ctx, hg_cluster_init_dev(ctx, r2, L.n), "cluster");
-      ck(ctx, hg_cluster_add_hits_dev(ctx, r2, L.n, static_cast<const hg_ani_hit *>(d_tree), n_edges, t), "cluster");
-      ck(ctx, hg_cluster_finish_dev(ctx, r2, L.n, static_cast<uint32_t *>(d_cl2), &v.n_cl), "cluster");
-      ck(ctx, hg_copy_d2h(ctx, v.rep.data(), d_rep2, L.n * sizeof(uint32_t)), "download");
-      ck(ctx, hg_copy_d2h(ctx, v.cl.data(), d_cl2, L.n * sizeof(uint32_t)), "download");
+      ck(ctx, hg_cluster_init_dev(ctx, d_rep2.get(), L.n), "cluster");
+      ck(ctx, hg_cluster_add_hits_dev(ctx, d_rep2.get(), L.n, d_tree.get(), n_edges, t), "cluster");
+      ck(ctx, hg_cluster_finish_dev(ctx, d_rep2.get(), L.n, d_cl2.get(), &v.n_cl), "cluster");
+      d_rep2.download(v.rep.data(), L.n);
+      d_cl2.download(v.cl.data(), L.n);
       more.push_back(std::move(v));
     }
-    (void)hg_dev_free(ctx, d_tree), (void)hg_dev_free(ctx, d_rep2), (void)hg_dev_free(ctx, d_cl2);
   } else {
-    ck(ctx, hg_cluster_dev(ctx, D.hv[0], D.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, th, static_cast<uint32_t *>(d_rep),
-                           static_cast<uint32_t *>(d_cl), &n_cl), "cluster");
+    ck(ctx, hg_cluster_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(), d_cl.get(), &n_cl), "cluster");
   }
-  ck(ctx, hg_copy_d2h(ctx, rep.data(), d_rep, L.n * sizeof(uint32_t)), "download");
-  ck(ctx, hg_copy_d2h(ctx, cl.data(), d_cl, L.n * sizeof(uint32_t)), "download");
-  (void)hg_dev_free(ctx, d_rep), (void)hg_dev_free(ctx, d_cl);
-  release(multi, D);
+  d_rep.download(rep.data(), L.n);
+  d_cl.download(cl.data(), L.n);
   debugf("clusters on the host in %.1f ms", (now_s() - tp) * 1e3);
   std::vector<uint32_t> size(n_cl, 0);
   for (size_t i = 0; i < L.n; ++i) {
     // (a set-cover representative may have a larger index than its member)
-    if (cl[i] >= n_cl || (c.setcover ? rep[i] >= L.n : rep[i] > i)) die("inconsistent cluster result");
+    if (cl[i] >= n_cl || (setcover ? rep[i] >= L.n : rep[i] > i)) die("inconsistent cluster result");
     ++size[cl[i]];
   }
   size_t singletons = 0;
-  for (uint32_t s : size) singletons += s == 1;
+  for (uint32_t x : size) singletons += x == 1;
   for (const Level &v : more)
     for (size_t i = 0; i < L.n; ++i)
       if (v.cl[i] >= v.n_cl || v.rep[i] > i) die("inconsistent cluster result");
-  std::string o;
-  if (c.greedy || c.setcover) {
-    std::vector<uint32_t> pos(L.n);  // record -> processing position
-    for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
-    char num[16];
-    for (size_t i = 0; i < L.n; ++i) {
-      const uint32_t k = pos[i];
-      o += hg_sketch_file_get(L.f, i)->file_str;
-      o += '\t';
-      o += std::to_string(cl[k]);
-      o += '\t';
-      o += hg_sketch_file_get(L.f, perm[rep[k]])->file_str;
-      o.append(num, put_ani(num, ani[k]));  // "\t<ani>\n"
-    }
-  } else {
-    for (size_t i = 0; i < L.n; ++i) {
-      o += hg_sketch_file_get(L.f, i)->file_str;
-      o += '\t';
-      o += std::to_string(cl[i]);
-      o += '\t';
-      o += hg_sketch_file_get(L.f, rep[i])->file_str;
-      for (const Level &v : more) {  // (--levels: the same two columns per level)
-        o += '\t';
-        o += std::to_string(v.cl[i]);
-        o += '\t';
-        o += hg_sketch_file_get(L.f, v.rep[i])->file_str;
-      }
-      o += '\n';
-    }
-  }
-  FILE *f = std::fopen(c.out.c_str(), "wb");
-  if (!f || std::fwrite(o.data(), 1, o.size(), f) != o.size() || std::fclose(f) != 0) die("Dump cluster file failed!");
-  if (c.tree_given) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
-    std::string t;
-    char num[16];
-    for (const hg_ani_hit &e : tree) {
+  // one line per record, in file order: its name, "\t<cluster id>\t<name of the cluster's first member or representative>" for -a
+  // and for each level, then the ANI with the representative where there are representatives
+  std::vector<uint32_t> pos(L.n);  // record -> processing position
+  for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
+  write_tsv(c.out, c.threads, L.n,
+            [&](size_t i) {
+              size_t b = (size_t)L.len[i] + 12 + L.len[perm[rep[pos[i]]]] + 9;
+              for (const Level &v : more) b += 12 + L.len[v.rep[i]];
+              return b;
+            },
+            [&](size_t i, char *w) {
+              auto put_cluster = [&](char *o, uint32_t id, size_t r) {
+                size_t b = 0;
+                o[b++] = '\t', b += put_u32(o + b, id), o[b++] = '\t';
+                return b + L.put_name(o + b, r);
+              };
+              const uint32_t k = pos[i];
+              size_t b = L.put_name(w, i);
+              b += put_cluster(w + b, cl[k], perm[rep[k]]);
+              for (const Level &v : more) b += put_cluster(w + b, v.cl[i], v.rep[i]);
+              if (with_reps) return b + put_ani(w + b, ani[k]);  // "\t<ani>\n"
+              w[b++] = '\n';
+              return b;
+            },
+            "Dump cluster file failed!");
+  if (given(c, "tree")) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
+    for (const hg_ani_hit &e : tree)
       if (e.ref_idx >= L.n || e.qry_idx >= L.n) die("inconsistent cluster result");
-      t += hg_sketch_file_get(L.f, e.ref_idx)->file_str;
-      t += '\t';
-      t += hg_sketch_file_get(L.f, e.qry_idx)->file_str;
-      t.append(num, put_ani(num, e.ani));  // "\t<ani>\n"
-    }
-    FILE *ft = std::fopen(c.tree_out.c_str(), "wb");
-    if (!ft || std::fwrite(t.data(), 1, t.size(), ft) != t.size() || std::fclose(ft) != 0) die("Dump tree file failed!");
+    write_tsv(c.tree_out, c.threads, tree.size(), [&](size_t i) { return (size_t)L.len[tree[i].ref_idx] + L.len[tree[i].qry_idx] + 10; },
+              [&](size_t i, char *w) { return put_line(w, L, tree[i].ref_idx, L, tree[i].qry_idx, tree[i].ani); }, "Dump tree file failed!");
   }
   std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %.1f to file %s", L.n, n_cl,
                 singletons, th, c.out.c_str());
@@ -1204,7 +1156,7 @@ int run_cluster(const Cli &c) {
     std::vector<uint32_t> sz(v.n_cl, 0);
     for (size_t i = 0; i < L.n; ++i) ++sz[v.cl[i]];
     size_t single = 0;
-    for (uint32_t s : sz) single += s == 1;
+    for (uint32_t x : sz) single += x == 1;
     char lv[32];  // (one decimal like -a's line where that is the level, else as many digits as it needs)
     std::snprintf(lv, sizeof lv, "%.1f", (double)v.th);
     if (std::strtof(lv, nullptr) != v.th) std::snprintf(lv, sizeof lv, "%g", (double)v.th);
@@ -1212,11 +1164,8 @@ int run_cluster(const Cli &c) {
                   single, lv, c.out.c_str());
     logline("INFO", buf);
   }
-  std::snprintf(buf, sizeof buf, "Clustered %zu files took %.3fs", L.n,
-                std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  std::snprintf(buf, sizeof buf, "Clustered %zu files took %.3fs", L.n, now_s() - t0);
   logline("INFO", buf);
-  hg_sketch_file_free(L.f);
-  hg_multi_destroy(multi);
   return 0;
 }
 }  // namespace
@@ -1225,8 +1174,8 @@ int main(int argc, char **argv) {
   const Cli c = parse(argc, argv);
   // (a normal return: leaving through _exit once the outputs are closed saves the runtime's exit handlers -- 20-40 ms of a
   // 10 000 x 10 000 dist -- but those handlers are also where rocprofv3 and other tools write what they collected)
-  if (c.mode == "sketch") return run_sketch(c);
-  if (c.mode == "dist") return run_dist(c);
-  if (c.mode == "cluster") return run_cluster(c);
+  if (c.mode_bit == SKETCH) return run_sketch(c);
+  if (c.mode_bit == DIST) return run_dist(c);
+  if (c.mode_bit == CLUSTER) return run_cluster(c);
   return run_search(c);
 }
