@@ -89,6 +89,7 @@ struct Cli {
   bool order_size = false;     // --order file|size (cluster --linkage greedy)
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
+  bool hclust_average = false; // --hclust average (cluster): average linkage (UPGMA) on the dense matrix, a scheme of its own
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
   std::bitset<32> given;          // which options the command line carried, by row of `options`
@@ -193,6 +194,8 @@ const Option options[] = {
      "it chooses how cluster forms its clusters"},
     {"tree", 0, [](Cli &c, const Arg &a) { c.tree_out = a.file(); }, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
     {"levels", 0, take_levels, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
+    {"hclust", 0, [](Cli &c, const Arg &a) { c.hclust_average = a.choice({"average"}) == 0; }, CLUSTER,
+     "it chooses the hierarchical clustering of cluster"},
     {"columns", 0, take_columns, DIST, "it adds a pair's other metrics to the lines of dist", ONE_GPU_DIST},
     {"pairs", 0, [](Cli &c, const Arg &a) { c.pairs_file = a.file(); }, DIST, "it names the pairs dist evaluates", ONE_GPU_DIST},
     {"min_count", 0, [](Cli &c, const Arg &a) { c.min_count = (unsigned)a.uint(0xFFFFFFFFull, 1); }, SKETCH,
@@ -210,6 +213,70 @@ size_t option_row(const char *name) {
 }
 bool given(const Cli &c, const char *name) { return c.given[option_row(name)]; }
 
+// `hyper-gen --help`; `hyper-gen cluster --help` prints it too, with a paragraph on --hclust behind it
+void print_help() {
+  std::printf("HyperGen: Fast and memory-efficient genome sketching in hyperdimensional space (MI355X build)\n\n"
+              "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
+              "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
+              "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
+              "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy|setcover]\n"
+              "                    [--tree {output_tree}] [--levels L1,L2,...]\n\n"
+              "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
+              "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
+              "         -Q --quant_scale [1.0], -a --ani_th [85.0], -D --device [cpu]\n"
+              "extensions: -n --top_n [1] (search), --pack_layout avx2|naive [avx2] (sketch: the payload layout of\n"
+              "         reference hosts with / without AVX2; dist and search read both), --shards N (dist / search: N\n"
+              "         shards dealt round the visible GPUs; default one per GPU), cluster (single-linkage clusters at\n"
+              "         -a --ani_th [95.0] on the first visible GPU: one line per sketch, file, cluster id, file of the\n"
+              "         cluster's first member), --ani_metric mash|containment|max_containment [mash] (dist / search /\n"
+              "         cluster: containment = the share of the query's hashes found in the reference -- the identity of a\n"
+              "         fragment, a partial MAG or a draft with a larger genome; max_containment = the same against the\n"
+              "         smaller of the two; dist on one file with containment writes every ordered pair i != j; cluster\n"
+              "         takes mash or max_containment), --min_count N [1] (sketch: keep a sampled k-mer only if it occurs\n"
+              "         at least N times in the file -- for raw reads, where every sequencing error makes k-mers that occur\n"
+              "         once; 1 = every sampled k-mer, the reference's set), --search_path auto|hits|topk [auto] (search:\n"
+              "         topk selects the -n best per query on the device while blocks of the ANI matrix stream past -- memory\n"
+              "         does not grow with the number of pairs above -a; hits builds the thresholded hit list first; auto =\n"
+              "         topk for -n <= 64, hits beyond; both write the same file), --linkage single|greedy|setcover [single]\n"
+              "         (cluster: greedy = one representative per cluster, as dereplication tools choose them -- a sketch is\n"
+              "         a representative unless an earlier representative is within -a of it, else it joins the best such\n"
+              "         one; representatives are pairwise below -a, every member is within -a of its own; one line per\n"
+              "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative;\n"
+              "         setcover = greedy set cover, as MMseqs2 and Linclust cluster: the sketch with the most still-uncovered\n"
+              "         neighbours within -a becomes a representative and takes them as its members, ties to the first in\n"
+              "         the file, until none is left -- the guarantees and the lines of greedy, the representative chosen by\n"
+              "         coverage instead of file order; it holds the hits of the whole comparison, 12 bytes per pair within -a),\n"
+              "         --order file|size [file] (cluster --linkage greedy: the order the sketches are processed in; size =\n"
+              "         descending hv_norm_2, ties in file order -- the most complete genome of a group represents it;\n"
+              "         cluster ids count the representatives in that order, the lines stay in file order),\n"
+              "         --tree <file> (cluster --linkage single: the single-linkage tree at the floor -a -- the maximum-ANI\n"
+              "         spanning forest, genomes - clusters lines, strongest first: file, file, ANI as dist prints it; cut\n"
+              "         at any threshold >= -a it gives that threshold's clusters, its order is the merge order),\n"
+              "         --levels L1,L2,... (cluster --linkage single: 1 to 8 further thresholds, ascending, above -a, all from\n"
+              "         one comparison at -a; every line of -o becomes file, then for -a and each level the cluster id and\n"
+              "         the file of the cluster's first member),\n"
+              "         --columns LIST (dist: a comma list out of mash, containment, containment_ref, max_containment; every\n"
+              "         line gets one further field per name, in the order listed -- the pair's ANI under that metric, whatever\n"
+              "         --ani_metric selected the lines; containment_ref = the share of the reference's hashes found in the\n"
+              "         query; runs on the first visible GPU),\n"
+              "         --pairs FILE (dist: evaluate the pairs FILE lists, ref_name<TAB>qry_name[<TAB>anything] per line, names\n"
+              "         as -r and -q carry them -- a dist TSV can be fed back; one line per listed pair in the order of the\n"
+              "         list, ANI under --ani_metric, then the --columns fields; -a is not applied; runs on the first\n"
+              "         visible GPU)\n");
+}
+void print_cluster_help() {
+  print_help();
+  std::printf("\ncluster --hclust average: average linkage (UPGMA), the hierarchical clustering of dRep and of scipy's\n"
+              "         linkage(method=\"average\") on an ANI matrix, computed on the first visible GPU from the dense matrix of\n"
+              "         all pairs (8 bytes per pair; up to 65536 sketches).  Every ANI counts as dist prints it, in thousandths:\n"
+              "         the two clusters with the highest average ANI between their members merge, ties to the pair whose\n"
+              "         first members come first in the file, while that average is at least -a [95.0].  -o gets the lines of\n"
+              "         single linkage: file, cluster id, file of the cluster's first member.  --tree <file> writes the merges,\n"
+              "         genomes - clusters lines, every child before its parent: file of the first member of the cluster that\n"
+              "         stays, file of the first member of the one absorbed, average ANI of the merge as dist prints it, size\n"
+              "         of the merged cluster.  It is a scheme of its own: it does not go with --linkage or --levels.\n");
+}
+
 Cli parse(int argc, char **argv) {
   if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
   Cli c;
@@ -219,54 +286,7 @@ Cli parse(int argc, char **argv) {
     std::exit(0);
   }
   if (c.mode == "--help" || c.mode == "-h") {
-    std::printf("HyperGen: Fast and memory-efficient genome sketching in hyperdimensional space (MI355X build)\n\n"
-                "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
-                "  hyper-gen dist -r {ref_sketch} -q {query_sketch} -o {output_ANI_results}\n"
-                "  hyper-gen search -r {ref_sketch} -q {query_sketch} -o {top_hits_per_query} [-n top_n]\n"
-                "  hyper-gen cluster -p {sketch_file} -o {output_clusters} [-a 95.0] [--linkage single|greedy|setcover]\n"
-                "                    [--tree {output_tree}] [--levels L1,L2,...]\n\n"
-                "options: -p --path, -r --path_r, -q --path_q, -o --out, -t --thread [16], -m --sketch_method,\n"
-                "         -C --canonical [true], -k --ksize [21], -S --seed [123], -s --scaled [1500], -d --hv_d [4096],\n"
-                "         -Q --quant_scale [1.0], -a --ani_th [85.0], -D --device [cpu]\n"
-                "extensions: -n --top_n [1] (search), --pack_layout avx2|naive [avx2] (sketch: the payload layout of\n"
-                "         reference hosts with / without AVX2; dist and search read both), --shards N (dist / search: N\n"
-                "         shards dealt round the visible GPUs; default one per GPU), cluster (single-linkage clusters at\n"
-                "         -a --ani_th [95.0] on the first visible GPU: one line per sketch, file, cluster id, file of the\n"
-                "         cluster's first member), --ani_metric mash|containment|max_containment [mash] (dist / search /\n"
-                "         cluster: containment = the share of the query's hashes found in the reference -- the identity of a\n"
-                "         fragment, a partial MAG or a draft with a larger genome; max_containment = the same against the\n"
-                "         smaller of the two; dist on one file with containment writes every ordered pair i != j; cluster\n"
-                "         takes mash or max_containment), --min_count N [1] (sketch: keep a sampled k-mer only if it occurs\n"
-                "         at least N times in the file -- for raw reads, where every sequencing error makes k-mers that occur\n"
-                "         once; 1 = every sampled k-mer, the reference's set), --search_path auto|hits|topk [auto] (search:\n"
-                "         topk selects the -n best per query on the device while blocks of the ANI matrix stream past -- memory\n"
-                "         does not grow with the number of pairs above -a; hits builds the thresholded hit list first; auto =\n"
-                "         topk for -n <= 64, hits beyond; both write the same file), --linkage single|greedy|setcover [single]\n"
-                "         (cluster: greedy = one representative per cluster, as dereplication tools choose them -- a sketch is\n"
-                "         a representative unless an earlier representative is within -a of it, else it joins the best such\n"
-                "         one; representatives are pairwise below -a, every member is within -a of its own; one line per\n"
-                "         sketch: file, cluster id, file of its representative, ANI with it -- 100 for a representative;\n"
-                "         setcover = greedy set cover, as MMseqs2 and Linclust cluster: the sketch with the most still-uncovered\n"
-                "         neighbours within -a becomes a representative and takes them as its members, ties to the first in\n"
-                "         the file, until none is left -- the guarantees and the lines of greedy, the representative chosen by\n"
-                "         coverage instead of file order; it holds the hits of the whole comparison, 12 bytes per pair within -a),\n"
-                "         --order file|size [file] (cluster --linkage greedy: the order the sketches are processed in; size =\n"
-                "         descending hv_norm_2, ties in file order -- the most complete genome of a group represents it;\n"
-                "         cluster ids count the representatives in that order, the lines stay in file order),\n"
-                "         --tree <file> (cluster --linkage single: the single-linkage tree at the floor -a -- the maximum-ANI\n"
-                "         spanning forest, genomes - clusters lines, strongest first: file, file, ANI as dist prints it; cut\n"
-                "         at any threshold >= -a it gives that threshold's clusters, its order is the merge order),\n"
-                "         --levels L1,L2,... (cluster --linkage single: 1 to 8 further thresholds, ascending, above -a, all from\n"
-                "         one comparison at -a; every line of -o becomes file, then for -a and each level the cluster id and\n"
-                "         the file of the cluster's first member),\n"
-                "         --columns LIST (dist: a comma list out of mash, containment, containment_ref, max_containment; every\n"
-                "         line gets one further field per name, in the order listed -- the pair's ANI under that metric, whatever\n"
-                "         --ani_metric selected the lines; containment_ref = the share of the reference's hashes found in the\n"
-                "         query; runs on the first visible GPU),\n"
-                "         --pairs FILE (dist: evaluate the pairs FILE lists, ref_name<TAB>qry_name[<TAB>anything] per line, names\n"
-                "         as -r and -q carry them -- a dist TSV can be fed back; one line per listed pair in the order of the\n"
-                "         list, ANI under --ani_metric, then the --columns fields; -a is not applied; runs on the first\n"
-                "         visible GPU)\n");
+    print_help();
     std::exit(0);
   }
   static const char *const modes[] = {"sketch", "dist", "search", "cluster"};
@@ -277,6 +297,10 @@ Cli parse(int argc, char **argv) {
   if (c.mode_bit == CLUSTER) c.ani_th = 95.0f;
   for (int i = 2; i < argc; ++i) {
     Arg a{argv[i], "", nullptr};
+    if (c.mode_bit == CLUSTER && (a.flag == "--help" || a.flag == "-h")) {
+      print_cluster_help();
+      std::exit(0);
+    }
     const Option *o = nullptr;
     bool have_val = false;
     if (a.flag.rfind("--", 0) == 0) {
@@ -312,6 +336,10 @@ Cli parse(int argc, char **argv) {
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
+  if (c.hclust_average && given(c, "linkage"))
+    die("--hclust does not go with --linkage: average linkage is a scheme of its own, not one of --linkage's");
+  if (c.hclust_average && given(c, "levels"))
+    die("--levels is not supported with --hclust: it cuts the single-linkage tree, not the dendrogram of average linkage");
   if (given(c, "order") && c.mode_bit == CLUSTER && c.linkage == Linkage::setcover)
     die("--order is not supported by cluster --linkage setcover: the order the representatives are chosen in is the rule's own");
   if (given(c, "order") && !(c.mode_bit == CLUSTER && c.linkage == Linkage::greedy))
@@ -1044,6 +1072,9 @@ int run_search(const Cli &c) {
 // --linkage setcover (hg_cluster_setcover_dev): greedy set cover -- the sketch with the most still-uncovered neighbours
 // becomes a representative and takes them as its members.  The lines are those of greedy, in file order; a representative
 // may stand behind its members in the file.
+// --hclust average (hg_cluster_average_dev): average linkage on the dense matrix.  The lines of single linkage; --tree
+// writes the merges, every child before its parent: "<file_str of the name that stays>\t<file_str of the absorbed
+// name>\t<average ANI of the merge, as dist prints it>\t<size of the merged cluster>\n".
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
   const float th = c.ani_th;
@@ -1073,7 +1104,37 @@ int run_cluster(const Cli &c) {
   };
   std::vector<Level> more;
   std::vector<hg_ani_hit> tree;  // --tree / --levels
-  if (with_reps) {
+  struct Merge {                 // --hclust with --tree: the absorbed name, what it went into, the merge's average and size
+    uint32_t name, into, size;
+    float level;
+  };
+  std::vector<Merge> merges;
+  if (c.hclust_average) {
+    const bool want = given(c, "tree");
+    DevBuf<uint32_t> d_into(ctx), d_size(ctx);  // (NULL without --tree: the library then skips the dendrogram)
+    DevBuf<float> d_level(ctx);
+    if (want) d_into.alloc(L.n), d_size.alloc(L.n), d_level.alloc(L.n);
+    ck(ctx, hg_cluster_average_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(), d_cl.get(), d_into.get(), d_level.get(),
+                                   d_size.get(), &n_cl), "cluster");
+    debugf("average linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_average_rounds(ctx));
+    if (want) {
+      std::vector<uint32_t> into(L.n), sz(L.n);
+      std::vector<float> level(L.n);
+      d_into.download(into.data(), L.n), d_size.download(sz.data(), L.n), d_level.download(level.data(), L.n);
+      for (size_t i = 0; i < L.n; ++i) {
+        if (into[i] > i) die("inconsistent cluster result");
+        if (into[i] != i) merges.push_back(Merge{(uint32_t)i, into[i], sz[i], level[i]});
+      }
+      // averages never increase towards the root: by (level descending, size ascending, into, name) children come first
+      std::sort(merges.begin(), merges.end(), [](const Merge &x, const Merge &y) {
+        if (x.level != y.level) return x.level > y.level;
+        if (x.size != y.size) return x.size < y.size;
+        if (x.into != y.into) return x.into < y.into;
+        return x.name < y.name;
+      });
+      if (merges.size() != L.n - n_cl) die("inconsistent cluster result");
+    }
+  } else if (with_reps) {
     DevBuf<float> d_ani(ctx, L.n);
     ck(ctx, (setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(),
                                                                          d_cl.get(), d_ani.get(), &n_cl), "cluster");
@@ -1143,7 +1204,17 @@ int run_cluster(const Cli &c) {
               return b;
             },
             "Dump cluster file failed!");
-  if (given(c, "tree")) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
+  if (given(c, "tree") && c.hclust_average) {  // one line per merge: file of into, file of the absorbed name, level, size
+    write_tsv(c.tree_out, c.threads, merges.size(), [&](size_t i) { return (size_t)L.len[merges[i].into] + L.len[merges[i].name] + 22; },
+              [&](size_t i, char *w) {
+                size_t b = put_line(w, L, merges[i].into, L, merges[i].name, merges[i].level);
+                w[b - 1] = '\t';  // (put_line ends the line behind the ANI)
+                b += put_u32(w + b, merges[i].size);
+                w[b++] = '\n';
+                return b;
+              },
+              "Dump tree file failed!");
+  } else if (given(c, "tree")) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
     for (const hg_ani_hit &e : tree)
       if (e.ref_idx >= L.n || e.qry_idx >= L.n) die("inconsistent cluster result");
     write_tsv(c.tree_out, c.threads, tree.size(), [&](size_t i) { return (size_t)L.len[tree[i].ref_idx] + L.len[tree[i].qry_idx] + 10; },

@@ -90,6 +90,10 @@ int hg_device_count(void);
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "tree_rounds" = "<n>"         (rounds hg_cluster_tree* queue before they read the count of selecting roots back;
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
+ *       "average_rounds" = "<n>"      (rounds hg_cluster_average* queue before they read the round's merge count back;
+ *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
+ *       "average_block_rows" = "<n>"  (rows per block of the ANI matrix in hg_cluster_average_dev; 0 = automatic, from
+ *                                      HG_SEARCH_BLOCK_BYTES)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  * Nothing in the library reads environment variables. */
@@ -287,11 +291,11 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
  * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev} and hg_cluster_tree{,_dev} accept HG_ANI_MASH and
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev} and hg_cluster_average{,_dev} accept HG_ANI_MASH and
  * HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
- * hg_cluster_tree_hits_dev (they take hits), hg_dist_prep_ops_dev, the
+ * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev (it takes the matrix), hg_dist_prep_ops_dev, the
  * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
@@ -623,6 +627,58 @@ hg_status hg_cluster_tree(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, 
                           size_t *n_clusters);
 /* rounds of the last tree call on this ctx, summed over its blocks (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_tree_rounds(const hg_ctx *ctx);
+
+/* Average linkage, UPGMA (no reference counterpart): the hierarchical clustering genome pipelines run on an ANI matrix --
+ * dRep's primary clustering, scipy's linkage(method="average").  The pairs below the threshold enter the averages, so the
+ * scheme works on the dense matrix, not on a hit list.  Input: n items and ani(i, j) for i < j -- the float
+ * hg_dist_full_dev writes at [i, j] (reference i, query j) -- and ani_th.  Everything is decided on integers:
+ *   m(i, j)  = the integer `dist` prints for the pair, in thousandths: NaN and negative values 0, values above 100 100,
+ *              then rint((double)ani * 1000.0): 0 .. 100 000;
+ *   th_milli = the same of ani_th.  A NaN threshold merges nothing, a threshold above 100 merges nothing, ani_th <= 0
+ *              merges everything into one cluster;
+ *   a cluster is named by its smallest member, c(A) is its size, S(A, B) the sum of m(a, b) over a in A, b in B;
+ *   pair {A, B} is BETTER than {C, D} iff S(A,B) c(C) c(D) > S(C,D) c(A) c(B), compared exactly; on equality the pair
+ *   with the smaller lower name wins, then the pair with the smaller higher name;
+ *   while the best pair has S(A,B) >= th_milli c(A) c(B): merge it.  The merged cluster keeps the smaller name and
+ *   S(K, A u B) = S(K,A) + S(K,B).
+ * Results: rep[i] = the smallest index of i's cluster, cluster[i] = its dense id in increasing order of rep (the layout of
+ * hg_cluster_dev), *n_clusters their number.  The dendrogram, three optional arrays of n entries (each may be NULL): for a
+ * name B that was absorbed into A, into[B] = A, level[B] = (float)(((double)S / (double)(c(A) c(B))) / 1000.0) -- two IEEE
+ * double divisions and one conversion, nothing contracted --, size[B] = c(A) + c(B) right after the merge; for a name never
+ * absorbed into[i] = i, level[i] = 0, size[i] = the final size of its cluster.  The averages along a root path never
+ * increase (UPGMA is monotone): sorted by (level descending, size ascending, into, index) the absorbed entries list the
+ * merges with every child before its parent.
+ * Only integers are added and the comparisons are exact (128-bit cross products): the result depends on the matrix alone
+ * -- not on scheduling, block size or the rounds per readback -- and anyone can reproduce it from a `dist -a 0` TSV.
+ * On the device (hg_cluster_average.hip) the rule is resolved in rounds on a dense n x n matrix of u64 sums: every pair of
+ * mutual best partners merges at once, which is the sequential result because average linkage is reducible.  Per round
+ * average_best_kernel (one workgroup per live row: its best partner among the pairs that meet the threshold),
+ * average_pair_kernel (one lane per node: mutual pairs merge), average_rows_kernel (row A += row B) and
+ * average_cols_kernel (M[R][A] += M[R][B] in every surviving row).  The host queues "average_rounds" rounds
+ * (hg_ctx_set_debug; default 4) per readback of the round's merge count and stops at a round that merged nothing.  Groups
+ * of near-equal members take some tens of rounds; the worst case, a chain whose neighbour similarities fall with the index,
+ * takes O(n) rounds, and is accepted as the greedy resolution's path is.
+ * n <= HG_CLUSTER_AVERAGE_MAX_N (the matrix is 34 GB there; 800 MB at 10 000): beyond it HG_ERR_UNSUPPORTED before anything
+ * is allocated; a failed allocation is HG_ERR_OOM; the matrix is released before the call returns.  n == 0: HG_OK with
+ * *n_clusters = 0.  NULL rep, cluster or n_clusters: HG_ERR_INVALID.  Results are final on return; one clustering at a
+ * time per ctx.  Launches count under HG_T_DIST when timing is on.
+ *   hg_cluster_average_matrix_dev : d_ani, n x n floats, row-major; only [i, j] with i < j is read.  Independent of the
+ *                                   ctx's ANI metric.
+ *   hg_cluster_average_dev        : resident sketches (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT); the matrix is filled from
+ *                                   row blocks of hg_dist_full_dev -- rows [r0, r1) x columns [r0, n) in a scratch block of
+ *                                   at most HG_SEARCH_BLOCK_BYTES; debug key "average_block_rows" forces the row count.
+ *   hg_cluster_average            : host arrays in and out, staged through the ctx. */
+#define HG_CLUSTER_AVERAGE_MAX_N 65536u
+hg_status hg_cluster_average_matrix_dev(hg_ctx *ctx, const float *d_ani, size_t n, float ani_th, uint32_t *d_rep,
+                                        uint32_t *d_cluster, uint32_t *d_into, float *d_level, uint32_t *d_size, size_t *n_clusters);
+hg_status hg_cluster_average_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                                 float ani_th, uint32_t *d_rep, uint32_t *d_cluster, uint32_t *d_into, float *d_level,
+                                 uint32_t *d_size, size_t *n_clusters);
+hg_status hg_cluster_average(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                             float ani_th, uint32_t *rep, uint32_t *cluster, uint32_t *into, float *level, uint32_t *size,
+                             size_t *n_clusters);
+/* rounds of the last average-linkage call on this ctx, the one that merged nothing included (diagnostic; 0 = none yet) */
+uint64_t hg_ctx_cluster_average_rounds(const hg_ctx *ctx);
 
 /* ---- sketch compression (host side; src/hd.rs:114-232) -------------------------------- */
 uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d);
