@@ -1,23 +1,13 @@
 // hg_api.hip -- the C ABI of include/hypergen.h, part 1: context, streams, workspaces, timing brackets, memory helpers.
 // (hg_api_sketch.hip: the sketch entry points; hg_api_dist.hip: the dist entry points.)  No CPU fallback lives anywhere:
 // every compute entry point runs HIP kernels or fails.
-#include <algorithm>
 #include <atomic>
-#include <cctype>
-#include <cstdio>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <mutex>
+#include <new>
+#include <string>
 #include <thread>
-#include <vector>
-
-#include <chrono>
-#include <functional>
-#include <memory>
-#include <sched.h>
-
-#include "hg_host.h"
 
 #include "hg_internal.h"
 
@@ -164,6 +154,7 @@ extern "C" hg_status hg_ctx_set_debug(hg_ctx *c, const char *key, const char *va
   else if (k == "dist_order") c->dbg_dist_order = v;  // "plain": no diagonal-first tile order
   else if (k == "ham_path") c->dbg_ham_path = v;
   else if (k == "hostfed") c->dbg_hostfed = v;  // hg_sketch_batch / hg_kmer_hash_sample: "ascii" never 2-bit pack on the host, "packed" always
+  else if (k == "hostfed_stage_bytes") c->dbg_hostfed_stage_bytes = std::strtoull(v.c_str(), nullptr, 10);  // hg_sketch_batch: bytes at which a sub-batch closes
   else if (k == "sketch_path") c->dbg_sketch_path = v;  // "sync": every sketch step takes the synchronous path (counters read back between sort and encode)
   else if (k == "kmer_input") c->dbg_kmer_input = v;  // "packed": ASCII batches are 2-bit packed on the device first and take the packed kernels
   else return hg_fail(c, HG_ERR_INVALID, "unknown debug key " + k);

@@ -1,22 +1,6 @@
 // hg_api_dist.hip -- the C ABI of include/hypergen.h, part 3: the dist path -- full and thresholded ANI matrices of device- or
 // host-resident hypervectors, blocks of a larger matrix, operands prepared where the rows live (src/dist.rs:139-161,231-294).
 #include <algorithm>
-#include <atomic>
-#include <cctype>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <vector>
-
-#include <chrono>
-#include <functional>
-#include <memory>
-#include <sched.h>
-
-#include "hg_host.h"
 
 #include "hg_internal.h"
 

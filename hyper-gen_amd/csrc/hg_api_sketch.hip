@@ -1,23 +1,23 @@
 // hg_api_sketch.hip -- the C ABI of include/hypergen.h, part 2: the sketch path -- batch plans, hash + sample -> sort / unique ->
 // encode over the genomes of a batch (device-resident, host-fed with uploads and host-side 2-bit packing under them, one
 // genome per call), page-locked read buffers.  What src/sketch.rs:35-56 and src/sketch_cuda.rs:79-166 do per file.
+// The host-fed batch reads top to bottom in hg_sketch_batch: decide and lay out (hg_hostfed_layout.h, arithmetic only), then an
+// uploader with one function per upload route, a consumer and a closing read-back, the two threads joined by a Handover (hg_host.h).
 #include <algorithm>
 #include <atomic>
 #include <cctype>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include <vector>
-
 #include <chrono>
+#include <cstdio>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <sched.h>
+#include <string>
+#include <thread>
+#include <vector>
 
 #include "hg_host.h"
+#include "hg_hostfed_layout.h"
 
 #include "hg_sketch.h"
 
@@ -125,13 +125,6 @@ extern "C" hg_status hg_read_fastx_pinned(const char *path, uint32_t mode, uint8
 extern "C" void hg_pinned_free(void *p) {
   if (p) (void)hipHostFree(p);
 }
-
-// Host-fed batch.  The batch is cut into sub-batches of about HG_STAGE_BYTES; a helper thread queues their
-// uploads on the context's copy stream (one event per sub-batch) while this thread runs hash/sort/encode
-// of the sub-batches already on the device, so PCIe transfer and kernels overlap for pinned and for
-// pageable caller memory alike (a pageable hipMemcpyAsync blocks the thread that issues it).
-constexpr uint64_t HG_STAGE_BYTES = 64ull << 20;
-constexpr uint64_t HG_PACK_BYTES = HG_STAGE_BYTES + (2ull << 20);  // a sub-batch of genomes < 1 MiB each fits
 
 // Host threads the library may use for its own host-side work on a call (2-bit packing of a host-fed batch): the cores
 // this process may run on, at most 16 -- the reference's default `-t` (src/utils.rs:54-56).
@@ -247,6 +240,198 @@ static hipError_t pack_buf_for(hg_ctx *c, int b, size_t need) {
   return hipSuccess;
 }
 
+// One genome, 2-bit packed by the calling thread into staging buffer 0 (the whole genome as one piece, timed for
+// pack_single()'s sake) and queued for d_dst on `stream`: hg_kmer_hash_sample and the n = 1 of hg_sketch_batch.
+static hipError_t upload_one_packed(hg_ctx *c, const SingleChoice &single, const uint8_t *seq, uint64_t n_bps, uint32_t norm_mode,
+                                    void *d_dst, hipStream_t stream) {
+  const size_t bytes = hg_pack2_size(n_bps);
+  hipError_t e = pack_buf_for(c, 0, bytes);
+  if (e != hipSuccess) return e;
+  const auto t0 = std::chrono::steady_clock::now();
+  hg_pack2_piece(seq, n_bps, norm_mode, static_cast<uint8_t *>(c->pack_buf[0]), 0, n_bps);
+  pack_measured(single, n_bps, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  if ((e = hipMemcpyAsync(d_dst, c->pack_buf[0], bytes, hipMemcpyHostToDevice, stream)) == hipSuccess) e = hipEventRecord(c->pack_ev[0], stream);
+  c->pack_used[0] = true;
+  return e;
+}
+
+// ---- host-fed batch -------------------------------------------------------------------------------------------------
+// The batch is cut into sub-batches of about HG_STAGE_BYTES (hg_hostfed_layout.h: the decision to pack, the layout, the
+// upload routes and the packing tasks, as arithmetic); a helper thread queues their uploads on the context's copy stream
+// (one event per sub-batch) while the calling thread runs hash/sort/encode of the sub-batches already on the device, so PCIe
+// transfer and kernels overlap for pinned and for pageable caller memory alike (a pageable hipMemcpyAsync blocks the thread
+// that issues it).
+namespace {
+struct HostfedDev {  // the device side of a call
+  uint8_t *seq;
+  int16_t *hv;
+  int32_t *n2;
+  uint32_t *nh;
+  size_t hv_bytes;
+  hipStream_t up_stream;  // one sub-batch (the n = 1 of a one-call-per-genome pool above all): its upload goes on the context's
+  bool one_stream;        // own stream, in front of its kernels -- no second stream, no event to wait for
+};
+
+// What the uploader reads.  It writes (1) lay->subs[j].packed of the sub-batches j behind the first, while it works on the
+// first: the consumer reads subs[j] after done->wait(j) has returned; (2) the context's staging buffers (pack_buf, pack_cap,
+// pack_ev, pack_used), which the calling thread touches again only after it has joined the uploader.
+struct HostfedUpload {
+  hg_ctx *c;
+  const uint8_t *const *seqs;
+  HostfedLayout *lay;
+  HostfedDev dev;
+  CallPool *pool;         // packed route (nullptr: `single` packs)
+  uint32_t norm_mode;
+  SingleChoice single;    // n = 1, packed by pack_single()'s choice
+  bool src_pinned;
+  int pack_node;          // NUMA node the pool's threads run on
+  unsigned threads;
+  Handover *done;
+};
+
+// 2-bit pack the sub-batch into page-locked staging (all host threads of the call), then ONE upload
+hipError_t upload_packed(const HostfedUpload &u, size_t k) {
+  hg_ctx *c = u.c;
+  HostfedLayout &lay = *u.lay;
+  const HostfedSub sub = lay.subs[k];
+  const size_t n = lay.lens.size();
+  if (u.single.packed) return upload_one_packed(c, u.single, u.seqs[0], lay.lens[0], u.norm_mode, u.dev.seq, u.dev.up_stream);
+  const int b = (int)(k & 1);
+  hipError_t e = pack_buf_for(c, b, n == 1 ? sub.pk_bytes : HG_PACK_BYTES);
+  if (e != hipSuccess) return e;
+  auto *pin = static_cast<uint8_t *>(c->pack_buf[b]);
+  const HostfedPackWork w = lay.pack_work(k);
+  const auto t0 = std::chrono::steady_clock::now();
+  u.pool->run(w.tasks(), [&](size_t t) {
+    for (size_t i = w.task_first[t]; i < w.task_first[t + 1]; ++i) {
+      const HostfedPackWork::Piece &pc = w.pieces[i];
+      hg_pack2_piece(u.seqs[pc.g], lay.lens[pc.g], u.norm_mode, pin + (lay.boffs[pc.g] - lay.boffs[sub.g0]), pc.b0, pc.b1);
+    }
+  });
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // Packing has to outrun the link to be worth it: the first packed sub-batch is timed, and the rest goes as ASCII when the
+  // host is too slow.  (Page-locked sources go at ~55 GB/s as ASCII; pageable ones through the runtime's bounce buffer at
+  // ~12 GB/s: a host whose cores are capped by a cgroup quota -- host_threads() cannot see one -- may pack slower than even that)
+  if (k == 0 && (double)sub.span < (u.src_pinned ? 55e9 : 12e9) * sec && c->dbg_hostfed != "packed") lay.demote_after(k);
+  if ((e = hipMemcpyAsync(u.dev.seq + lay.boffs[sub.g0], pin, sub.pk_bytes, hipMemcpyHostToDevice, u.dev.up_stream)) == hipSuccess)
+    e = hipEventRecord(c->pack_ev[b], u.dev.up_stream);
+  c->pack_used[b] = true;
+  return e;
+}
+
+// many small genomes: into page-locked staging in the device layout, then ONE upload
+hipError_t upload_staged(const HostfedUpload &u, size_t k) {
+  hg_ctx *c = u.c;
+  const HostfedLayout &lay = *u.lay;
+  const HostfedSub &sub = lay.subs[k];
+  const int b = (int)(k & 1);
+  hipError_t e = pack_buf_for(c, b, HG_PACK_BYTES);
+  if (e != hipSuccess) return e;
+  auto *pin = static_cast<uint8_t *>(c->pack_buf[b]);
+  for (size_t g = sub.g0; g < sub.g1; ++g)
+    if (lay.lens[g]) std::memcpy(pin + (lay.offs[g] - lay.offs[sub.g0]), u.seqs[g], lay.lens[g]);
+  if ((e = hipMemcpyAsync(u.dev.seq + lay.offs[sub.g0], pin, sub.span, hipMemcpyHostToDevice, u.dev.up_stream)) == hipSuccess)
+    e = hipEventRecord(c->pack_ev[b], u.dev.up_stream);
+  c->pack_used[b] = true;
+  return e;
+}
+
+// one copy per genome, from where the caller has it
+hipError_t upload_direct(const HostfedUpload &u, size_t k) {
+  const HostfedLayout &lay = *u.lay;
+  hipError_t e = hipSuccess;
+  for (size_t g = lay.subs[k].g0; g < lay.subs[k].g1 && e == hipSuccess; ++g)
+    if (lay.lens[g]) e = hipMemcpyAsync(u.dev.seq + lay.offs[g], u.seqs[g], lay.lens[g], hipMemcpyHostToDevice, u.dev.up_stream);
+  return e;
+}
+
+// The uploader: queues every sub-batch's upload (and its event) and publishes it; on an error it releases the consumer, which
+// then reports it.  Runs on a thread of its own when there is more than one sub-batch.
+void hostfed_upload(const HostfedUpload &u) {
+  const size_t n_subs = u.lay->subs.size();
+  hipError_t e = hipSetDevice(u.c->device);
+  if (n_subs > 1) (void)hg_bind_thread_to_numa_node(u.pack_node, u.threads);  // (the helper thread only, never the caller's)
+  for (size_t k = 0; k < n_subs && e == hipSuccess; ++k) {
+    switch (u.lay->route(k)) {
+      case HostfedRoute::PACKED: e = upload_packed(u, k); break;
+      case HostfedRoute::STAGED: e = upload_staged(u, k); break;
+      case HostfedRoute::DIRECT: e = upload_direct(u, k); break;
+    }
+    if (e == hipSuccess && !u.dev.one_stream) e = hipEventRecord(u.c->copy_events[k], u.dev.up_stream);
+    if (e == hipSuccess) u.done->publish(k + 1);
+  }
+  if (e != hipSuccess) u.done->fail((int)e);
+}
+
+// device buffers for sequence and results; more than one sub-batch: the copy stream and an event per sub-batch
+hg_status hostfed_ensure(hg_ctx *c, const HostfedLayout &lay, const hg_sketch_params *p, HostfedDev &dev) {
+  const size_t n = lay.lens.size(), n_subs = lay.subs.size();
+  hg_status s;
+  dev.hv_bytes = n * (size_t)p->hv_d * sizeof(int16_t);
+  if ((s = hg_ensure(c, c->w_seq, lay.total + 64)) != HG_OK) return s;
+  if ((s = hg_ensure(c, c->w_hv, dev.hv_bytes + n * 8 + 64)) != HG_OK) return s;
+  dev.seq = static_cast<uint8_t *>(c->w_seq.p);
+  dev.hv = static_cast<int16_t *>(c->w_hv.p);
+  dev.n2 = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(c->w_hv.p) + ((dev.hv_bytes + 15) & ~(size_t)15));
+  dev.nh = reinterpret_cast<uint32_t *>(dev.n2 + n);
+  dev.one_stream = n_subs == 1;
+  if (!dev.one_stream && !c->copy_stream) HG_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  dev.up_stream = dev.one_stream ? c->stream : c->copy_stream;
+  while (!dev.one_stream && c->copy_events.size() < n_subs) {
+    hipEvent_t e;
+    HG_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    c->copy_events.push_back(e);
+  }
+  return HG_OK;
+}
+
+// The pool's threads run on the NUMA node the sequences lie on (page-locked memory from the HIP runtime: the device's node,
+// like the staging buffers they write; packing from the other socket is ~1.5x slower), the uploader thread too.
+int hostfed_pack_node(const hg_ctx *c, const uint8_t *const *seqs, const size_t *lens, size_t n) {
+  for (size_t g = 0; g < n; ++g)
+    if (lens[g]) {
+      const int node = hg_numa_node_of(seqs[g]);
+      if (node >= 0) return node;
+    }
+  return hg_device_numa_node(c->device);
+}
+
+// The consumer: sketches every sub-batch as its upload is queued and queues the copy of its HVs back
+hg_status hostfed_consume(hg_ctx *c, const HostfedLayout &lay, const HostfedDev &dev, Handover &done, const hg_sketch_params *p,
+                          int16_t *hv_out) {
+  hg_status s = HG_OK;
+  for (size_t k = 0; k < lay.subs.size() && s == HG_OK; ++k) {
+    const int err = done.wait(k);
+    if (err) return hg_fail(c, HG_ERR_HIP, std::string("sequence upload: ") + hipGetErrorString((hipError_t)err));
+    const HostfedSub &sub = lay.subs[k];
+    const size_t g0 = sub.g0, m = sub.g1 - g0, row = (size_t)p->hv_d;
+    hipError_t e = dev.one_stream ? hipSuccess : hipStreamWaitEvent(c->stream, c->copy_events[k], 0);
+    if (e != hipSuccess) return hg_fail(c, HG_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
+    if (sub.packed)
+      s = hg_sketch_batch_dev_packed(c, dev.seq, lay.boffs.data() + g0, lay.lens.data() + g0, m, p, dev.hv + g0 * row, dev.n2 + g0, dev.nh + g0);
+    else
+      s = hg_sketch_batch_dev(c, dev.seq, lay.offs.data() + g0, lay.lens.data() + g0, m, p, dev.hv + g0 * row, dev.n2 + g0, dev.nh + g0);
+    if (s != HG_OK) return s;
+    e = hipMemcpyAsync(hv_out + g0 * row, dev.hv + g0 * row, m * row * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) s = hg_fail(c, HG_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+  }
+  return s;
+}
+
+// Closes the call: the last sub-batch's check word (the earlier ones were read as their successors were queued), all HVs
+// again when a step was redone (it leaves stale rows in the copies queued behind it), norms and counts.
+hg_status hostfed_finish(hg_ctx *c, const HostfedDev &dev, size_t n, uint64_t redone_before, int16_t *hv_out, int32_t *norm2_out,
+                         uint32_t *nhash_out) {
+  const hg_status s = hg_sketch_resolve(c);
+  if (s != HG_OK) return s;
+  if (c->n_redone_steps != redone_before) HG_HIP(c, hipMemcpyAsync(hv_out, dev.hv, dev.hv_bytes, hipMemcpyDeviceToHost, c->stream));
+  HG_HIP(c, hipMemcpyAsync(norm2_out, dev.n2, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HG_HIP(c, hipMemcpyAsync(nhash_out, dev.nh, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HG_HIP(c, hipStreamSynchronize(c->stream));
+  return HG_OK;
+}
+}  // namespace
+
 extern "C" hg_status hg_sketch_batch(hg_ctx *c, const uint8_t *const *seqs, const size_t *lens, size_t n,
                                      const hg_sketch_params *p, int16_t *hv_out, int32_t *norm2_out,
                                      uint32_t *nhash_out) {
@@ -256,207 +441,39 @@ extern "C" hg_status hg_sketch_batch(hg_ctx *c, const uint8_t *const *seqs, cons
   if (n == 0) return HG_OK;
   if (!seqs || !lens || !hv_out || !norm2_out || !nhash_out) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
   HG_ENTER(c);
-  // The link is what limits this entry point (50 GB/s = 10 k genomes/s of 5 Mbp as ASCII): a batch that is worth it goes
-  // over as 2-bit packed bases -- hg_pack2 blobs, 0.375 bytes per base, packed by a few host threads of this call into the
-  // page-locked staging buffers while the previous sub-batch uploads -- and is sketched by the packed-input kernels
-  // (bit-identical results).  Needs cores: with fewer than 4 usable ones the ASCII path stays.  Hook: "hostfed" = "ascii".
-  // A call that hands over little (the n = 1 of the one-call-per-genome pattern) packs on its own thread, when
-  // pack_single() says the link is contended.
-  HostfedCall in_flight;
-  unsigned P = host_threads();
   uint64_t all_bytes = 0;
-  for (size_t g = 0; g < n; ++g) all_bytes += lens[g];
-  // (batches of genomes below 1 kbp on average stay ASCII: hg_pack2 blobs carry 32 bytes of padding each)
-  bool want_pack = (P >= 4 && all_bytes >= (32ull << 20) && all_bytes / n >= (1u << 10) && c->dbg_hostfed != "ascii") ||
-                   (n > 1 && c->dbg_hostfed == "packed");
-  if (want_pack) P = std::max(1u, P / (unsigned)(1 + in_flight.others));
-  SingleChoice single;
-  if (!want_pack && n == 1) {
-    single = pack_single(c, seqs[0], lens[0], in_flight.others);
-    if (single.packed) want_pack = true, P = 1;
-  }
-  const uint64_t stage_bytes = want_pack ? 2 * HG_STAGE_BYTES : HG_STAGE_BYTES;  // (packed: 48 MB per upload)
-  // device layout: 16-byte aligned starts, 64 bytes of slack; sub-batch boundaries by bytes
-  std::vector<uint64_t> offs(n), l64(n), boffs(n);
-  std::vector<size_t> cut{0};
-  uint64_t total = 0, in_chunk = 0;
   for (size_t g = 0; g < n; ++g) {
     if (lens[g] && !seqs[g]) return hg_fail(c, HG_ERR_INVALID, "NULL sequence");
-    if (in_chunk >= stage_bytes) cut.push_back(g), in_chunk = 0;
-    offs[g] = total, l64[g] = lens[g];
-    const uint64_t padded = (lens[g] + 15) & ~(uint64_t)15;
-    total += padded, in_chunk += padded;
+    all_bytes += lens[g];
   }
-  cut.push_back(n);
-  const size_t n_chunks = cut.size() - 1;
-  // packed sub-batches: blob g of sub-batch k at the sub-batch's own start in the device buffer (its ASCII region is
-  // larger than its blobs) + the sum of the blob sizes in front of it; a sub-batch whose blobs outgrow a staging buffer
-  // (one huge genome) stays ASCII
-  std::vector<uint8_t> sub_packed(n_chunks, 0);
-  std::vector<uint64_t> sub_pk_bytes(n_chunks, 0);
-  if (want_pack) {
-    for (size_t k = 0; k < n_chunks; ++k) {
-      uint64_t at = 0;
-      for (size_t g = cut[k]; g < cut[k + 1]; ++g) boffs[g] = offs[cut[k]] + at, at += hg_pack2_size(lens[g]);
-      sub_pk_bytes[k] = at;
-      // ... and one whose blobs outgrow its own ASCII region (hg_pack2_size is 32 for 1..16 bases, their padded ASCII 16:
-      // a sub-batch of very short sequences) stays ASCII too -- its blobs would run into the next sub-batch's region, or,
-      // for the last one, past the end of the buffer
-      const uint64_t span = offs[cut[k + 1] - 1] + ((lens[cut[k + 1] - 1] + 15) & ~(uint64_t)15) - offs[cut[k]];
-      sub_packed[k] = at <= HG_PACK_BYTES && at <= span && at > 0;
-    }
-  }
+  // decide: packed or ASCII, with how many threads.  A call that hands over little (the n = 1 of the one-call-per-genome
+  // pattern) packs on its own thread, when pack_single() says the link is contended.
+  HostfedCall in_flight;
+  const HostfedHook hook = c->dbg_hostfed == "ascii" ? HOSTFED_ASCII : c->dbg_hostfed == "packed" ? HOSTFED_PACKED : HOSTFED_AUTO;
+  HostfedDecision d = hostfed_decide(host_threads(), all_bytes, n, in_flight.others, hook);
+  SingleChoice single;
+  if (!d.want_pack && n == 1 && (single = pack_single(c, seqs[0], lens[0], in_flight.others)).packed) d = {true, 1};
+  HostfedLayout lay(lens, n, d.want_pack, hostfed_stage_bytes(d.want_pack, c->dbg_hostfed_stage_bytes), HG_PACK_BYTES);
+  HostfedDev dev;
+  if ((s = hostfed_ensure(c, lay, p, dev)) != HG_OK) return s;
+  const int pack_node = d.want_pack && d.threads > 1 ? hostfed_pack_node(c, seqs, lens, n) : -1;
   std::unique_ptr<CallPool> pool;
-  // The pool's threads run on the NUMA node the sequences lie on (page-locked memory from the HIP runtime: the device's node,
-  // like the staging buffers they write; packing from the other socket is ~1.5x slower), the uploader thread too.
-  int pack_node = -1;
-  if (want_pack && P > 1) {
-    for (size_t g = 0; g < n && pack_node < 0; ++g)
-      if (lens[g]) pack_node = hg_numa_node_of(seqs[g]);
-    if (pack_node < 0) pack_node = hg_device_numa_node(c->device);
-  }
-  if (want_pack) pool.reset(new CallPool(P, pack_node));  // (takes the threads it can get)
-  // packing has to outrun the link to be worth it from page-locked sources (ASCII goes at ~50 GB/s from those): the
-  // uploader times its first packed sub-batch and leaves the rest as ASCII when the host is too slow for that
-  const bool src_pinned = want_pack && n > 1 && host_pinned(seqs[0]);
-  if ((s = hg_ensure(c, c->w_seq, total + 64)) != HG_OK) return s;
-  const size_t hv_bytes = n * (size_t)p->hv_d * sizeof(int16_t);
-  if ((s = hg_ensure(c, c->w_hv, hv_bytes + n * 8 + 64)) != HG_OK) return s;
-  auto *d_seq = static_cast<uint8_t *>(c->w_seq.p);
-  auto *d_hv = static_cast<int16_t *>(c->w_hv.p);
-  auto *d_n2 = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(c->w_hv.p) + ((hv_bytes + 15) & ~(size_t)15));
-  auto *d_nh = reinterpret_cast<uint32_t *>(d_n2 + n);
-  // one sub-batch (the n = 1 of a one-call-per-genome pool above all): its upload goes on the context's own stream, in
-  // front of its kernels -- no second stream, no event to wait for
-  const bool one_stream = n_chunks == 1;
-  if (!one_stream && !c->copy_stream) HG_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  const hipStream_t up_stream = one_stream ? c->stream : c->copy_stream;
-  while (!one_stream && c->copy_events.size() < n_chunks) {
-    hipEvent_t e;
-    HG_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->copy_events.push_back(e);
-  }
-
-  const uint64_t redone_before = c->n_redone_steps;  // (a sub-batch whose step is run again leaves stale rows in the copies queued behind it)
-  std::mutex mu;
-  std::condition_variable cv;
-  size_t queued = 0;  // sub-batches whose uploads and event are queued
-  hipError_t copy_err = hipSuccess;
-  auto upload = [&](size_t first_chunk) {
-    hipError_t e = hipSetDevice(c->device);
-    if (n_chunks > 1) (void)hg_bind_thread_to_numa_node(pack_node, P);  // (the helper thread only, never the caller's)
-    for (size_t k = first_chunk; k < n_chunks; ++k) {
-      const size_t g0 = cut[k], g1 = cut[k + 1];
-      const uint64_t span = offs[g1 - 1] + ((l64[g1 - 1] + 15) & ~(uint64_t)15) - offs[g0];
-      if (sub_packed[k]) {
-        // 2-bit pack the sub-batch into page-locked staging (all host threads of the call), then ONE upload
-        const int b = (int)(k & 1);
-        if (e == hipSuccess) e = pack_buf_for(c, b, n == 1 ? sub_pk_bytes[k] : HG_PACK_BYTES);
-        if (e == hipSuccess) {
-          auto *pin = static_cast<uint8_t *>(c->pack_buf[b]);
-          // pieces of 1 Mbase, so that the threads finish together whatever the genome sizes
-          constexpr uint64_t PIECE = 1ull << 20;
-          std::vector<std::pair<size_t, uint64_t>> pieces;
-          for (size_t g = g0; g < g1; ++g)
-            for (uint64_t b = 0; b < lens[g]; b += PIECE) pieces.emplace_back(g, b);
-          // ... handed out in runs of at least 256 kbase: a task per 5 kbp genome cost more in the pool's hand-overs than
-          // in packing (100 000 x 5 kbp: 107 ms packed against 30 ms as ASCII through one staging copy)
-          std::vector<size_t> task_first{0};
-          {
-            uint64_t in_task = 0;
-            for (size_t i = 0; i < pieces.size(); ++i) {
-              if (in_task >= (256u << 10)) task_first.push_back(i), in_task = 0;
-              in_task += std::min<uint64_t>(lens[pieces[i].first] - pieces[i].second, PIECE);
-            }
-            task_first.push_back(pieces.size());
-          }
-          const auto t0 = std::chrono::steady_clock::now();
-          pool->run(task_first.size() - 1, [&](size_t t) {
-            for (size_t i = task_first[t]; i < task_first[t + 1]; ++i) {
-              const size_t g = pieces[i].first;
-              const uint64_t b = pieces[i].second;
-              hg_pack2_piece(seqs[g], lens[g], p->norm_mode, pin + (boffs[g] - boffs[g0]), b, std::min<uint64_t>(lens[g], b + PIECE));
-            }
-          });
-          const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-          // (page-locked sources go at ~55 GB/s as ASCII; pageable ones through the runtime's bounce buffer at ~12 GB/s: a
-          // host whose cores are capped by a cgroup quota -- host_threads() cannot see one -- may pack slower than even that)
-          if (n > 1 && k == first_chunk && (double)span < (src_pinned ? 55e9 : 12e9) * sec && c->dbg_hostfed != "packed")
-            for (size_t j = k + 1; j < n_chunks; ++j) sub_packed[j] = 0;
-          if (n == 1) pack_measured(single, lens[0], sec);
-          if (e == hipSuccess) e = hipMemcpyAsync(d_seq + boffs[g0], pin, sub_pk_bytes[k], hipMemcpyHostToDevice, up_stream);
-          if (e == hipSuccess) e = hipEventRecord(c->pack_ev[b], up_stream);
-          c->pack_used[b] = true;
-        }
-      } else if (g1 - g0 >= 16 && span / (g1 - g0) < ((uint64_t)1 << 20) && span <= HG_PACK_BYTES) {
-        // many small genomes: pack them into pinned memory (device layout) and upload once -- a
-        // hipMemcpyAsync per 2 kbp genome costs more than the genome
-        const int b = (int)(k & 1);
-        if (e == hipSuccess) e = pack_buf_for(c, b, HG_PACK_BYTES);
-        if (e == hipSuccess) {
-          auto *pin = static_cast<uint8_t *>(c->pack_buf[b]);
-          for (size_t g = g0; g < g1; ++g)
-            if (lens[g]) std::memcpy(pin + (offs[g] - offs[g0]), seqs[g], lens[g]);
-          e = hipMemcpyAsync(d_seq + offs[g0], pin, span, hipMemcpyHostToDevice, up_stream);
-          if (e == hipSuccess) e = hipEventRecord(c->pack_ev[b], up_stream);
-          c->pack_used[b] = true;
-        }
-      } else {
-        for (size_t g = g0; g < g1 && e == hipSuccess; ++g)
-          if (lens[g]) e = hipMemcpyAsync(d_seq + offs[g], seqs[g], lens[g], hipMemcpyHostToDevice, up_stream);
-      }
-      if (e == hipSuccess && !one_stream) e = hipEventRecord(c->copy_events[k], up_stream);
-      std::lock_guard<std::mutex> lk(mu);
-      if (e != hipSuccess) copy_err = e;
-      queued = e == hipSuccess ? k + 1 : n_chunks;  // on error release the consumer, which then reports it
-      cv.notify_all();
-      if (e != hipSuccess) return;
-    }
-  };
+  if (d.want_pack && !single.packed) pool.reset(new CallPool(d.threads, pack_node));  // (takes the threads it can get)
+  const bool src_pinned = d.want_pack && n > 1 && host_pinned(seqs[0]);
+  const uint64_t redone_before = c->n_redone_steps;
+  Handover done;
+  const HostfedUpload up{c, seqs, &lay, dev, pool.get(), p->norm_mode, single, src_pinned, pack_node, d.threads, &done};
   std::thread uploader;
-  if (n_chunks > 1) uploader = std::thread(upload, (size_t)0);
-  else upload(0);
-  s = HG_OK;
-  for (size_t k = 0; k < n_chunks && s == HG_OK; ++k) {
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      cv.wait(lk, [&] { return queued > k; });
-      if (copy_err != hipSuccess) {
-        s = hg_fail(c, HG_ERR_HIP, std::string("sequence upload: ") + hipGetErrorString(copy_err));
-        break;
-      }
-    }
-    const size_t g0 = cut[k], m = cut[k + 1] - g0;
-    hipError_t e = one_stream ? hipSuccess : hipStreamWaitEvent(c->stream, c->copy_events[k], 0);
-    if (e != hipSuccess) {
-      s = hg_fail(c, HG_ERR_HIP, std::string("hipStreamWaitEvent: ") + hipGetErrorString(e));
-      break;
-    }
-    if (sub_packed[k])
-      s = hg_sketch_batch_dev_packed(c, d_seq, boffs.data() + g0, l64.data() + g0, m, p, d_hv + g0 * (size_t)p->hv_d, d_n2 + g0,
-                                     d_nh + g0);
-    else
-      s = hg_sketch_batch_dev(c, d_seq, offs.data() + g0, l64.data() + g0, m, p, d_hv + g0 * (size_t)p->hv_d, d_n2 + g0,
-                              d_nh + g0);
-    if (s != HG_OK) break;
-    e = hipMemcpyAsync(hv_out + g0 * (size_t)p->hv_d, d_hv + g0 * (size_t)p->hv_d, m * (size_t)p->hv_d * sizeof(int16_t),
-                       hipMemcpyDeviceToHost, c->stream);
-    if (e != hipSuccess) s = hg_fail(c, HG_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-  }
+  if (lay.subs.size() > 1) uploader = std::thread(hostfed_upload, std::cref(up));
+  else hostfed_upload(up);
+  s = hostfed_consume(c, lay, dev, done, p, hv_out);
   if (uploader.joinable()) uploader.join();
-  if (!one_stream) (void)hipStreamSynchronize(c->copy_stream);
+  if (!dev.one_stream) (void)hipStreamSynchronize(c->copy_stream);
   if (s != HG_OK) {
     (void)hipStreamSynchronize(c->stream);
     return s;
   }
-  // the last sub-batch's check word (the earlier ones were read as their successors were queued)
-  if ((s = hg_sketch_resolve(c)) != HG_OK) return s;
-  if (c->n_redone_steps != redone_before)
-    HG_HIP(c, hipMemcpyAsync(hv_out, d_hv, hv_bytes, hipMemcpyDeviceToHost, c->stream));
-  HG_HIP(c, hipMemcpyAsync(norm2_out, d_n2, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HG_HIP(c, hipMemcpyAsync(nhash_out, d_nh, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HG_HIP(c, hipStreamSynchronize(c->stream));
-  return HG_OK;
+  return hostfed_finish(c, dev, n, redone_before, hv_out, norm2_out, nhash_out);
 }
 
 extern "C" hg_status hg_kmer_hash_sample(hg_ctx *c, const uint8_t *seq, size_t n_bps, uint32_t ksize,
@@ -484,17 +501,8 @@ extern "C" hg_status hg_kmer_hash_sample_min_count(hg_ctx *c, const uint8_t *seq
   HostfedCall in_flight;
   const SingleChoice single = pack_single(c, seq, n_bps, in_flight.others);
   const bool packed = single.packed;
-  if (packed) {
-    HG_HIP(c, pack_buf_for(c, 0, hg_pack2_size(n_bps)));
-    const auto tp0 = std::chrono::steady_clock::now();
-    hg_pack2_piece(seq, n_bps, norm_mode, static_cast<uint8_t *>(c->pack_buf[0]), 0, n_bps);  // (the whole genome as one piece)
-    pack_measured(single, n_bps, std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count());
-    HG_HIP(c, hipMemcpyAsync(c->w_seq.p, c->pack_buf[0], hg_pack2_size(n_bps), hipMemcpyHostToDevice, c->stream));
-    HG_HIP(c, hipEventRecord(c->pack_ev[0], c->stream));
-    c->pack_used[0] = true;
-  } else {
-    HG_HIP(c, hipMemcpyAsync(c->w_seq.p, seq, n_bps, hipMemcpyHostToDevice, c->stream));
-  }
+  if (packed) HG_HIP(c, upload_one_packed(c, single, seq, n_bps, norm_mode, c->w_seq.p, c->stream));
+  else HG_HIP(c, hipMemcpyAsync(c->w_seq.p, seq, n_bps, hipMemcpyHostToDevice, c->stream));
   // capacity heuristic wants "scaled"; derive it from the threshold (threshold = MAX / scaled)
   uint64_t scaled = threshold ? UINT64_MAX / threshold : UINT64_MAX;
   if (scaled < 1) scaled = 1;

@@ -96,3 +96,31 @@ class CallPool {
   bool stop_ = false;
 };
 
+// Hand-over of the sub-batches of a host-fed call from the thread that queues their uploads to the thread that sketches
+// them.  What the producer wrote before publish(count) or fail() is visible to the consumer once wait() has returned.
+class Handover {
+ public:
+  void publish(size_t count) { set(count, 0); }  // sub-batches [0, count) are queued
+  void fail(int err) { set(0, err); }            // (err != 0) nothing more will be published: releases the consumer
+  // blocks until sub-batch k is queued or the producer has failed; returns the producer's error, 0 if there is none
+  int wait(size_t k) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return err_ || count_ > k; });
+    return err_;
+  }
+
+ private:
+  void set(size_t count, int err) {
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (err) err_ = err;
+      else count_ = count;
+    }
+    cv_.notify_all();
+  }
+  std::mutex mu_;
+  std::condition_variable cv_;
+  size_t count_ = 0;
+  int err_ = 0;
+};
+

@@ -175,6 +175,7 @@ struct hg_ctx {
   uint64_t dbg_average_rounds = 0;  // test hook "average_rounds": rounds hg_cluster_average* queue per readback of the round's merge count (0: its default)
   uint64_t dbg_average_block_rows = 0;  // test hook "average_block_rows": rows per block of the ANI matrix in hg_cluster_average_dev (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
+  uint64_t dbg_hostfed_stage_bytes = 0;  // test hook "hostfed_stage_bytes": bytes at which a sub-batch of hg_sketch_batch closes (0: HG_STAGE_BYTES)
   uint64_t dbg_pair_limit = 0;  // test hook "pair_limit": pairs one kernel launch of a comparison may enumerate (0: 2^32 - 1, the hit counter's reach)
   // pinned host scratch
   void *h_pin = nullptr;

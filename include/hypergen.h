@@ -96,6 +96,8 @@ int hg_device_count(void);
  *                                      HG_SEARCH_BLOCK_BYTES)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
+ *       "hostfed_stage_bytes" = "<n>" (bytes of sequence at which hg_sketch_batch closes a sub-batch, twice as many when the
+ *                                      batch goes over 2-bit packed; 0 = the default, 64 MiB.  Any value gives the same result)
  * Nothing in the library reads environment variables. */
 hg_status hg_ctx_set_debug(hg_ctx *ctx, const char *key, const char *value);
 

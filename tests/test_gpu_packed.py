@@ -287,3 +287,94 @@ def test_hostfed_forced_packed_with_very_short_sequences(hg, orc):
         for i in (0, len(seqs) // 2, len(seqs) - 1):
             w_hv, w_n2, w_nh = orc.sketch_genome(seqs[i], 5, 1, 123, True, hv_d=256)
             assert res["packed"][2][i] == w_nh and res["packed"][1][i] == w_n2 and np.array_equal(res["packed"][0][i], w_hv)
+
+
+# ---- the sub-batch machinery of hg_sketch_batch at test size: debug key "hostfed_stage_bytes" closes a sub-batch after that many
+# bytes (twice as many when the batch goes packed) instead of 64 MiB, so that a megabyte runs through several sub-batches, all
+# three upload routes and both staging buffers.  Results must not depend on where the sub-batches end.
+
+def _sub_batches(seqs, stage):
+    """genome counts of the sub-batches: one closes when its padded bytes have reached `stage` before the next genome is added"""
+    counts, in_sub = [0], 0
+    for s in seqs:
+        if in_sub >= stage:
+            counts.append(0)
+            in_sub = 0
+        counts[-1] += 1
+        in_sub += (len(s) + 15) // 16 * 16
+    return counts
+
+
+def _hostfed_batch(hg, seqs, p, mode, stage):
+    c = hg.Context(0)
+    if mode:
+        c.set_debug("hostfed", mode)
+    if stage:
+        c.set_debug("hostfed_stage_bytes", stage)
+    res = c.sketch_batch(seqs, p)
+    kernel = c.last_kernel("kmer")
+    c.close()
+    return res, kernel
+
+
+def test_hostfed_three_upload_routes_in_one_call(hg, orc):
+    """sub-batches of >= 16 small genomes (one staging copy), of < 16 genomes around a 150 kbp one (a copy per genome) and, in
+    the packed mode, packed ones; an empty and a shorter-than-k genome among them"""
+    rng = np.random.default_rng(51)
+    seqs = (_host_genomes(rng, 48, 200, 9001) + [genome(rng, 150_000) for _ in range(3)] + [np.zeros(0, np.uint8), genome(rng, 11)]
+            + _host_genomes(rng, 20, 200, 9001))
+    counts = _sub_batches(seqs, 65536)  # (the ASCII mode's; every genome is far below 1 MiB)
+    assert len(counts) >= 4 and max(counts) >= 16 and min(counts) < 16, counts
+    assert len(_sub_batches(seqs, 2 * 65536)) >= 4
+    p = hg.default_params(scaled=20, hv_d=512)
+    whole, _ = _hostfed_batch(hg, seqs, p, "", 0)  # one sub-batch
+    for mode in ("ascii", "packed"):
+        res, kernel = _hostfed_batch(hg, seqs, p, mode, 65536)
+        assert kernel.endswith("true>") == (mode == "packed"), mode
+        for a, b in zip(res, whole):
+            assert np.array_equal(a, b), mode
+    for i in (0, 49, len(seqs) - 1):
+        w_hv, w_n2, w_nh = orc.sketch_genome(seqs[i], 21, 20, 123, True, hv_d=512)
+        assert whole[2][i] == w_nh and whole[1][i] == w_n2 and np.array_equal(whole[0][i], w_hv), i
+
+
+def test_hostfed_ascii_sub_batch_between_packed_ones(hg, orc):
+    """a sub-batch of 1..16-base sequences, whose blobs outgrow its own region of the device buffer, stays ASCII between two
+    sub-batches that go packed: each is sketched from the form and the offsets it was uploaded with"""
+    rng = np.random.default_rng(52)
+    big = [genome(rng, 50_000) for _ in range(4)]
+    seqs = big[:2] + [genome(rng, int(n)) for n in rng.integers(1, 17, 5000)] + big[2:]
+    assert _sub_batches(seqs, 2 * 32768) == [2, 4096, 906]
+    p = hg.default_params(ksize=5, scaled=1, hv_d=256)
+    res = {}
+    for mode in ("ascii", "packed"):
+        res[mode], kernel = _hostfed_batch(hg, seqs, p, mode, 32768)
+        assert kernel.endswith("true>") == (mode == "packed"), mode  # (the last sub-batch went packed)
+    for a, b in zip(res["ascii"], res["packed"]):
+        assert np.array_equal(a, b)
+    for i in (1, 2500, len(seqs) - 1):
+        w_hv, w_n2, w_nh = orc.sketch_genome(seqs[i], 5, 1, 123, True, hv_d=256)
+        assert res["packed"][2][i] == w_nh and res["packed"][1][i] == w_n2 and np.array_equal(res["packed"][0][i], w_hv), i
+
+
+def test_hostfed_single_genome_is_one_sub_batch_whatever_the_stage_bytes(hg, orc):
+    """hg_kmer_hash_sample and sketch_batch([s]) share the single-genome packed upload; one genome is one sub-batch, so the hook
+    changes nothing"""
+    rng = np.random.default_rng(53)
+    s = genome(rng, 300_000, junk=0.01)
+    p = hg.default_params(scaled=40, hv_d=512)
+    got = {}
+    for mode in ("ascii", "packed"):
+        c = hg.Context(0)
+        c.set_debug("hostfed", mode)
+        c.set_debug("hostfed_stage_bytes", 65536)
+        hashes = np.sort(c.kmer_hash_sample(s, 21, 40))
+        assert c.last_kernel("kmer").endswith("true>") == (mode == "packed")
+        got[mode] = (hashes,) + tuple(c.sketch_batch([s], p))
+        assert c.last_kernel("kmer").endswith("true>") == (mode == "packed")
+        c.close()
+    for a, b in zip(got["ascii"], got["packed"]):
+        assert np.array_equal(a, b)
+    w_hv, w_n2, w_nh = orc.sketch_genome(s, 21, 40, 123, True, hv_d=512)
+    assert np.array_equal(got["packed"][0], np.sort(orc.kmer_hash_sample(s, 21, 40, 123, True)))
+    assert got["packed"][3][0] == w_nh and got["packed"][2][0] == w_n2 and np.array_equal(got["packed"][1][0], w_hv)

@@ -22,7 +22,8 @@ def test_formats_under_asan_ubsan(tmp_path):
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_call_pool_and_piece_packer_under_tsan(tmp_path):
-    """the host threads of a host-fed call (hg_sketch_batch packs its sub-batches with them) under ThreadSanitizer"""
+    """the host threads of a host-fed call (hg_sketch_batch packs its sub-batches with them) and the hand-over between its
+    uploader and its consumer under ThreadSanitizer"""
     exe = tmp_path / "pool_driver"
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-fno-omit-frame-pointer",
                            os.path.join(ROOT, "tests", "native", "pool_tsan_driver.cpp"),
@@ -44,3 +45,16 @@ def test_stream_chunk_layout_under_asan_ubsan(tmp_path):
                            "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "stream layout driver ok" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_hostfed_batch_layout_under_asan_ubsan(tmp_path):
+    """the layout of a host-fed batch (hg_hostfed_layout.h: sub-batch cuts, genome and blob offsets, which sub-batches go
+    packed, upload routes, packing tasks, demotion, the decision to pack) against the loops hg_sketch_batch had before, over
+    seeded length lists, and the three cases of test_hostfed_forced_packed_with_very_short_sequences"""
+    exe = tmp_path / "hostfed_layout_driver"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "native", "hostfed_layout_driver.cpp"),
+                           "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "hostfed layout driver ok" in out.stdout, out.stdout + out.stderr
