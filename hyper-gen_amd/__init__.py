@@ -93,12 +93,29 @@ EXPORTS = [
     "hg_cluster_setcover_hits_dev", "hg_cluster_setcover_dev", "hg_cluster_setcover", "hg_ctx_cluster_setcover_rounds",
     "hg_cluster_tree_hits_dev", "hg_cluster_tree_dev", "hg_cluster_tree", "hg_ctx_cluster_tree_rounds",
     "hg_cluster_average_matrix_dev", "hg_cluster_average_dev", "hg_cluster_average", "hg_ctx_cluster_average_rounds",
+    "hg_cluster_stats_matrix_dev", "hg_cluster_stats_dev", "hg_cluster_stats",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
     "hg_ani_pairs_dev", "hg_ani_pairs",
 ]
 SEARCH_TOPK_MAX = 64  # HG_SEARCH_TOPK_MAX
 CLUSTER_AVERAGE_MAX_N = 65536  # HG_CLUSTER_AVERAGE_MAX_N
+STATS_NONE = 0xFFFFFFFF  # HG_STATS_NONE
+
+
+class NodeStat(C.Structure):  # hg_node_stat
+    _fields_ = [("within_sum", C.c_uint64), ("within_min", C.c_uint32), ("within_min_idx", C.c_uint32),
+                ("outside_max", C.c_uint32), ("outside_max_idx", C.c_uint32)]
+
+
+class ClusterStat(C.Structure):  # hg_cluster_stat
+    _fields_ = [("within_sum", C.c_uint64), ("size", C.c_uint32), ("first", C.c_uint32), ("medoid", C.c_uint32),
+                ("within_min", C.c_uint32), ("within_min_a", C.c_uint32), ("within_min_b", C.c_uint32),
+                ("outside_max", C.c_uint32), ("outside_member", C.c_uint32), ("outside_idx", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+NODE_STAT_DTYPE = np.dtype([(name, np.uint64 if t is C.c_uint64 else np.uint32) for name, t in NodeStat._fields_])
+CLUSTER_STAT_DTYPE = np.dtype([(name, np.uint64 if t is C.c_uint64 else np.uint32) for name, t in ClusterStat._fields_])
 
 
 def source_stamp():
@@ -295,6 +312,9 @@ def lib():
         "hg_cluster_average_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "hg_cluster_average": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "hg_ctx_cluster_average_rounds": (C.c_uint64, [vp]),
+        "hg_cluster_stats_matrix_dev": (C.c_int, [vp, vp, sz, vp, sz, vp, vp]),
+        "hg_cluster_stats_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
+        "hg_cluster_stats": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
         "hg_search_topk_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
         "hg_search_topk_block_dev": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
                                                vp, vp]),
@@ -840,6 +860,32 @@ class Context:
     def cluster_average_rounds(self):
         """rounds of the last average-linkage call on this ctx (hg_ctx_cluster_average_rounds)"""
         return int(lib().hg_ctx_cluster_average_rounds(self._h))
+
+    # ---- cluster statistics (hg_cluster_stats*) ---------------------------------------------------
+    def cluster_stats(self, hv, n2, cluster, n_clusters, ksize=21, node=True, stat=True):
+        """hg_cluster_stats on host sketches and a host assignment (cluster[i] < n_clusters, any labelling): numpy record
+        arrays (node, stat) of NODE_STAT_DTYPE and CLUSTER_STAT_DTYPE; node=False / stat=False passes NULL and gives None"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        cl = np.ascontiguousarray(cluster, np.uint32)
+        n = h.shape[0]
+        nodes = np.zeros(n, NODE_STAT_DTYPE) if node else None
+        stats = np.zeros(n_clusters, CLUSTER_STAT_DTYPE) if stat else None
+        self._ck(lib().hg_cluster_stats(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, _ptr(cl), n_clusters,
+                                        _ptr(nodes) if node else _ptr(0), _ptr(stats) if stat else _ptr(0)))
+        return nodes, stats
+
+    def cluster_stats_dev(self, d_hv, d_n2, n, hv_d, d_cluster, n_clusters, d_node=None, d_stat=None, ksize=21):
+        """hg_cluster_stats_dev on resident sketches (device pointers; d_node or d_stat may be None, not both): n records of
+        24 bytes at d_node, n_clusters records of 48 bytes at d_stat"""
+        self._ck(lib().hg_cluster_stats_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, _ptr(d_cluster or 0), n_clusters,
+                                            _ptr(d_node or 0), _ptr(d_stat or 0)))
+
+    def cluster_stats_matrix_dev(self, d_ani, n, d_cluster, n_clusters, d_node=None, d_stat=None):
+        """hg_cluster_stats_matrix_dev on a device-resident n x n float matrix, row-major (d_node or d_stat may be None, not
+        both)"""
+        self._ck(lib().hg_cluster_stats_matrix_dev(self._h, _ptr(d_ani or 0), n, _ptr(d_cluster or 0), n_clusters, _ptr(d_node or 0),
+                                                   _ptr(d_stat or 0)))
 
 
 def shard_range(n, shard, n_shards):

@@ -90,6 +90,7 @@ struct Cli {
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
   bool hclust_average = false; // --hclust average (cluster): average linkage (UPGMA) on the dense matrix, a scheme of its own
+  std::string stats_out;       // --stats <file> (cluster): medoid, cohesion and separation of every cluster at -a, one line each
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
   std::bitset<32> given;          // which options the command line carried, by row of `options`
@@ -196,6 +197,7 @@ const Option options[] = {
     {"levels", 0, take_levels, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
     {"hclust", 0, [](Cli &c, const Arg &a) { c.hclust_average = a.choice({"average"}) == 0; }, CLUSTER,
      "it chooses the hierarchical clustering of cluster"},
+    {"stats", 0, [](Cli &c, const Arg &a) { c.stats_out = a.file(); }, CLUSTER, "it describes the clusters of cluster", ONE_GPU_CLUSTER},
     {"columns", 0, take_columns, DIST, "it adds a pair's other metrics to the lines of dist", ONE_GPU_DIST},
     {"pairs", 0, [](Cli &c, const Arg &a) { c.pairs_file = a.file(); }, DIST, "it names the pairs dist evaluates", ONE_GPU_DIST},
     {"min_count", 0, [](Cli &c, const Arg &a) { c.min_count = (unsigned)a.uint(0xFFFFFFFFull, 1); }, SKETCH,
@@ -213,7 +215,7 @@ size_t option_row(const char *name) {
 }
 bool given(const Cli &c, const char *name) { return c.given[option_row(name)]; }
 
-// `hyper-gen --help`; `hyper-gen cluster --help` prints it too, with a paragraph on --hclust behind it
+// `hyper-gen --help`; `hyper-gen cluster --help` prints it too, with a paragraph on --hclust and one on --stats behind it
 void print_help() {
   std::printf("HyperGen: Fast and memory-efficient genome sketching in hyperdimensional space (MI355X build)\n\n"
               "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
@@ -275,6 +277,15 @@ void print_cluster_help() {
               "         genomes - clusters lines, every child before its parent: file of the first member of the cluster that\n"
               "         stays, file of the first member of the one absorbed, average ANI of the merge as dist prints it, size\n"
               "         of the merged cluster.  It is a scheme of its own: it does not go with --linkage or --levels.\n");
+  std::printf("\ncluster --stats <file>: how good the clusters at -a are, with every --linkage and with --hclust, computed on the\n"
+              "         first visible GPU from all pairs, block by block (no matrix is held).  Every ANI counts as dist prints\n"
+              "         it, in thousandths.  One line per cluster, in id order: cluster id, size, file of the medoid (the member\n"
+              "         with the highest sum of ANIs with the other members, ties to the one processed first), mean ANI within\n"
+              "         the cluster over its ordered pairs, lowest ANI within the cluster -- far below -a: the cluster\n"
+              "         chained --, files of the two members that have it, highest ANI between a member and a sketch outside,\n"
+              "         file of that member, file of that sketch, cluster id of that sketch.  NA in the fields a singleton, or\n"
+              "         a run with one cluster, does not have.  A cluster whose highest outside ANI is not below its lowest\n"
+              "         within ANI is counted as not separated in the log.  -o is what it is without --stats.\n");
 }
 
 Cli parse(int argc, char **argv) {
@@ -1075,6 +1086,8 @@ int run_search(const Cli &c) {
 // --hclust average (hg_cluster_average_dev): average linkage on the dense matrix.  The lines of single linkage; --tree
 // writes the merges, every child before its parent: "<file_str of the name that stays>\t<file_str of the absorbed
 // name>\t<average ANI of the merge, as dist prints it>\t<size of the merged cluster>\n".
+// --stats <file> (hg_cluster_stats_dev): one line per cluster at -a, whatever formed the clusters -- the statistics of the
+// device arrays as they stand, in processing order under --order size, so that ties go to the sketch processed first.
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
   const float th = c.ani_th;
@@ -1168,6 +1181,16 @@ int run_cluster(const Cli &c) {
   d_rep.download(rep.data(), L.n);
   d_cl.download(cl.data(), L.n);
   debugf("clusters on the host in %.1f ms", (now_s() - tp) * 1e3);
+  // --stats: the records of the clusters at -a, from the device arrays as they stand (processing order)
+  std::vector<hg_cluster_stat> stats;
+  if (given(c, "stats")) {
+    const double ts = now_s();
+    DevBuf<hg_cluster_stat> d_stat(ctx, std::max<size_t>(n_cl, 1));
+    ck(ctx, hg_cluster_stats_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, d_cl.get(), n_cl, nullptr, d_stat.get()), "cluster statistics");
+    stats.resize(n_cl);
+    if (n_cl) d_stat.download(stats.data(), n_cl);
+    debugf("cluster statistics in %.1f ms", (now_s() - ts) * 1e3);
+  }
   std::vector<uint32_t> size(n_cl, 0);
   for (size_t i = 0; i < L.n; ++i) {
     // (a set-cover representative may have a larger index than its member)
@@ -1223,6 +1246,57 @@ int run_cluster(const Cli &c) {
   std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %.1f to file %s", L.n, n_cl,
                 singletons, th, c.out.c_str());
   logline("INFO", buf);
+  if (given(c, "stats")) {
+    // one line per cluster, in id order: id, size, medoid, mean and minimum within (and the pair that has it), the nearest
+    // sketch outside (its ANI, the member, the sketch, the sketch's cluster); NA where a cluster has no such value
+    const uint32_t none = HG_STATS_NONE;
+    size_t mixed = 0;  // clusters of two or more whose nearest outside sketch is as close as their two least similar members
+    for (const hg_cluster_stat &x : stats) {
+      const bool pairs = x.size >= 2, outside = x.outside_idx != none;
+      if (x.size == 0 || x.medoid >= L.n || (pairs && (x.within_min_a >= L.n || x.within_min_b >= L.n)) ||
+          (outside && (x.outside_member >= L.n || x.outside_idx >= L.n)))
+        die("inconsistent cluster result");
+      mixed += pairs && outside && x.outside_max >= x.within_min;
+    }
+    auto name_len = [&](uint32_t k) { return k == none ? (size_t)2 : (size_t)L.len[perm[k]]; };
+    write_tsv(c.stats_out, c.threads, stats.size(),
+              [&](size_t i) {
+                const hg_cluster_stat &x = stats[i];
+                return 80 + name_len(x.medoid) + name_len(x.within_min_a) + name_len(x.within_min_b) + name_len(x.outside_member) +
+                       name_len(x.outside_idx);
+              },
+              [&](size_t i, char *w) {
+                const hg_cluster_stat &x = stats[i];
+                size_t b = 0;
+                auto tab = [&] { w[b++] = '\t'; };
+                auto na = [&] { tab(), w[b++] = 'N', w[b++] = 'A'; };
+                auto name = [&](uint32_t k) { tab(), b += L.put_name(w + b, perm[k]); };
+                auto milli = [&](uint32_t m) {  // the thousandths as dist prints an ANI
+                  tab(), b += put_u32(w + b, m / 1000), w[b++] = '.';
+                  w[b++] = (char)('0' + m / 100 % 10), w[b++] = (char)('0' + m / 10 % 10), w[b++] = (char)('0' + m % 10);
+                };
+                b += put_u32(w + b, (uint32_t)i), tab(), b += put_u32(w + b, x.size), name(x.medoid);
+                if (x.size >= 2) {
+                  const float mean = (float)(((double)x.within_sum / ((double)x.size * (double)(x.size - 1))) / 1000.0);
+                  b += put_ani(w + b, mean) - 1;  // (without put_ani's end of line)
+                  milli(x.within_min), name(x.within_min_a), name(x.within_min_b);
+                } else {
+                  na(), na(), na(), na();
+                }
+                if (x.outside_idx != none) {
+                  milli(x.outside_max), name(x.outside_member), name(x.outside_idx);
+                  tab(), b += put_u32(w + b, cl[x.outside_idx]);
+                } else {
+                  na(), na(), na(), na();
+                }
+                w[b++] = '\n';
+                return b;
+              },
+              "Dump statistics file failed!");
+    std::snprintf(buf, sizeof buf, "Output statistics of %zu clusters (%zu not separated) to file %s", stats.size(), mixed,
+                  c.stats_out.c_str());
+    logline("INFO", buf);
+  }
   for (const Level &v : more) {
     std::vector<uint32_t> sz(v.n_cl, 0);
     for (size_t i = 0; i < L.n; ++i) ++sz[v.cl[i]];

@@ -94,6 +94,8 @@ int hg_device_count(void);
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "average_block_rows" = "<n>"  (rows per block of the ANI matrix in hg_cluster_average_dev; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
+ *       "stats_block_rows" = "<n>"    (rows per block of the ANI matrix in hg_cluster_stats_dev; 0 = automatic, from
+ *                                      HG_SEARCH_BLOCK_BYTES)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  *       "hostfed_stage_bytes" = "<n>" (bytes of sequence at which hg_sketch_batch closes a sub-batch, twice as many when the
@@ -293,11 +295,11 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
  * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev}, hg_cluster_stats{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev} and hg_cluster_average{,_dev} accept HG_ANI_MASH and
- * HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
- * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev (it takes the matrix), hg_dist_prep_ops_dev, the
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev} and hg_cluster_stats{,_dev}
+ * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
+ * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev and hg_cluster_stats_matrix_dev (they take the matrix), hg_dist_prep_ops_dev, the
  * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
@@ -681,6 +683,69 @@ hg_status hg_cluster_average(hg_ctx *ctx, const int16_t *hv, const int32_t *norm
                              size_t *n_clusters);
 /* rounds of the last average-linkage call on this ctx, the one that merged nothing included (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_average_rounds(const hg_ctx *ctx);
+
+/* Cluster statistics (no reference counterpart): how good a clustering is -- per cluster the medoid, the cohesion (sum and
+ * minimum of the within-cluster ANI) and the separation (the nearest item outside), the figures dRep, skDER and galah
+ * report or use -- from the dense ANI matrix and a cluster assignment.  Input: n items, ani(i, j) -- the float
+ * hg_dist_full_dev writes at [i, j] (reference i, query j) -- and cluster[i] < n_clusters in ANY labelling: it need not come
+ * from this library, and ids without members are allowed.  Everything is decided on integers:
+ *   m(i, j) = the integer `dist` prints for the pair, in thousandths (the m of average linkage above): NaN and negative
+ *             values 0, values above 100 100 000, else rint((double)ani * 1000.0);
+ *   the row of i uses row i of the matrix only, the diagonal is never read, and nothing assumes symmetry: an asymmetric
+ *   matrix has one defined answer.
+ * Per node, hg_node_stat (24 bytes):
+ *   within_sum                      the sum of m(i, j) over j != i in i's cluster;
+ *   within_min, within_min_idx      the smallest m(i, j) over j != i in i's cluster and the smallest j that attains it;
+ *                                   HG_STATS_NONE twice for a singleton;
+ *   outside_max, outside_max_idx    the largest m(i, j) over j outside i's cluster and the smallest j that attains it;
+ *                                   HG_STATS_NONE twice when there is no item outside.
+ * Per cluster id, hg_cluster_stat (48 bytes):
+ *   within_sum                      the sum of the members' within_sum: the ordered pairs, size (size - 1) of them;
+ *   size, first                     the number of members and the smallest member;
+ *   medoid                          the member with the largest within_sum, ties to the smallest index (a singleton is its
+ *                                   own medoid);
+ *   within_min, _a, _b              the minimum of the members' within_min, the smallest member that attains it and that
+ *                                   member's within_min_idx;
+ *   outside_max, outside_member,    the maximum of the members' outside_max, the smallest member that attains it and that
+ *   outside_idx                     member's outside_max_idx;
+ *   reserved                        0.
+ * HG_STATS_NONE marks an absent value; an id without members has size = 0, within_sum = 0 and HG_STATS_NONE in every index
+ * and value field.  The mean within-cluster ANI of a cluster is (float)(((double)within_sum / (double)(size (size - 1))) /
+ * 1000.0).  Only integer add, min and max are used: the result depends on the matrix and the assignment alone -- not on
+ * block size, scheduling or the order of atomics.
+ * On the device (hg_cluster_stats.hip): cluster_stats_rows_kernel, one workgroup per row of a block of the matrix (16-byte
+ * loads, head and tail of a row peeled, a reduction by wave shuffles and LDS); cluster_stats_fold_kernel and
+ * cluster_stats_medoid_kernel, one lane per node, 64-bit atomics per cluster id; cluster_stats_emit_kernel, one lane per
+ * cluster id.  Memory: 48 bytes per cluster id, 24 per node when d_node is NULL, and in hg_cluster_stats_dev one block of
+ * the matrix; no n x n matrix is held.
+ * d_node or d_stat may be NULL, not both (HG_ERR_INVALID).  n == 0: HG_OK, the n_clusters records are written as empty.
+ * n >= 2^31: HG_ERR_UNSUPPORTED.  NULL cluster (n > 0): HG_ERR_INVALID.  A cluster[i] >= n_clusters fails the call with
+ * HG_ERR_INVALID -- it indexes nothing, and the next call on the ctx starts clean.  Results are final on return.  Launches
+ * count under HG_T_DIST when timing is on.
+ *   hg_cluster_stats_matrix_dev : d_ani, n x n floats, row-major.  Independent of the ctx's ANI metric.
+ *   hg_cluster_stats_dev        : resident sketches (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT); the matrix is streamed as rows
+ *                                 [r0, r1) x all n columns from hg_dist_full_dev in a scratch block of at most
+ *                                 HG_SEARCH_BLOCK_BYTES; debug key "stats_block_rows" forces the row count.
+ *   hg_cluster_stats            : host arrays in and out, staged through the ctx. */
+#define HG_STATS_NONE 0xFFFFFFFFu
+typedef struct {
+  uint64_t within_sum;
+  uint32_t within_min, within_min_idx;
+  uint32_t outside_max, outside_max_idx;
+} hg_node_stat;
+typedef struct {
+  uint64_t within_sum;
+  uint32_t size, first, medoid;
+  uint32_t within_min, within_min_a, within_min_b;
+  uint32_t outside_max, outside_member, outside_idx;
+  uint32_t reserved;
+} hg_cluster_stat;
+hg_status hg_cluster_stats_matrix_dev(hg_ctx *ctx, const float *d_ani, size_t n, const uint32_t *d_cluster, size_t n_clusters,
+                                      hg_node_stat *d_node, hg_cluster_stat *d_stat);
+hg_status hg_cluster_stats_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                               const uint32_t *d_cluster, size_t n_clusters, hg_node_stat *d_node, hg_cluster_stat *d_stat);
+hg_status hg_cluster_stats(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                           const uint32_t *cluster, size_t n_clusters, hg_node_stat *node, hg_cluster_stat *stat);
 
 /* ---- sketch compression (host side; src/hd.rs:114-232) -------------------------------- */
 uint32_t hg_hv_quant_bits(const int16_t *hv, uint32_t hv_d);
