@@ -93,6 +93,7 @@ EXPORTS = [
     "hg_cluster_setcover_hits_dev", "hg_cluster_setcover_dev", "hg_cluster_setcover", "hg_ctx_cluster_setcover_rounds",
     "hg_cluster_tree_hits_dev", "hg_cluster_tree_dev", "hg_cluster_tree", "hg_ctx_cluster_tree_rounds",
     "hg_cluster_average_matrix_dev", "hg_cluster_average_dev", "hg_cluster_average", "hg_ctx_cluster_average_rounds",
+    "hg_cluster_complete_matrix_dev", "hg_cluster_complete_dev", "hg_cluster_complete", "hg_ctx_cluster_complete_rounds",
     "hg_cluster_stats_matrix_dev", "hg_cluster_stats_dev", "hg_cluster_stats",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
@@ -100,6 +101,7 @@ EXPORTS = [
 ]
 SEARCH_TOPK_MAX = 64  # HG_SEARCH_TOPK_MAX
 CLUSTER_AVERAGE_MAX_N = 65536  # HG_CLUSTER_AVERAGE_MAX_N
+CLUSTER_COMPLETE_MAX_N = 65536  # HG_CLUSTER_COMPLETE_MAX_N
 STATS_NONE = 0xFFFFFFFF  # HG_STATS_NONE
 
 
@@ -312,6 +314,10 @@ def lib():
         "hg_cluster_average_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "hg_cluster_average": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
         "hg_ctx_cluster_average_rounds": (C.c_uint64, [vp]),
+        "hg_cluster_complete_matrix_dev": (C.c_int, [vp, vp, sz, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "hg_cluster_complete_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "hg_cluster_complete": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, vp, vp, vp, vp, vp, C.POINTER(sz)]),
+        "hg_ctx_cluster_complete_rounds": (C.c_uint64, [vp]),
         "hg_cluster_stats_matrix_dev": (C.c_int, [vp, vp, sz, vp, sz, vp, vp]),
         "hg_cluster_stats_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
         "hg_cluster_stats": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
@@ -860,6 +866,42 @@ class Context:
     def cluster_average_rounds(self):
         """rounds of the last average-linkage call on this ctx (hg_ctx_cluster_average_rounds)"""
         return int(lib().hg_ctx_cluster_average_rounds(self._h))
+
+    # ---- complete linkage (hg_cluster_complete*) --------------------------------------------------
+    def cluster_complete(self, hv, n2, ksize=21, ani_th=95.0):
+        """hg_cluster_complete on host sketches: numpy (rep, cluster, into, level, size, n_clusters) -- rep[i] = the smallest
+        index of i's cluster, cluster[i] = its dense id in order of rep; the dendrogram: into[b] = the name b was absorbed
+        into (b itself if never), level[b] = the minimum ANI between the two merged clusters (0 if never), size[b] = the size of the merged
+        cluster (of b's own final cluster if never)"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        rep, cl, into, size = (np.zeros(n, np.uint32) for _ in range(4))
+        level = np.zeros(n, np.float32)
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_complete(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th), _ptr(rep), _ptr(cl),
+                                          _ptr(into), _ptr(level), _ptr(size), C.byref(nc)))
+        return rep, cl, into, level, size, nc.value
+
+    def cluster_complete_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_into=None, d_level=None, d_size=None, ksize=21, ani_th=95.0):
+        """hg_cluster_complete_dev on resident sketches (device pointers; d_into, d_level and d_size may each be None);
+        returns the number of clusters"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_complete_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep or 0),
+                                              _ptr(d_cluster or 0), _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
+        return nc.value
+
+    def cluster_complete_matrix_dev(self, d_ani, n, ani_th, d_rep, d_cluster, d_into=None, d_level=None, d_size=None):
+        """hg_cluster_complete_matrix_dev on a device-resident n x n float matrix, of which [i, j] with i < j is read
+        (d_into, d_level and d_size may each be None); returns the number of clusters"""
+        nc = C.c_size_t(0)
+        self._ck(lib().hg_cluster_complete_matrix_dev(self._h, _ptr(d_ani or 0), n, C.c_float(ani_th), _ptr(d_rep or 0), _ptr(d_cluster or 0),
+                                                     _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
+        return nc.value
+
+    def cluster_complete_rounds(self):
+        """rounds of the last complete-linkage call on this ctx (hg_ctx_cluster_complete_rounds)"""
+        return int(lib().hg_ctx_cluster_complete_rounds(self._h))
 
     # ---- cluster statistics (hg_cluster_stats*) ---------------------------------------------------
     def cluster_stats(self, hv, n2, cluster, n_clusters, ksize=21, node=True, stat=True):

@@ -89,7 +89,8 @@ struct Cli {
   bool order_size = false;     // --order file|size (cluster --linkage greedy)
   std::string tree_out;        // --tree <file> (cluster --linkage single): the single-linkage tree, one line per edge
   std::vector<float> levels;   // --levels L1,L2,... (cluster --linkage single): more thresholds, cut from the one tree
-  bool hclust_average = false; // --hclust average (cluster): average linkage (UPGMA) on the dense matrix, a scheme of its own
+  bool hclust_average = false; // --hclust average, --agglomerate average (cluster): average linkage (UPGMA) on the dense matrix, a scheme of its own
+  bool complete = false;       // --agglomerate complete (cluster): complete linkage on the dense matrix, likewise
   std::string stats_out;       // --stats <file> (cluster): medoid, cohesion and separation of every cluster at -a, one line each
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
@@ -197,6 +198,8 @@ const Option options[] = {
     {"levels", 0, take_levels, CLUSTER, "it belongs to cluster --linkage single", ONE_GPU_CLUSTER},
     {"hclust", 0, [](Cli &c, const Arg &a) { c.hclust_average = a.choice({"average"}) == 0; }, CLUSTER,
      "it chooses the hierarchical clustering of cluster"},
+    {"agglomerate", 0, [](Cli &c, const Arg &a) { c.complete = a.choice({"average", "complete"}) == 1, c.hclust_average = !c.complete; },
+     CLUSTER, "it chooses the agglomerative clustering of cluster"},
     {"stats", 0, [](Cli &c, const Arg &a) { c.stats_out = a.file(); }, CLUSTER, "it describes the clusters of cluster", ONE_GPU_CLUSTER},
     {"columns", 0, take_columns, DIST, "it adds a pair's other metrics to the lines of dist", ONE_GPU_DIST},
     {"pairs", 0, [](Cli &c, const Arg &a) { c.pairs_file = a.file(); }, DIST, "it names the pairs dist evaluates", ONE_GPU_DIST},
@@ -215,7 +218,8 @@ size_t option_row(const char *name) {
 }
 bool given(const Cli &c, const char *name) { return c.given[option_row(name)]; }
 
-// `hyper-gen --help`; `hyper-gen cluster --help` prints it too, with a paragraph on --hclust and one on --stats behind it
+// `hyper-gen --help`; `hyper-gen cluster --help` prints it too, with a paragraph on --hclust, one on --agglomerate and one on
+// --stats behind it
 void print_help() {
   std::printf("HyperGen: Fast and memory-efficient genome sketching in hyperdimensional space (MI355X build)\n\n"
               "  hyper-gen sketch -p {fna_path} -o {output_sketch_file}\n"
@@ -277,6 +281,14 @@ void print_cluster_help() {
               "         genomes - clusters lines, every child before its parent: file of the first member of the cluster that\n"
               "         stays, file of the first member of the one absorbed, average ANI of the merge as dist prints it, size\n"
               "         of the merged cluster.  It is a scheme of its own: it does not go with --linkage or --levels.\n");
+  std::printf("\ncluster --agglomerate average|complete: the agglomerative clusterings on the dense matrix.  average is --hclust\n"
+              "         average, the same files byte for byte.  complete is complete linkage, dRep's --clusterAlg complete and\n"
+              "         scipy's linkage(method=\"complete\") on an ANI matrix (4 bytes per pair; up to 65536 sketches): the two\n"
+              "         clusters whose least similar members have the highest ANI merge, ties to the pair whose first members\n"
+              "         come first in the file, while that lowest ANI is at least -a [95.0] -- EVERY pair inside a cluster is at\n"
+              "         least -a, as dist prints it, which no other scheme promises.  -o, --tree and --stats get the lines of\n"
+              "         --hclust average; the third field of a --tree line is the lowest ANI between the two merged clusters.\n"
+              "         It does not go with --hclust, --linkage or --levels.\n");
   std::printf("\ncluster --stats <file>: how good the clusters at -a are, with every --linkage and with --hclust, computed on the\n"
               "         first visible GPU from all pairs, block by block (no matrix is held).  Every ANI counts as dist prints\n"
               "         it, in thousandths.  One line per cluster, in id order: cluster id, size, file of the medoid (the member\n"
@@ -347,6 +359,12 @@ Cli parse(int argc, char **argv) {
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
+  if (given(c, "agglomerate") && given(c, "hclust"))
+    die("--agglomerate does not go with --hclust: both choose the clustering on the dense matrix (--agglomerate average is --hclust average)");
+  if (given(c, "agglomerate") && given(c, "linkage"))
+    die("--agglomerate does not go with --linkage: average and complete linkage are schemes of their own, not ones of --linkage's");
+  if (given(c, "agglomerate") && given(c, "levels"))
+    die("--levels is not supported with --agglomerate: it cuts the single-linkage tree, not the dendrogram of average or complete linkage");
   if (c.hclust_average && given(c, "linkage"))
     die("--hclust does not go with --linkage: average linkage is a scheme of its own, not one of --linkage's");
   if (c.hclust_average && given(c, "levels"))
@@ -1083,9 +1101,11 @@ int run_search(const Cli &c) {
 // --linkage setcover (hg_cluster_setcover_dev): greedy set cover -- the sketch with the most still-uncovered neighbours
 // becomes a representative and takes them as its members.  The lines are those of greedy, in file order; a representative
 // may stand behind its members in the file.
-// --hclust average (hg_cluster_average_dev): average linkage on the dense matrix.  The lines of single linkage; --tree
-// writes the merges, every child before its parent: "<file_str of the name that stays>\t<file_str of the absorbed
-// name>\t<average ANI of the merge, as dist prints it>\t<size of the merged cluster>\n".
+// --hclust average, --agglomerate average (hg_cluster_average_dev): average linkage on the dense matrix.  The lines of
+// single linkage; --tree writes the merges, every child before its parent: "<file_str of the name that stays>\t<file_str
+// of the absorbed name>\t<average ANI of the merge, as dist prints it>\t<size of the merged cluster>\n".
+// --agglomerate complete (hg_cluster_complete_dev): complete linkage on the dense matrix.  The same lines; the third field
+// of a --tree line is the lowest ANI between the two merged clusters.
 // --stats <file> (hg_cluster_stats_dev): one line per cluster at -a, whatever formed the clusters -- the statistics of the
 // device arrays as they stand, in processing order under --order size, so that ties go to the sketch processed first.
 int run_cluster(const Cli &c) {
@@ -1117,19 +1137,22 @@ int run_cluster(const Cli &c) {
   };
   std::vector<Level> more;
   std::vector<hg_ani_hit> tree;  // --tree / --levels
-  struct Merge {                 // --hclust with --tree: the absorbed name, what it went into, the merge's average and size
+  const bool dense = c.hclust_average || c.complete;  // average or complete linkage: the schemes on the dense matrix
+  struct Merge {                 // ... with --tree: the absorbed name, what it went into, the merge's level and size
     uint32_t name, into, size;
     float level;
   };
   std::vector<Merge> merges;
-  if (c.hclust_average) {
+  if (dense) {
     const bool want = given(c, "tree");
     DevBuf<uint32_t> d_into(ctx), d_size(ctx);  // (NULL without --tree: the library then skips the dendrogram)
     DevBuf<float> d_level(ctx);
     if (want) d_into.alloc(L.n), d_size.alloc(L.n), d_level.alloc(L.n);
-    ck(ctx, hg_cluster_average_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(), d_cl.get(), d_into.get(), d_level.get(),
-                                   d_size.get(), &n_cl), "cluster");
-    debugf("average linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_average_rounds(ctx));
+    ck(ctx, (c.complete ? hg_cluster_complete_dev : hg_cluster_average_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(),
+                                                                            d_cl.get(), d_into.get(), d_level.get(), d_size.get(), &n_cl),
+       "cluster");
+    if (c.complete) debugf("complete linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_complete_rounds(ctx));
+    else debugf("average linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_average_rounds(ctx));
     if (want) {
       std::vector<uint32_t> into(L.n), sz(L.n);
       std::vector<float> level(L.n);
@@ -1138,7 +1161,7 @@ int run_cluster(const Cli &c) {
         if (into[i] > i) die("inconsistent cluster result");
         if (into[i] != i) merges.push_back(Merge{(uint32_t)i, into[i], sz[i], level[i]});
       }
-      // averages never increase towards the root: by (level descending, size ascending, into, name) children come first
+      // averages, and minima, never increase towards the root: by (level descending, size ascending, into, name) children come first
       std::sort(merges.begin(), merges.end(), [](const Merge &x, const Merge &y) {
         if (x.level != y.level) return x.level > y.level;
         if (x.size != y.size) return x.size < y.size;
@@ -1227,7 +1250,7 @@ int run_cluster(const Cli &c) {
               return b;
             },
             "Dump cluster file failed!");
-  if (given(c, "tree") && c.hclust_average) {  // one line per merge: file of into, file of the absorbed name, level, size
+  if (given(c, "tree") && dense) {  // one line per merge: file of into, file of the absorbed name, level, size
     write_tsv(c.tree_out, c.threads, merges.size(), [&](size_t i) { return (size_t)L.len[merges[i].into] + L.len[merges[i].name] + 22; },
               [&](size_t i, char *w) {
                 size_t b = put_line(w, L, merges[i].into, L, merges[i].name, merges[i].level);

@@ -125,8 +125,10 @@ struct hg_ctx {
   uint64_t tree_rounds = 0;  // rounds the last tree call ran, summed over its blocks (hg_ctx_cluster_tree_rounds)
   Buf w_average;  // hg_cluster_average*: per-node state -- n partner words of the round, n absorbed names, n sizes, n merge sizes, n levels (the matrix lives for one call)
   uint64_t average_rounds = 0;  // rounds the last average-linkage call ran (hg_ctx_cluster_average_rounds)
+  Buf w_complete; // hg_cluster_complete*: per-node state, ld entries each -- best partners, absorbed names of the round, sizes, merge sizes, levels (the matrix lives for one call)
+  uint64_t complete_rounds = 0;  // rounds the last complete-linkage call ran (hg_ctx_cluster_complete_rounds)
   Buf w_cstats;   // hg_cluster_stats*: n_clusters accumulators of 48 bytes, then n node records when the caller takes none
-  Buf w_srch_blk;   // hg_search_topk*, hg_cluster_average_dev, hg_cluster_stats_dev: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
+  Buf w_srch_blk;   // hg_search_topk*, hg_cluster_average_dev, hg_cluster_complete_dev, hg_cluster_stats_dev: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
   Buf w_srch_lists; // ... the slice lists of one block: keys, then counts
   Buf w_srch_state; // ... the running k best keys per query, state[j * Q + q]
   Buf w_srch_out;   // hg_search_topk: staged results (rows, then counts)
@@ -175,6 +177,9 @@ struct hg_ctx {
   uint64_t dbg_tree_rounds = 0;  // test hook "tree_rounds": rounds hg_cluster_tree* queue per readback of the count of selecting roots (0: its default)
   uint64_t dbg_average_rounds = 0;  // test hook "average_rounds": rounds hg_cluster_average* queue per readback of the round's merge count (0: its default)
   uint64_t dbg_average_block_rows = 0;  // test hook "average_block_rows": rows per block of the ANI matrix in hg_cluster_average_dev (0: by HG_SEARCH_BLOCK_BYTES)
+  uint64_t dbg_complete_rounds = 0;  // test hook "complete_rounds": rounds hg_cluster_complete* queue per readback of the round's merge count (0: its default)
+  uint64_t dbg_complete_block_rows = 0;  // test hook "complete_block_rows": rows per block of the ANI matrix in hg_cluster_complete_dev (0: by HG_SEARCH_BLOCK_BYTES)
+  bool dbg_complete_rescan_all = false;  // test hook "complete_rescan" = "all": hg_cluster_complete* scan every live row in every round
   uint64_t dbg_stats_block_rows = 0;  // test hook "stats_block_rows": rows per block of the ANI matrix in hg_cluster_stats_dev (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_hostfed_stage_bytes = 0;  // test hook "hostfed_stage_bytes": bytes at which a sub-batch of hg_sketch_batch closes (0: HG_STAGE_BYTES)

@@ -94,6 +94,12 @@ int hg_device_count(void);
  *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
  *       "average_block_rows" = "<n>"  (rows per block of the ANI matrix in hg_cluster_average_dev; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
+ *       "complete_rounds" = "<n>"     (rounds hg_cluster_complete* queue before they read the round's merge count back;
+ *                                      0 = the default, 4.  Any value gives the same result: tests run 1 and the default)
+ *       "complete_block_rows" = "<n>" (rows per block of the ANI matrix in hg_cluster_complete_dev; 0 = automatic, from
+ *                                      HG_SEARCH_BLOCK_BYTES)
+ *       "complete_rescan" = "" | "all" ("all": hg_cluster_complete* scan every live row in every round instead of only the
+ *                                      rows a merge invalidated.  Both give the same result and the same round count)
  *       "stats_block_rows" = "<n>"    (rows per block of the ANI matrix in hg_cluster_stats_dev; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
@@ -295,11 +301,11 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_ctx_set_ani_metric: host-side state of the ctx like its stream, read when each call is made; HG_ERR_INVALID for any other
  * value.  It applies to hg_dist_full{,_dev}, hg_dist{,_dev}, hg_dist_block_dev, hg_dist_block_ops_dev, hg_dist_multi{,_dev}
  * (hg_multi_set_ani_metric sets every shard's ctx), hg_search_topk{,_dev,_block_dev,_multi_dev}, hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev}, hg_cluster_stats{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev}, hg_cluster_complete{,_dev}, hg_cluster_stats{,_dev} and hg_ani_from_dots_dev.  symmetric != 0 under
  * HG_ANI_CONTAINMENT is HG_ERR_INVALID (the metric is directional: call without it for every ordered pair); hg_cluster{,_dev},
- * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev} and hg_cluster_stats{,_dev}
+ * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev}, hg_cluster_complete{,_dev} and hg_cluster_stats{,_dev}
  * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
- * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev and hg_cluster_stats_matrix_dev (they take the matrix), hg_dist_prep_ops_dev, the
+ * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev, hg_cluster_complete_matrix_dev and hg_cluster_stats_matrix_dev (they take the matrix), hg_dist_prep_ops_dev, the
  * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
@@ -683,6 +689,65 @@ hg_status hg_cluster_average(hg_ctx *ctx, const int16_t *hv, const int32_t *norm
                              size_t *n_clusters);
 /* rounds of the last average-linkage call on this ctx, the one that merged nothing included (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_average_rounds(const hg_ctx *ctx);
+
+/* Complete linkage (no reference counterpart): the hierarchical clustering in which EVERY pair inside a cluster is at
+ * least the threshold -- dRep's --clusterAlg complete, scipy's linkage(method="complete") on an ANI matrix; what "a species
+ * cluster at 95" means when it is meant strictly.  Single linkage chains, the representative schemes bound a member
+ * against its representative only, average linkage bounds an average; this scheme bounds the lowest ANI within.  Input as
+ * for average linkage: n items, ani(i, j) for i < j, and ani_th.  Everything is decided on integers:
+ *   m(i, j)  = the m of average linkage above (hg_avg_milli: NaN and negative values 0, values above 100 100 000, else
+ *              rint((double)ani * 1000.0)): it fits 32 bits;
+ *   th_milli = the same of ani_th.  A NaN threshold merges nothing, a threshold above 100 merges nothing, ani_th <= 0
+ *              merges everything into one cluster, pairs of ANI 0 or NaN included;
+ *   a cluster is named by its smallest member, W(A, B) is the minimum of m(a, b) over a in A, b in B;
+ *   pair {A, B} is BETTER than {C, D} iff W(A, B) > W(C, D); on equality the pair with the smaller lower name wins, then
+ *   the pair with the smaller higher name;
+ *   while the best pair has W(A, B) >= th_milli: merge it.  The merged cluster keeps the smaller name and
+ *   W(K, A u B) = min(W(K, A), W(K, B)).
+ * Results: exactly the outputs of hg_cluster_average*: rep, cluster (dense ids in increasing order of rep), *n_clusters, and
+ * the three optional arrays of the dendrogram (each may be NULL).  For a name B that was absorbed into A, into[B] = A,
+ * level[B] = (float)((double)W / 1000.0) of its merge, size[B] = the merged size; for a name never absorbed into[i] = i,
+ * level[i] = 0, size[i] = the final size of its cluster.  Levels never rise towards the root (a minimum over more pairs is
+ * not larger): sorted by (level descending, size ascending, into, index) the absorbed entries list the merges with every
+ * child before its parent.
+ * Only integer min and compares occur: the result depends on the matrix alone -- not on scheduling, block size or the
+ * rounds per readback -- and anyone can reproduce it from a `dist -a 0` TSV.
+ * On the device (hg_cluster_complete.hip) the rule is resolved in rounds on a dense matrix of u32 minima, n rows of n
+ * rounded up to a multiple of 4: every pair of mutual best partners merges at once, which is the sequential result because
+ * complete linkage is reducible.  The tie-break survives a merge: the key of K in row A is (W(A, K), -K); the key of
+ * C u D, C < D, is (min(W(A, C), W(A, D)), -C), which is key(C) or strictly smaller in its first component, so a partner
+ * that beat both C and D still beats their union; the global best pair is mutual, so every round but the last one merges.
+ * complete_fill_kernel quantises the upper triangle, complete_mirror_kernel transposes it; per round complete_best_kernel
+ * (one workgroup per live row: its best partner among the pairs with m >= th_milli, as one 64-bit maximum
+ * m << 32 | 0xFFFFFFFF - j), complete_pair_kernel (one lane per node: mutual pairs merge), complete_rows_kernel
+ * (row A = min(row A, row B)) and complete_cols_kernel (M[R][A] = min(M[R][A], M[R][B]) in every surviving row).
+ * Similarities between clusters only ever fall, so from round 2 on complete_best_kernel keeps a live row's partner without
+ * a scan when the row has none (it is retired: it never gets one again) or when neither the row nor its partner took part
+ * in a merge of the previous round (the partner is still the best); debug key "complete_rescan" = "all" scans every live
+ * row every round, with identical results and round counts.  The host queues "complete_rounds" rounds (hg_ctx_set_debug;
+ * default 4) per readback of the round's merge count and stops at a round that merged nothing.  The worst case, a chain
+ * whose neighbour similarities fall with the index, takes O(n) rounds.
+ * n <= HG_CLUSTER_COMPLETE_MAX_N (the matrix is 17 GB there; 400 MB at 10 000): beyond it HG_ERR_UNSUPPORTED before anything
+ * is allocated, and the next call starts clean; a failed allocation is HG_ERR_OOM; the matrix is released before the call
+ * returns.  n == 0: HG_OK with *n_clusters = 0.  NULL rep, cluster or n_clusters: HG_ERR_INVALID.  Results are final on
+ * return; one clustering at a time per ctx.  Launches count under HG_T_DIST when timing is on.
+ *   hg_cluster_complete_matrix_dev : d_ani, n x n floats, row-major; only [i, j] with i < j is read.  Independent of the
+ *                                    ctx's ANI metric.
+ *   hg_cluster_complete_dev        : resident sketches (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT); the matrix is filled from
+ *                                    row blocks of hg_dist_full_dev -- rows [r0, r1) x columns [r0, n) in a scratch block of
+ *                                    at most HG_SEARCH_BLOCK_BYTES; debug key "complete_block_rows" forces the row count.
+ *   hg_cluster_complete            : host arrays in and out, staged through the ctx. */
+#define HG_CLUSTER_COMPLETE_MAX_N 65536u
+hg_status hg_cluster_complete_matrix_dev(hg_ctx *ctx, const float *d_ani, size_t n, float ani_th, uint32_t *d_rep,
+                                         uint32_t *d_cluster, uint32_t *d_into, float *d_level, uint32_t *d_size, size_t *n_clusters);
+hg_status hg_cluster_complete_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                                  float ani_th, uint32_t *d_rep, uint32_t *d_cluster, uint32_t *d_into, float *d_level,
+                                  uint32_t *d_size, size_t *n_clusters);
+hg_status hg_cluster_complete(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                              float ani_th, uint32_t *rep, uint32_t *cluster, uint32_t *into, float *level, uint32_t *size,
+                              size_t *n_clusters);
+/* rounds of the last complete-linkage call on this ctx, the one that merged nothing included (diagnostic; 0 = none yet) */
+uint64_t hg_ctx_cluster_complete_rounds(const hg_ctx *ctx);
 
 /* Cluster statistics (no reference counterpart): how good a clustering is -- per cluster the medoid, the cohesion (sum and
  * minimum of the within-cluster ANI) and the separation (the nearest item outside), the figures dRep, skDER and galah
