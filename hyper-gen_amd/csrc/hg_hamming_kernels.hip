@@ -180,6 +180,7 @@ static hg_status ham_launch(hg_ctx *c, const uint32_t *d_ref, size_t R, const ui
   else if (cols == 32) hipLaunchKernelGGL(hamming_kernel<2>, grid, dim3(256), 0, c->stream, a);
   else hipLaunchKernelGGL(hamming_kernel<8>, grid, dim3(256), 0, c->stream, a);
   HG_HIP(c, hipGetLastError());
+  c->last_kernel[HG_T_DIST] = cols == 16 ? "hamming_kernel<1>" : cols == 32 ? "hamming_kernel<2>" : "hamming_kernel<8>";
   return HG_OK;
 }
 

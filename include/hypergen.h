@@ -124,6 +124,8 @@ hg_status hg_ctx_timings(hg_ctx *ctx, float ms_sum[HG_T_COUNT], uint32_t launche
 /* name of the kernel the last call launched for timing class `cls` (HG_T_KMER, HG_T_DIST), spelled as rocprofv3
  * prints it ("kmer_sample_shared<21, true, false>", "dist_mfma_kernel<false, false, true, true, 5, true, false, false, false>");
  * "" if none.  A measurement harness uses it to check that a committed profile belongs to the kernel that ran.
+ * HG_T_DIST after a bit-packed Hamming call: the GEMM's dist_mfma_kernel instantiation when the search ran on the matrix pipe,
+ * "hamming_kernel<1>", "<2>" or "<8>" (16, 32 or 128 query columns per tile) when the xor + popcount kernel did the work.
  * HG_T_SORT / HG_T_ENCODE: every kernel the last sketch step (or hg_kmer_hash_sample's sort, hg_hv_encode's encode) queued
  * for the class, in launch order, joined by " + " ("sort_unique_kernel<true> + sort_unique_rest_kernel",
  * "encode_wave_kernel + sketch_finish_kernel"); a step run again later through the synchronous path reports that run.

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import golden
+from payload_models import bp8x_model as _bp8x_model, naive_model as _naive_model
 
 
 def test_t1ha2_upstream_selfcheck(orc):
@@ -174,21 +175,6 @@ def test_pack_roundtrip_and_width(orc):
     assert (stream >> (5 * 9)) & 0x1FF == 7 + 256
 
 
-def _bp8x_model(values, q):
-    """BitPacker8x block from the crate's definition, bit by bit in Python integers (a third formulation, shared with
-    neither oracle/hg_oracle.c nor hg_formats.cpp): lane l = i % 8 owns a stream of 32*q bits, element r = i // 8
-    starts at bit r*q; an unmasked element spills up to bit 31 of its first word and, if it straddles a word
-    boundary, its bits from (32 - c) upwards continue at bit 0 of the next word; word w of lane l = output u32 8w + l."""
-    words = [[0] * 8 for _ in range(q)]
-    for i, v in enumerate(values):
-        lane, p = i % 8, (i // 8) * q
-        w0, c = divmod(p, 32)
-        words[w0][lane] |= (v << c) & 0xFFFFFFFF
-        if c + q > 32:
-            words[w0 + 1][lane] |= v >> (32 - c)
-    return np.array(words, dtype="<u4").tobytes()
-
-
 def test_pack_follows_the_crate_definition_incl_q16_and_partial_blocks(orc):
     rng = np.random.default_rng(11)
     for q in range(6, 17):
@@ -212,18 +198,6 @@ def test_pack_follows_the_crate_definition_incl_q16_and_partial_blocks(orc):
             elif whole:  # every even-indexed element of a lane that was >= 0 spills 0xFFFF into its odd neighbour
                 assert (back[:whole] != hv[:whole]).any()
             assert (back[whole:] == np.int16(-off if q < 16 else -32768)).all()  # 0 as i16 - offset (src/hd.rs:206-212)
-
-
-def _naive_model(hv, q):
-    """third statement of the non-AVX2 layout (src/hd.rs:158-166), on Python integers: the stream is the concatenation of
-    the values' low q bits, LSB first; 16 stream bits per i16 word, (q*d + 16) // 16 words"""
-    bits = []
-    for x in hv:
-        bits += [((int(x) & 0xFFFF) >> k) & 1 for k in range(q)]
-    words = [0] * ((q * len(hv) + 16) // 16)
-    for i, b in enumerate(bits):
-        words[i // 16] |= b << (i % 16)
-    return np.array(words, np.uint16).view(np.int16)
 
 
 def test_naive_layout_follows_the_reference_loops(orc):
