@@ -95,6 +95,7 @@ EXPORTS = [
     "hg_cluster_average_matrix_dev", "hg_cluster_average_dev", "hg_cluster_average", "hg_ctx_cluster_average_rounds",
     "hg_cluster_complete_matrix_dev", "hg_cluster_complete_dev", "hg_cluster_complete", "hg_ctx_cluster_complete_rounds",
     "hg_cluster_stats_matrix_dev", "hg_cluster_stats_dev", "hg_cluster_stats",
+    "hg_nj_matrix_dev", "hg_nj_dev", "hg_nj", "hg_nj_newick",
     "hg_ctx_set_ani_metric", "hg_ctx_ani_metric", "hg_multi_set_ani_metric",
     "hg_search_topk_dev", "hg_search_topk_block_dev", "hg_search_topk", "hg_search_topk_merge", "hg_search_topk_multi_dev",
     "hg_ani_pairs_dev", "hg_ani_pairs",
@@ -103,6 +104,9 @@ SEARCH_TOPK_MAX = 64  # HG_SEARCH_TOPK_MAX
 CLUSTER_AVERAGE_MAX_N = 65536  # HG_CLUSTER_AVERAGE_MAX_N
 CLUSTER_COMPLETE_MAX_N = 65536  # HG_CLUSTER_COMPLETE_MAX_N
 STATS_NONE = 0xFFFFFFFF  # HG_STATS_NONE
+NJ_MAX_N = 65536  # HG_NJ_MAX_N
+NJ_FRAC_BITS = 15  # HG_NJ_FRAC_BITS: a branch length counts 2^-15 thousandths of an ANI percent
+NJ_JOIN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("len_a", "<i8"), ("len_b", "<i8")])  # hg_nj_join, 24 bytes
 
 
 class NodeStat(C.Structure):  # hg_node_stat
@@ -321,6 +325,10 @@ def lib():
         "hg_cluster_stats_matrix_dev": (C.c_int, [vp, vp, sz, vp, sz, vp, vp]),
         "hg_cluster_stats_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
         "hg_cluster_stats": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, vp]),
+        "hg_nj_matrix_dev": (C.c_int, [vp, vp, sz, vp, C.POINTER(sz)]),
+        "hg_nj_dev": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.POINTER(sz)]),
+        "hg_nj": (C.c_int, [vp, vp, vp, sz, C.c_uint32, C.c_uint32, vp, C.POINTER(sz)]),
+        "hg_nj_newick": (C.c_int, [vp, sz, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(sz)]),
         "hg_search_topk_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
         "hg_search_topk_block_dev": (C.c_int, [vp, vp, vp, sz, sz, vp, vp, sz, sz, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
                                                vp, vp]),
@@ -903,6 +911,32 @@ class Context:
         """rounds of the last complete-linkage call on this ctx (hg_ctx_cluster_complete_rounds)"""
         return int(lib().hg_ctx_cluster_complete_rounds(self._h))
 
+    # ---- neighbour joining (hg_nj*) ---------------------------------------------------------------
+    def nj(self, hv, n2, ksize=21):
+        """hg_nj on host sketches: the n - 1 joins of the neighbour-joining tree as a numpy record array of NJ_JOIN_DTYPE
+        (a < b the joined names, the joined node keeps a; len_a, len_b their branches in 2^-15 thousandths of an ANI percent);
+        nj_newick() writes the tree"""
+        h = np.ascontiguousarray(hv, np.int16)
+        nn = np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        joins = np.zeros(max(n, 1) - 1, NJ_JOIN_DTYPE)
+        nj = C.c_size_t(0)
+        self._ck(lib().hg_nj(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, _ptr(joins), C.byref(nj)))
+        return joins[:nj.value]
+
+    def nj_dev(self, d_hv, d_n2, n, hv_d, d_joins, ksize=21):
+        """hg_nj_dev on resident sketches (device pointers; d_joins: n - 1 records of 24 bytes); returns the number of joins"""
+        nj = C.c_size_t(0)
+        self._ck(lib().hg_nj_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, _ptr(d_joins or 0), C.byref(nj)))
+        return nj.value
+
+    def nj_matrix_dev(self, d_ani, n, d_joins):
+        """hg_nj_matrix_dev on a device-resident n x n float matrix, of which [i, j] with i < j is read (d_joins: n - 1
+        records of 24 bytes); returns the number of joins"""
+        nj = C.c_size_t(0)
+        self._ck(lib().hg_nj_matrix_dev(self._h, _ptr(d_ani or 0), n, _ptr(d_joins or 0), C.byref(nj)))
+        return nj.value
+
     # ---- cluster statistics (hg_cluster_stats*) ---------------------------------------------------
     def cluster_stats(self, hv, n2, cluster, n_clusters, ksize=21, node=True, stat=True):
         """hg_cluster_stats on host sketches and a host assignment (cluster[i] < n_clusters, any labelling): numpy record
@@ -1157,6 +1191,25 @@ def sort_ani_hits(hits, Q, symmetric=False):
 
 
 READ_MERGE, READ_NEEDLETAIL = 0, 1
+
+
+def nj_newick(joins, names):
+    """hg_nj_newick: the join list of Context.nj* (NJ_JOIN_DTYPE records, len(names) - 1 of them) and the items' names ->
+    the unrooted tree in Newick form (str; names may be str or bytes).  Raises HgError(ERR_INVALID) for a list that is not a
+    valid join sequence."""
+    j = np.ascontiguousarray(joins, NJ_JOIN_DTYPE)
+    n = len(names)
+    if j.shape != (max(n, 1) - 1,):
+        raise HgError(ERR_INVALID, "nj_newick: %d names take %d joins" % (n, max(n, 1) - 1))
+    arr = (C.c_char_p * max(n, 1))(*[x if isinstance(x, bytes) else str(x).encode() for x in names])
+    p, ln = C.c_void_p(), C.c_size_t(0)
+    st = lib().hg_nj_newick(_ptr(j) if j.size else None, n, arr, C.byref(p), C.byref(ln))
+    if st != OK:
+        raise HgError(st, "hg_nj_newick")
+    try:
+        return C.string_at(p, ln.value).decode()
+    finally:
+        lib().hg_free(p)
 
 
 def read_merge_seq(path, mode=READ_MERGE):

@@ -77,7 +77,7 @@ extern "C" void hg_ctx_destroy(hg_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   hg_ctx::Buf *bufs[] = {&c->w_items, &c->w_gmeta, &c->w_hits, &c->w_cnt, &c->w_seq, &c->w_hv, &c->w_hits2, &c->w_lsort, &c->w_redo, &c->w_pk, &c->w_pktab,
                          &c->w_misc, &c->w_f16a, &c->w_f16b, &c->w_stats, &c->w_ani, &c->w_hv2, &c->w_cen,
-                         &c->w_n2a, &c->w_n2b, &c->w_sorthits, &c->w_clu_res, &c->w_clu, &c->w_clu_hits, &c->w_grd, &c->w_setcover, &c->w_tree, &c->w_average, &c->w_complete, &c->w_cstats, &c->w_srch_blk, &c->w_srch_lists, &c->w_srch_state, &c->w_srch_out, &c->w_i8a, &c->w_i8b, &c->w_i8misc};
+                         &c->w_n2a, &c->w_n2b, &c->w_sorthits, &c->w_clu_res, &c->w_clu, &c->w_clu_hits, &c->w_grd, &c->w_setcover, &c->w_tree, &c->w_average, &c->w_complete, &c->w_nj, &c->w_cstats, &c->w_srch_blk, &c->w_srch_lists, &c->w_srch_state, &c->w_srch_out, &c->w_i8a, &c->w_i8b, &c->w_i8misc};
   for (auto *b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (auto &t : c->tile_tabs) {
@@ -152,6 +152,7 @@ extern "C" hg_status hg_ctx_set_debug(hg_ctx *c, const char *key, const char *va
   else if (k == "complete_rounds") c->dbg_complete_rounds = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_complete*: rounds queued per readback of the merge count
   else if (k == "complete_block_rows") c->dbg_complete_block_rows = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_complete_dev: rows per block of the ANI matrix
   else if (k == "complete_rescan") c->dbg_complete_rescan_all = v == "all";  // hg_cluster_complete*: "all" scans every live row in every round
+  else if (k == "nj_block_rows") c->dbg_nj_block_rows = std::strtoull(v.c_str(), nullptr, 10);  // hg_nj_dev: rows per block of the ANI matrix
   else if (k == "stats_block_rows") c->dbg_stats_block_rows = std::strtoull(v.c_str(), nullptr, 10);  // hg_cluster_stats_dev: rows per block of the ANI matrix
   else if (k == "search_block_rows") c->dbg_search_block_rows = std::strtoull(v.c_str(), nullptr, 10);  // hg_search_topk*: reference rows per block
   else if (k == "dist_path") c->dbg_dist_path = v;

@@ -94,6 +94,7 @@ struct Cli {
   std::string stats_out;       // --stats <file> (cluster): medoid, cohesion and separation of every cluster at -a, one line each
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
+  std::string newick_out;         // --newick <file> (dist on one file): the neighbour-joining tree of all its sketches
   std::bitset<32> given;          // which options the command line carried, by row of `options`
 };
 
@@ -203,6 +204,7 @@ const Option options[] = {
     {"stats", 0, [](Cli &c, const Arg &a) { c.stats_out = a.file(); }, CLUSTER, "it describes the clusters of cluster", ONE_GPU_CLUSTER},
     {"columns", 0, take_columns, DIST, "it adds a pair's other metrics to the lines of dist", ONE_GPU_DIST},
     {"pairs", 0, [](Cli &c, const Arg &a) { c.pairs_file = a.file(); }, DIST, "it names the pairs dist evaluates", ONE_GPU_DIST},
+    {"newick", 0, [](Cli &c, const Arg &a) { c.newick_out = a.file(); }, DIST, "it draws the tree of dist's comparison", ONE_GPU_DIST},
     {"min_count", 0, [](Cli &c, const Arg &a) { c.min_count = (unsigned)a.uint(0xFFFFFFFFull, 1); }, SKETCH,
      "the filter needs the k-mer counts, which a sketch no longer has"},
     // (testing aid: the several-GPU path on fewer GPUs)
@@ -300,6 +302,23 @@ void print_cluster_help() {
               "         within ANI is counted as not separated in the log.  -o is what it is without --stats.\n");
 }
 
+// `hyper-gen dist --help`: the general help with a paragraph on --newick behind it
+void print_dist_help() {
+  print_help();
+  std::printf("\ndist --newick <file>: the neighbour-joining tree of all sketches of the one file -r and -q name, computed on the first\n"
+              "         visible GPU from the dense matrix of all pairs (4 bytes per pair; up to 65536 sketches), whatever -a is.\n"
+              "         The distance of a pair is 100 - ANI as dist prints it, in thousandths, held in fixed point (2^-15\n"
+              "         thousandths); the rule is neighbour joining on integers: with c nodes left and r(i) the sum of a node's\n"
+              "         distances, the pair with the lowest (c - 2) d(i, j) - r(i) - r(j) joins, ties to the pair whose first\n"
+              "         members come first in the file, and the joined node is at (d(a, k) + d(b, k) - d(a, b)) / 2 from every\n"
+              "         other k -- the tree depends on the ANI values alone and can be reproduced from a dist -a 0 TSV.  The\n"
+              "         file is one line of Newick: every label is a name as the TSV carries it, in single quotes, a quote\n"
+              "         inside doubled; the tree is unrooted, its top level has three children; branch lengths are substitutions\n"
+              "         per site, 1 - ANI / 100, with eight decimals, and may be negative, as neighbour joining leaves them\n"
+              "         (nothing is clamped).  -o is what it is without --newick.  It needs --ani_metric mash or\n"
+              "         max_containment and does not go with --pairs or --shards.\n");
+}
+
 Cli parse(int argc, char **argv) {
   if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
   Cli c;
@@ -322,6 +341,10 @@ Cli parse(int argc, char **argv) {
     Arg a{argv[i], "", nullptr};
     if (c.mode_bit == CLUSTER && (a.flag == "--help" || a.flag == "-h")) {
       print_cluster_help();
+      std::exit(0);
+    }
+    if (c.mode_bit == DIST && (a.flag == "--help" || a.flag == "-h")) {
+      print_dist_help();
       std::exit(0);
     }
     const Option *o = nullptr;
@@ -380,6 +403,10 @@ Cli parse(int argc, char **argv) {
     die("invalid value for '--levels': every level must be above -a, the threshold the tree is built at");
   if (c.mode_bit == CLUSTER && c.ani_metric == HG_ANI_CONTAINMENT)
     die("--ani_metric containment is not supported by cluster: it is directional (mash | max_containment)");
+  if (given(c, "newick") && c.path_r != c.path_q) die("--newick needs one sketch file: -r and -q must name the same file");
+  if (given(c, "newick") && c.ani_metric == HG_ANI_CONTAINMENT)
+    die("--ani_metric containment is not supported with --newick: it is directional (mash | max_containment)");
+  if (given(c, "newick") && given(c, "pairs")) die("--pairs is not supported with --newick: the tree needs every pair, not the listed ones");
   return c;
 }
 
@@ -944,7 +971,8 @@ int run_dist(const Cli &c) {
   // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
   const bool sym_full = sym && c.ani_metric == HG_ANI_CONTAINMENT;
   // --columns / --pairs: the pairs' further metrics come from one hg_ani_pairs_dev call on the device list, on one GPU
-  const bool pairs = given(c, "pairs"), one_gpu = pairs || given(c, "columns");
+  // --newick: the neighbour-joining tree of the file's sketches (hg_nj_dev), on that GPU too
+  const bool pairs = given(c, "pairs"), newick = given(c, "newick"), with_cols = pairs || given(c, "columns"), one_gpu = with_cols || newick;
   const uint32_t metric_bit = c.ani_metric == HG_ANI_MASH ? HG_PAIRS_MASH : c.ani_metric == HG_ANI_CONTAINMENT ? HG_PAIRS_CONTAINMENT : HG_PAIRS_MAX_CONTAINMENT;
   uint32_t mask = pairs ? metric_bit : 0u;  // (--pairs: the ANI field itself is a column of the call)
   for (const uint32_t b : c.columns) mask |= b;
@@ -979,9 +1007,9 @@ int run_dist(const Cli &c) {
       // (ordered on the device: dump_ani_file's order, src/utils.rs:262-269 -- two stable radix passes instead of a comparison
       // sort of up to 10^6..10^8 triples on one host core)
       const bool full = sym_full || !sym;
-      found = all_hits(s.multi, R, s.dR, full ? &Q : nullptr, full ? &dq : nullptr, c.ani_th, true, hits, one_gpu ? &d_list : nullptr);
+      found = all_hits(s.multi, R, s.dR, full ? &Q : nullptr, full ? &dq : nullptr, c.ani_th, true, hits, with_cols ? &d_list : nullptr);
     }
-    if (one_gpu && found) {  // the columns of the ordered device list, before the download
+    if (with_cols && found) {  // the columns of the ordered device list, before the download
       DevBuf<float> d_cols(ctx, found * n_cols);
       ck(ctx, hg_ani_pairs_dev(ctx, s.dR.hv[0], s.dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize, d_list.get(), found,
                                mask, d_cols.get(), nullptr), "ani_pairs");
@@ -994,6 +1022,17 @@ int run_dist(const Cli &c) {
         d_list.download(hits.p, found);
       }
     }
+  }
+  std::vector<hg_nj_join> joins;  // --newick: the tree's joins, computed while the sketches are on the device
+  if (newick) {
+    hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+    const double tn = now_s();
+    DevBuf<hg_nj_join> d_joins(ctx, std::max<size_t>(R.n, 2) - 1);
+    size_t n_joins = 0;
+    ck(ctx, hg_nj_dev(ctx, s.dR.hv[0], s.dR.n2[0], R.n, (uint32_t)R.hv_d, R.ksize, d_joins.get(), &n_joins), "nj");
+    joins.resize(n_joins);
+    if (n_joins) d_joins.download(joins.data(), n_joins);
+    debugf("neighbour joining of %zu sketches in %.1f ms", R.n, (now_s() - tn) * 1e3);
   }
   if (sym_full && !pairs) {  // (the pairs i = j are not written: the order of the rest stays)
     size_t w = 0;
@@ -1026,6 +1065,19 @@ int run_dist(const Cli &c) {
     logline("WARN", buf);
   } else {
     std::snprintf(buf, sizeof buf, "Output %zu of %zu ANIs above threshold %.1f to file %s", found, total, c.ani_th, c.out.c_str());
+    logline("INFO", buf);
+  }
+  if (newick) {
+    std::vector<const char *> names(R.n);
+    for (size_t i = 0; i < R.n; ++i) names[i] = hg_sketch_file_get(R.f, i)->file_str;
+    char *text = nullptr;
+    size_t len = 0;
+    if (hg_nj_newick(joins.data(), R.n, names.data(), &text, &len) != HG_OK) die("inconsistent neighbour-joining result");
+    FILE *f = std::fopen(c.newick_out.c_str(), "wb");
+    const bool bad = !f || std::fwrite(text, 1, len, f) != len;
+    if ((f && std::fclose(f) != 0) || bad) die("Dump Newick file failed!");
+    hg_free(text);
+    std::snprintf(buf, sizeof buf, "Output neighbour-joining tree of %zu genomes to file %s", R.n, c.newick_out.c_str());
     logline("INFO", buf);
   }
   std::snprintf(buf, sizeof buf, "Computed ANIs for %zu ref files and %zu query files took %.3fs", R.n, Q.n, now_s() - t0);

@@ -845,3 +845,110 @@ extern "C" hg_status hg_read_merge_seq(const char *path, uint8_t **out, size_t *
 }
 
 extern "C" void hg_free(void *p) { std::free(p); }
+
+// ---- hg_nj_newick: a join list of hg_nj* as an unrooted Newick tree (the contract: include/hypergen.h) ---------------
+namespace {
+// a branch length in substitutions per site with eight decimals, by integers only: t = (|len| * 1000 + 16384) >> 15
+void nj_put_length(std::string &w, int64_t len) {
+  const unsigned __int128 mag = len < 0 ? (unsigned __int128)0 - (unsigned __int128)(__int128)len : (unsigned __int128)len;
+  const unsigned __int128 t = (mag * 1000u + 16384u) >> 15;
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "%s%llu.%08llu", len < 0 && t != 0 ? "-" : "", (unsigned long long)(t / 100000000u),
+                (unsigned long long)(t % 100000000u));
+  w += buf;
+}
+void nj_put_label(std::string &w, const char *name) {
+  w += '\'';
+  for (const char *p = name; *p; ++p) {
+    if (*p == '\'') w += '\'';
+    w += *p;
+  }
+  w += '\'';
+}
+}  // namespace
+
+extern "C" hg_status hg_nj_newick(const hg_nj_join *joins, size_t n, const char *const *names, char **out, size_t *len) {
+  if (!out) return HG_ERR_INVALID;
+  *out = nullptr;
+  if (len) *len = 0;
+  if (n == 0 || n > 0x7FFFFFFFull || !names || (n >= 2 && !joins)) return HG_ERR_INVALID;
+  for (size_t i = 0; i < n; ++i)
+    if (!names[i]) return HG_ERR_INVALID;
+  std::string w;
+  try {
+    // nodes: the leaves 0 .. n - 1, then one per join; at[name] = the node that carries the name now
+    const size_t n_joins = n - 1;
+    std::vector<uint32_t> at(n);
+    std::vector<uint8_t> live(n, 1);
+    for (size_t i = 0; i < n; ++i) at[i] = (uint32_t)i;
+    std::vector<uint32_t> kid_a(n_joins), kid_b(n_joins);  // of node n + t
+    for (size_t t = 0; t < n_joins; ++t) {
+      const hg_nj_join &j = joins[t];
+      if (j.a >= j.b || j.b >= n || !live[j.a] || !live[j.b]) return HG_ERR_INVALID;
+      kid_a[t] = at[j.a], kid_b[t] = at[j.b];
+      at[j.a] = (uint32_t)(n + t), live[j.b] = 0;
+    }
+    // the subtree of a node, without recursion (a caterpillar is n - 1 levels deep): a stack of nodes still to write and
+    // with, for a join, how many of its children are written
+    struct Todo {
+      uint32_t node, kids_done;
+    };
+    std::vector<Todo> todo;
+    auto put_subtree = [&](uint32_t root) {
+      todo.push_back(Todo{root, 0});
+      while (!todo.empty()) {
+        const Todo x = todo.back();
+        todo.pop_back();
+        if (x.node < n) {
+          nj_put_label(w, names[x.node]);
+          continue;
+        }
+        const size_t t = x.node - n;
+        if (x.kids_done == 0) {
+          w += '(';
+          todo.push_back(Todo{x.node, 1});
+          todo.push_back(Todo{kid_a[t], 0});
+        } else if (x.kids_done == 1) {
+          w += ':', nj_put_length(w, joins[t].len_a), w += ',';
+          todo.push_back(Todo{x.node, 2});
+          todo.push_back(Todo{kid_b[t], 0});
+        } else {
+          w += ':', nj_put_length(w, joins[t].len_b), w += ')';
+        }
+      }
+    };
+    if (n == 1) {
+      nj_put_label(w, names[0]);
+    } else if (n == 2) {
+      put_subtree((uint32_t)n);
+    } else {
+      // unrooted: the two children of the second-to-last join and the other side of the last one, by their names
+      const hg_nj_join &p = joins[n - 3], &l = joins[n - 2];
+      if (l.a != p.a && l.b != p.a) return HG_ERR_INVALID;  // (cannot happen in a valid sequence: two names are live)
+      const uint32_t other = l.a == p.a ? l.b : l.a;
+      struct Top {
+        uint32_t name, node;
+        int64_t len;
+      } top[3] = {{p.a, kid_a[n - 3], p.len_a},
+                  {p.b, kid_b[n - 3], p.len_b},
+                  {other, l.a == p.a ? kid_b[n - 2] : kid_a[n - 2], (int64_t)((uint64_t)l.len_a + (uint64_t)l.len_b)}};  // (len_b is 0 in hg_nj*'s lists)
+      std::sort(top, top + 3, [](const Top &x, const Top &y) { return x.name < y.name; });
+      w += '(';
+      for (int k = 0; k < 3; ++k) {
+        if (k) w += ',';
+        put_subtree(top[k].node);
+        w += ':', nj_put_length(w, top[k].len);
+      }
+      w += ')';
+    }
+    w += ';';
+  } catch (const std::bad_alloc &) {
+    return HG_ERR_OOM;
+  }
+  char *buf = static_cast<char *>(std::malloc(w.size() + 1));
+  if (!buf) return HG_ERR_OOM;
+  std::memcpy(buf, w.c_str(), w.size() + 1);
+  *out = buf;
+  if (len) *len = w.size();
+  return HG_OK;
+}

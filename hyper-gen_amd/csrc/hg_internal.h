@@ -127,8 +127,9 @@ struct hg_ctx {
   uint64_t average_rounds = 0;  // rounds the last average-linkage call ran (hg_ctx_cluster_average_rounds)
   Buf w_complete; // hg_cluster_complete*: per-node state, ld entries each -- best partners, absorbed names of the round, sizes, merge sizes, levels (the matrix lives for one call)
   uint64_t complete_rounds = 0;  // rounds the last complete-linkage call ran (hg_ctx_cluster_complete_rounds)
+  Buf w_nj;       // hg_nj*: per-node state, ld entries each -- r() and the row results Q (i64), live marks and the row results j (u32) (the matrix lives for one call)
   Buf w_cstats;   // hg_cluster_stats*: n_clusters accumulators of 48 bytes, then n node records when the caller takes none
-  Buf w_srch_blk;   // hg_search_topk*, hg_cluster_average_dev, hg_cluster_complete_dev, hg_cluster_stats_dev: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
+  Buf w_srch_blk;   // hg_search_topk*, hg_cluster_average_dev, hg_cluster_complete_dev, hg_cluster_stats_dev, hg_nj_dev: one block of the ANI matrix (HG_SEARCH_BLOCK_BYTES at most, unless the hook forces more rows)
   Buf w_srch_lists; // ... the slice lists of one block: keys, then counts
   Buf w_srch_state; // ... the running k best keys per query, state[j * Q + q]
   Buf w_srch_out;   // hg_search_topk: staged results (rows, then counts)
@@ -180,6 +181,7 @@ struct hg_ctx {
   uint64_t dbg_complete_rounds = 0;  // test hook "complete_rounds": rounds hg_cluster_complete* queue per readback of the round's merge count (0: its default)
   uint64_t dbg_complete_block_rows = 0;  // test hook "complete_block_rows": rows per block of the ANI matrix in hg_cluster_complete_dev (0: by HG_SEARCH_BLOCK_BYTES)
   bool dbg_complete_rescan_all = false;  // test hook "complete_rescan" = "all": hg_cluster_complete* scan every live row in every round
+  uint64_t dbg_nj_block_rows = 0;  // test hook "nj_block_rows": rows per block of the ANI matrix in hg_nj_dev (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_stats_block_rows = 0;  // test hook "stats_block_rows": rows per block of the ANI matrix in hg_cluster_stats_dev (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_search_block_rows = 0;  // test hook "search_block_rows": reference rows per block of hg_search_topk* (0: by HG_SEARCH_BLOCK_BYTES)
   uint64_t dbg_hostfed_stage_bytes = 0;  // test hook "hostfed_stage_bytes": bytes at which a sub-batch of hg_sketch_batch closes (0: HG_STAGE_BYTES)

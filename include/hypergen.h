@@ -100,6 +100,8 @@ int hg_device_count(void);
  *                                      HG_SEARCH_BLOCK_BYTES)
  *       "complete_rescan" = "" | "all" ("all": hg_cluster_complete* scan every live row in every round instead of only the
  *                                      rows a merge invalidated.  Both give the same result and the same round count)
+ *       "nj_block_rows" = "<n>"       (rows per block of the ANI matrix in hg_nj_dev; 0 = automatic, from
+ *                                      HG_SEARCH_BLOCK_BYTES)
  *       "stats_block_rows" = "<n>"    (rows per block of the ANI matrix in hg_cluster_stats_dev; 0 = automatic, from
  *                                      HG_SEARCH_BLOCK_BYTES)
  *       "search_block_rows" = "<n>"   (reference rows per matrix block of hg_search_topk*; 0 = automatic, from
@@ -308,7 +310,9 @@ hg_status hg_ani_from_dots_dev(hg_ctx *ctx, const int32_t *d_dot, const int32_t 
  * hg_cluster_greedy{,_dev}, hg_cluster_setcover{,_dev}, hg_cluster_tree{,_dev}, hg_cluster_average{,_dev}, hg_cluster_complete{,_dev} and hg_cluster_stats{,_dev}
  * accept HG_ANI_MASH and HG_ANI_MAX_CONTAINMENT only.  hg_cluster_add_hits_dev, hg_cluster_greedy_hits_dev, hg_cluster_setcover_hits_dev and
  * hg_cluster_tree_hits_dev (they take hits), hg_cluster_average_matrix_dev, hg_cluster_complete_matrix_dev and hg_cluster_stats_matrix_dev (they take the matrix), hg_dist_prep_ops_dev, the
- * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
+ * sort / top-k calls, hg_ani_pairs{,_dev} (its columns name their metrics) and the Hamming search do not depend on it.  hg_nj{,_dev}
+ * read it and accept the two symmetric metrics as clustering does; hg_nj_matrix_dev and hg_nj_newick do not depend on it.
+ * hg_ctx_ani_metric: HG_ANI_MASH on a fresh ctx. */
 #define HG_ANI_MASH 0
 #define HG_ANI_CONTAINMENT 1
 #define HG_ANI_MAX_CONTAINMENT 2
@@ -750,6 +754,72 @@ hg_status hg_cluster_complete(hg_ctx *ctx, const int16_t *hv, const int32_t *nor
                               size_t *n_clusters);
 /* rounds of the last complete-linkage call on this ctx, the one that merged nothing included (diagnostic; 0 = none yet) */
 uint64_t hg_ctx_cluster_complete_rounds(const hg_ctx *ctx);
+
+/* Neighbour joining (no reference counterpart): the distance tree people draw from an all-pairs Mash / ANI table --
+ * mashtree, `mash triangle | rapidnj`, the dendrogram step of pyani and dRep reports.  UPGMA (hg_cluster_average*) assumes a
+ * clock and yields a merge table; neighbour joining does not, and yields an unrooted tree with branch lengths.  Input: n
+ * items and ani(i, j) for i < j -- the float hg_dist_full_dev writes at [i, j].  Everything is decided on integers:
+ *   m(i, j) = the m of average linkage above (hg_avg_milli: NaN and negative values 0, values above 100 100 000, else
+ *             rint((double)ani * 1000.0)): the integer `dist` prints, in thousandths;
+ *   d(i, j) = (100 000 - m(i, j)) << HG_NJ_FRAC_BITS, d(i, i) = 0: a fixed-point distance, one unit = 2^-15 thousandths of
+ *             an ANI percent.  Every d stays in [0, 100 000 << 15], below 2^32: the matrix is u32;
+ *   a node is named by an index; a joined node keeps the smaller of its two children's names; c = the live count, n at first.
+ *   While c >= 3:
+ *     1. r(i) = the sum of d(i, k) over live k != i (integers: the order of summation is irrelevant);
+ *     2. Q(i, j) = (c - 2) d(i, j) - r(i) - r(j) in signed 64 bits (its magnitude is below 2^50 at n = 65 536);
+ *     3. the pair to join is the minimum of (Q, i, j) over live i < j, compared lexicographically and exactly: ties go to
+ *        the smaller lower name, then to the smaller higher name;
+ *     4. for the joined pair a < b and D = d(a, b): len_a = floor(((c - 2) D + r(a) - r(b)) / (2 (c - 2))) -- a floor
+ *        towards minus infinity, not a truncation --, len_b = D - len_a.  Either may be negative; neither is clamped;
+ *     5. for every live k other than a and b: d(a, k) = d(k, a) = max(0, (d(a, k) + d(b, k) - D) >> 1), an arithmetic
+ *        shift (floor).  Then b dies and c becomes c - 1.
+ *   At c = 2 the two live names a < b give the last join (a, b, len_a = d(a, b), len_b = 0).
+ * Result: joins[0 .. n - 2] in this order, hg_nj_join {a, b, len_a, len_b} (24 bytes), lengths in units of 2^-15
+ * thousandths; *n_joins = n - 1 for n >= 2 and 0 for n <= 1.
+ * The result depends on the matrix alone -- not on scheduling or block size -- and anyone can reproduce it from a
+ * `dist -a 0` TSV.  The floor of step 5 loses at most half a unit per update: over 65 535 nested joins the drift is at most
+ * one thousandth of a percent.  The clamp at 0 never acts on an additive (tree) matrix, and an additive matrix whose path
+ * lengths are integers in thousandths is recovered exactly: topology and every branch.
+ * On the device (hg_nj.hip; the three formulas once, in hg_nj_math.h) the matrix is n rows of n rounded up to a multiple
+ * of 4: nj_fill_kernel quantises the upper triangle, nj_mirror_kernel transposes it, nj_rsum_kernel sums the rows.
+ * Neighbour joining is not reducible, so there is one join per round: n - 2 rounds and the last join are queued ahead
+ * without a readback (c is a launch argument).  Per round nj_best_kernel (one workgroup per live row i: the minimum of
+ * (c - 2) d - r(j) over the live columns j > i, ties to the smaller j, from 16-byte loads of the row and of the live marks),
+ * nj_pick_kernel (one workgroup: the minimum of (Q, i) over the rows, the join, b dies) and nj_update_kernel (one lane per
+ * k: row and column a, r(k), and r(a) by one 64-bit atomic add per workgroup).  Scanning only the columns above the row
+ * halves the traffic; the scan still reads about n^3 / 4 words over the whole call, dead columns included.
+ * n <= HG_NJ_MAX_N (the matrix is 17 GB there; 400 MB at 10 000): beyond it HG_ERR_UNSUPPORTED before anything is
+ * allocated; a failed allocation is HG_ERR_OOM; the matrix is released before the call returns and the ctx is usable
+ * afterwards.  n == 0 and n == 1: HG_OK with *n_joins = 0.  NULL joins or n_joins (or inputs): HG_ERR_INVALID.  Results are
+ * final on return.  Launches count under HG_T_DIST when timing is on.
+ *   hg_nj_matrix_dev : d_ani, n x n floats, row-major; only [i, j] with i < j is read.  Independent of the ctx's ANI metric.
+ *   hg_nj_dev        : resident sketches (HG_ANI_MASH or HG_ANI_MAX_CONTAINMENT; the directional metric is HG_ERR_INVALID as
+ *                      in clustering); the matrix is filled from row blocks of hg_dist_full_dev -- rows [r0, r1) x columns
+ *                      [r0, n) in a scratch block of at most HG_SEARCH_BLOCK_BYTES; debug key "nj_block_rows" forces the
+ *                      row count.
+ *   hg_nj            : host arrays in and out, staged through the ctx.
+ *   hg_nj_newick     : host only, no ctx.  joins[0 .. n - 2] of n >= 1 items and their n names -> the unrooted tree in Newick
+ *                      form, a NUL-terminated string in *out (hg_free releases it), its length without the NUL in *len (len
+ *                      may be NULL).  Every label is single-quoted, an inner ' doubled.  An inner node is
+ *                      (sub(a):len_a,sub(b):len_b), a first.  n = 1: 'name';  n = 2: ('a':L,'b':0.00000000);  n >= 3: the top
+ *                      level is a trifurcation of the two children of the second-to-last join and the other side of the last
+ *                      join, each with its length, in increasing order of their names (a subtree's name is its smallest leaf
+ *                      index).  A length is printed in substitutions per site, 1 - ANI / 100, with eight decimals, by
+ *                      integers only: t = (|len| * 1000 + 16384) >> 15, then an optional '-' (only if len < 0 and t != 0),
+ *                      t / 10^8, '.', and t % 10^8 zero-padded.  A join list that is not a valid sequence (a >= b, a name
+ *                      >= n, a dead name reused), n == 0 or a NULL argument: HG_ERR_INVALID, never a read out of bounds. */
+#define HG_NJ_FRAC_BITS 15
+#define HG_NJ_MAX_N 65536u
+typedef struct {
+  uint32_t a, b;        /* the joined names, a < b; the joined node is called a */
+  int64_t len_a, len_b; /* their branches to the joined node, in units of 2^-15 thousandths of an ANI percent */
+} hg_nj_join;
+hg_status hg_nj_matrix_dev(hg_ctx *ctx, const float *d_ani, size_t n, hg_nj_join *d_joins, size_t *n_joins);
+hg_status hg_nj_dev(hg_ctx *ctx, const int16_t *d_hv, const int32_t *d_norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                    hg_nj_join *d_joins, size_t *n_joins);
+hg_status hg_nj(hg_ctx *ctx, const int16_t *hv, const int32_t *norm2, size_t n, uint32_t hv_d, uint32_t ksize,
+                hg_nj_join *joins, size_t *n_joins);
+hg_status hg_nj_newick(const hg_nj_join *joins, size_t n, const char *const *names, char **out, size_t *len);
 
 /* Cluster statistics (no reference counterpart): how good a clustering is -- per cluster the medoid, the cohesion (sum and
  * minimum of the within-cluster ANI) and the separation (the nearest item outside), the figures dRep, skDER and galah
