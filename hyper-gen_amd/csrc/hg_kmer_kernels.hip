@@ -16,8 +16,8 @@
 //    ADDRESS: one v_cndmask picks the image, the hash words are ds_reads with immediate offsets -- no instruction
 //    touches the bytes;
 //  * t1ha2 is specialised per k; for k = 17..32 the whole k-mer body (word reads, three or four mixup64 stages,
-//    final64, candidate compare on the high dword) is one asm statement on fixed register pairs: 56 / 66 vector
-//    instructions, 25 / 30 of them v_mad_u64_u32;
+//    final64, candidate compare on the high dword) is one asm statement on fixed register pairs: 55 / 65 vector
+//    instructions, 24 / 29 of them v_mad_u64_u32 (the first mixup multiplies a bounded operand: HG_KS_BOUNDED_FIRST);
 //  * survivors (1/scaled of the k-mers) are staged in a small LDS list and the workgroup reserves its range of the
 //    genome's hit slice with ONE global atomic at the end of its work item; lossless: no 8-slot cap like
 //    src/cuda_kernel.cu:316, hash value 0 is kept;
@@ -256,7 +256,8 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 // that goes through an SGPR pair.  Here all temporaries are fixed physical registers, every result is produced in the
 // pair that consumes it, carries go through VCC into a VOP2 v_addc (no SGPR read hazard), and what is left is what the
 // ISA forces: the high dword of a product is an ODD register and a 64-bit addend has to start at an EVEN one -- one
-// v_mov per 128-bit product (into the pair Z = {x, 0}).  56 vector instructions per hash + candidate compare instead of 64.
+// v_mov per 128-bit product (into the pair Z = {x, 0}).  56 vector instructions per hash + candidate compare instead of 64
+// (55 with the bounded first mixup, HG_KS_MUL128_BOUNDED below).
 //   v[56:61] / v[62:67]  hash words of k-mer j / j+1 (filled by HG_KS_READ one k-mer ahead)
 //   Z v[68:69]  H v71 (hash high dword)  X v[72:73]  A v[74:75]  T v[76:77]  U v[78:79]  S1 v[80:81]  S2 v[82:83]  R v[84:85]
 //   Y v[86:87]  C v[88:89]
@@ -268,6 +269,28 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_mad_u64_u32 " OUT ", %[junk], v77, 1, " ADDEND "\n\t"                                     \
   "v_mad_u64_u32 " OUT ", %[junk], " XHI ", " PHI ", " OUT "\n\t"                              \
   "v_addc_co_u32_e32 " OUTHI ", vcc, 0, " OUTHI ", vcc\n\t"
+// The FIRST mixup's multiplicand is x = s + w0 with s wave-uniform and small (the seed, k <= 24; the length K, k >= 25)
+// and w0 eight staged bytes, each one of "ACGT" in every k-mer that is KEPT: both phase images are written from the
+// code -> ASCII lookups, whatever the input byte was, so w0.lo, w0.hi <= 0x54545454.  (Lanes whose k-mers are discarded
+// anyway -- lookahead lanes, slots a dead wave did not stage -- may multiply anything: the stage is arithmetic only, no
+// address depends on it.)  With s below FIRST_SEED_END (first_mixup_bounded() below evaluates the worst case):
+//   * no carry leaves the low dword of s + w0: x0 = w0.lo + s is one 32-bit add and x1 is w0.hi as read;
+//   * W = x0 p1 + x1 p0 + hi32(x0 p0) < 2^64: the third product has no carry-out, so the v_addc goes;
+//   * hi32(W) + s < 2^32 (the stage's addend is s as well): the "x 1" product is one 32-bit add into Z's low half, and
+//     the last product takes Z as its addend, as HG_KS_FINAL's does.
+// One v_lshl_add_u64, one v_mad_u64_u32 and one v_addc_co_u32 become two v_add_u32: 7 instructions instead of 8.
+// ADD32: s as a 32-bit operand (an SGPR or an inline constant).  Z's high half stays 0.
+#ifndef HG_KS_BOUNDED_FIRST
+#define HG_KS_BOUNDED_FIRST 1  /* first mixup on bounded operands (0: the general text for every seed, A/B) */
+#endif
+#define HG_KS_MUL128_BOUNDED(W0L, W0H, PLO, PHI, ADD32, OUT)                                   \
+  "v_add_u32_e32 v72, " ADD32 ", " W0L "\n\t"                                                  \
+  "v_mad_u64_u32 v[74:75], %[junk], v72, " PLO ", 0\n\t"                                       \
+  "v_mov_b32 v68, v75\n\t"                                                                     \
+  "v_mad_u64_u32 v[76:77], %[junk], " W0H ", " PLO ", v[68:69]\n\t"                            \
+  "v_mad_u64_u32 v[76:77], %[junk], v72, " PHI ", v[76:77]\n\t"                                \
+  "v_add_u32_e32 v68, " ADD32 ", v77\n\t"                                                      \
+  "v_mad_u64_u32 " OUT ", %[junk], " W0H ", " PHI ", v[68:69]\n\t"
 // lo64(x * P) -> {OLO, OHI} (a pair): three chained products and one add into the pair's own high half
 #define HG_KS_LO64(XLO, XHI, PLO, PHI, OUT, OLO_UNUSED, OHI)                                   \
   "v_mad_u64_u32 " OUT ", %[junk], " XLO ", " PLO ", 0\n\t"                                    \
@@ -330,8 +353,9 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 // the two word buffers: (R0..R7) and the same as register pairs; K <= 24 uses the first three pairs
 #define HG_KS_REGS0 ("56", "57", "58", "59", "60", "61", "90", "91")
 #define HG_KS_REGS1 ("62", "63", "64", "65", "66", "67", "92", "93")
-#define HG_KS_PAIRS0 ("v[56:57]", "v[58:59]", "v[60:61]", "v[90:91]")
-#define HG_KS_PAIRS1 ("v[62:63]", "v[64:65]", "v[66:67]", "v[92:93]")
+// (in front: the first word's two dwords by name, for the bounded first mixup)
+#define HG_KS_PAIRS0 ("v56", "v57", "v[56:57]", "v[58:59]", "v[60:61]", "v[90:91]")
+#define HG_KS_PAIRS1 ("v62", "v63", "v[62:63]", "v[64:65]", "v[66:67]", "v[92:93]")
 #define HG_KS_APPLY(M, ARGS) M ARGS
 // final64(a, b): x = (a + rot64(b, 41)) * P0, y = (rot64(a, 23) + b) * P6 (low halves), z = x ^ y, mux64(z, P5), compare.
 // The compare only marks CANDIDATES: hi32(h) <= hi32(threshold), one 32-bit compare on the high dword's v_xor instead of
@@ -358,11 +382,25 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_addc_co_u32_e32 v79, vcc, 0, v79, vcc\n\t"                                                                      \
   "v_xor_b32_e32 v71, v76, v79\n\t"                                                                                  \
   "v_cmp_ge_u32_e64 %[mask], %[thrh], v71"
-// 17 <= K <= 24: three stages
-#define HG_KS_HASH_TEXT_3(W0, W1, W2, W3)                                                                            \
-  /* mixup64<P3>(b, a, w0): x = seed + w0; b = K ^ lo; a = seed + hi */                                              \
+// The first mixup: lo64 -> {v74, v76}, hi64 + s -> U.  _FULL: the general text, any 64-bit seed; the other one is the bounded
+// text where HG_KS_BOUNDED_FIRST is set.
+//   17 <= K <= 24, mixup64<P3>(b, a, w0): x = seed + w0; b = K ^ lo; a = seed + hi
+//   25 <= K <= 32, mixup64<P4>(a, b, w0): x = K + w0; a = seed ^ lo; b = K + hi
+#define HG_KS_FIRST_FULL_3(W0L, W0H, W0)                                                                             \
   "v_lshl_add_u64 v[72:73], " W0 ", 0, %[seed]\n\t"                                                                  \
-  HG_KS_MUL128("v72", "v73", "%[p3l]", "%[p3h]", "%[seed]", "v[78:79]", "v79")                                       \
+  HG_KS_MUL128("v72", "v73", "%[p3l]", "%[p3h]", "%[seed]", "v[78:79]", "v79")
+#define HG_KS_FIRST_FULL_4(W0L, W0H, W0)                                                                             \
+  "v_lshl_add_u64 v[72:73], " W0 ", 0, %[kk]\n\t"                                                                    \
+  HG_KS_MUL128("v72", "v73", "%[p4l]", "%[p4h]", "%[kk]", "v[78:79]", "v79")
+#if HG_KS_BOUNDED_FIRST
+#define HG_KS_FIRST_3(W0L, W0H, W0) HG_KS_MUL128_BOUNDED(W0L, W0H, "%[p3l]", "%[p3h]", "%[seedl]", "v[78:79]")
+#define HG_KS_FIRST_4(W0L, W0H, W0) HG_KS_MUL128_BOUNDED(W0L, W0H, "%[p4l]", "%[p4h]", "%[kk]", "v[78:79]")
+#else
+#define HG_KS_FIRST_3(W0L, W0H, W0) HG_KS_FIRST_FULL_3(W0L, W0H, W0)
+#define HG_KS_FIRST_4(W0L, W0H, W0) HG_KS_FIRST_FULL_4(W0L, W0H, W0)
+#endif
+// 17 <= K <= 24: three stages
+#define HG_KS_REST_3(W1, W2, W3)                                                                                     \
   "v_xor_b32_e32 v80, %[kk], v74\n\t"                                                                                \
   "v_mov_b32 v81, v76\n\t"                                                                                           \
   /* mixup64<P2>(a, b, w1): x = b + w1; a ^= lo; b += hi   (a = U, b = S1 -> a = S2, b = R) */                       \
@@ -376,11 +414,11 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v80, v84, v74\n\t"                                                                                  \
   "v_xor_b32_e32 v81, v85, v76\n\t"                                                                                  \
   HG_KS_FINAL("v[78:79]", "v78", "v79", "v[80:81]", "v80", "v81")
+#define HG_KS_HASH_TEXT_3(W0L, W0H, W0, W1, W2, W3) HG_KS_FIRST_3(W0L, W0H, W0) HG_KS_REST_3(W1, W2, W3)
+#define HG_KS_HASH_FULL_TEXT_3(W0L, W0H, W0, W1, W2, W3) HG_KS_FIRST_FULL_3(W0L, W0H, W0) HG_KS_REST_3(W1, W2, W3)
 // 25 <= K <= 32: four stages (the first one's b is the length, a small constant)
-#define HG_KS_HASH_TEXT_4(W0, W1, W2, W3)                                                                            \
-  /* mixup64<P4>(a, b, w0): x = K + w0; a = seed ^ lo; b = K + hi   (-> a = S1, b = U) */                            \
-  "v_lshl_add_u64 v[72:73], " W0 ", 0, %[kk]\n\t"                                                                    \
-  HG_KS_MUL128("v72", "v73", "%[p4l]", "%[p4h]", "%[kk]", "v[78:79]", "v79")                                         \
+#define HG_KS_REST_4(W1, W2, W3)                                                                                     \
+  /* (first mixup: -> a = S1, b = U) */                                                                              \
   "v_xor_b32_e32 v80, %[seedl], v74\n\t"                                                                             \
   "v_xor_b32_e32 v81, %[seedh], v76\n\t"                                                                             \
   /* mixup64<P3>(b, a, w1): x = a + w1; b ^= lo; a += hi   (a = S1, b = U -> b = S2, a = R) */                       \
@@ -399,6 +437,8 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v82, v78, v74\n\t"                                                                                  \
   "v_xor_b32_e32 v83, v79, v76\n\t"                                                                                  \
   HG_KS_FINAL("v[84:85]", "v84", "v85", "v[82:83]", "v82", "v83")
+#define HG_KS_HASH_TEXT_4(W0L, W0H, W0, W1, W2, W3) HG_KS_FIRST_4(W0L, W0H, W0) HG_KS_REST_4(W1, W2, W3)
+#define HG_KS_HASH_FULL_TEXT_4(W0L, W0H, W0, W1, W2, W3) HG_KS_FIRST_FULL_4(W0L, W0H, W0) HG_KS_REST_4(W1, W2, W3)
 #define HG_KS_HASH_INPUTS                                                                                            \
   [seed] "s"(seed), [thrh] "s"((uint32_t)(threshold >> 32)), [kk] "n"(K), [p0l] "s"((uint32_t)P0), [p0h] "s"((uint32_t)(P0 >> 32)),     \
       [p1l] "s"((uint32_t)P1), [p1h] "s"((uint32_t)(P1 >> 32)), [p2l] "s"((uint32_t)P2), [p2h] "s"((uint32_t)(P2 >> 32)), \
@@ -447,6 +487,27 @@ constexpr bool geos_one_geometry_per_class(std::integer_sequence<int, Ks...>) {
            GeoS<Ks + 1>::SPAN == GeoS<(Ks + 1 <= 21 ? 21 : 32)>::SPAN) && ...);
 }
 static_assert(geos_one_geometry_per_class(std::make_integer_sequence<int, 32>{}), "TILE, TILES and SPAN depend on K only through WIN");
+
+// The bounded first mixup (HG_KS_MUL128_BOUNDED) at its worst case: both dwords of w0 are "TTTT" -- every staged byte of a
+// kept k-mer is one of ACGT -- and s (operand and addend of the stage: the seed for k <= 24, K for k >= 25) is the largest
+// one admitted.  Every term grows with x0, x1 and s, so the maxima decide.
+constexpr uint64_t FIRST_SEED_END = 1ull << 28;  // k = 17..24: seeds from here on take the general text (they hold up to 0x66C7395F)
+constexpr bool first_mixup_bounded(uint64_t P, uint64_t s) {
+  const uint64_t p0 = (uint32_t)P, p1 = P >> 32, x1 = 0x54545454ull, x0 = x1 + s;
+  if (s >> 32 || x0 >> 32) return false;                                              // x0 = w0.lo + s is a 32-bit add
+  const unsigned __int128 W = (unsigned __int128)x0 * p1 + (unsigned __int128)x1 * p0 + ((x0 * p0) >> 32);
+  if (W >> 64) return false;                                                           // no carry out of the third product
+  const uint64_t z = (uint64_t)(W >> 32) + s;
+  if (z >> 32) return false;                                                           // hi32(W) + s is a 32-bit add
+  return (((unsigned __int128)x1 * p1 + z) >> 64) == 0;                               // hi64 + s < 2^64
+}
+template <int... Ks>
+constexpr bool first_mixup_bounded_k25_32(std::integer_sequence<int, Ks...>) {
+  return (first_mixup_bounded(P4, 25 + Ks) && ...);
+}
+static_assert(first_mixup_bounded(P3, FIRST_SEED_END - 1), "k = 17..24: first mixup's bounds at the largest admitted seed");
+static_assert(first_mixup_bounded_k25_32(std::make_integer_sequence<int, 8>{}), "k = 25..32: first mixup's bounds with s = K");
+static_assert(first_mixup_bounded(P3, 0x66C7395Full) && !first_mixup_bounded(P3, 0x66C73960ull), "where the k = 17..24 bounds end");
 
 // PACKED: the genome is a hg_pack2 blob (include/hypergen.h: 2-bit codes, 4 bases per byte, then the not-a-base bitmap;
 // 0.375 bytes per base in HBM instead of 1) and the tile level does no classification at all: a lane fetches its whole
@@ -891,30 +952,35 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
 #define HG_KS_FIRST(C, N)                                                                                             \
   if constexpr (KCASE == C)                                                                                           \
     asm volatile(HG_KS_APPLY(HG_KS_READ_TEXT_##C, HG_KS_REGS0) : HG_KS_OUT0 : [base] "v"(base), HG_KS_OFFS);
-#define HG_KS_EVEN(C, N)                                                                                              \
-  if constexpr (KCASE == C)                                                                                           \
+// (each k-mer statement twice: the first mixup's bounded text, FB, and the general one; one of them is compiled)
+#define HG_KS_EVEN(C, N) HG_KS_EVEN1(C, HG_KS_HASH_TEXT_##N, FB) HG_KS_EVEN1(C, HG_KS_HASH_FULL_TEXT_##N, !FB)
+#define HG_KS_ODD(C, N) HG_KS_ODD1(C, HG_KS_HASH_TEXT_##N, FB) HG_KS_ODD1(C, HG_KS_HASH_FULL_TEXT_##N, !FB)
+#define HG_KS_LAST(C, N) HG_KS_LAST1(C, HG_KS_HASH_TEXT_##N, FB) HG_KS_LAST1(C, HG_KS_HASH_FULL_TEXT_##N, !FB)
+#define HG_KS_EVEN1(C, HASH, COND)                                                                                    \
+  if constexpr (KCASE == C && (COND))                                                                                 \
     asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS0) HG_KS_APPLY(HG_KS_READ_TEXT_##C, HG_KS_REGS1) "\n\t"   \
-                 HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS0)                                                       \
+                 HG_KS_APPLY(HASH, HG_KS_PAIRS0)                                                                      \
                  : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair), HG_KS_OUT1     \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), [base] "v"(base), HG_KS_OFFS, HG_KS_IN0                    \
                  : HG_KS_HASH_CLOBBERS);
-#define HG_KS_ODD(C, N)                                                                                               \
-  if constexpr (KCASE == C)                                                                                           \
+#define HG_KS_ODD1(C, HASH, COND)                                                                                     \
+  if constexpr (KCASE == C && (COND))                                                                                 \
     asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS1) HG_KS_APPLY(HG_KS_READ_TEXT_##C, HG_KS_REGS0) "\n\t"   \
-                 HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS1)                                                       \
+                 HG_KS_APPLY(HASH, HG_KS_PAIRS1)                                                                      \
                  : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair), HG_KS_OUT0     \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), [base] "v"(base), HG_KS_OFFS, HG_KS_IN1                    \
                  : HG_KS_HASH_CLOBBERS);
-#define HG_KS_LAST(C, N)                                                                                              \
-  if constexpr (KCASE == C)                                                                                           \
-    asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS1) HG_KS_APPLY(HG_KS_HASH_TEXT_##N, HG_KS_PAIRS1)         \
+#define HG_KS_LAST1(C, HASH, COND)                                                                                    \
+  if constexpr (KCASE == C && (COND))                                                                                 \
+    asm volatile(HG_KS_APPLY(HG_KS_WAIT_TEXT_##C, HG_KS_REGS1) HG_KS_APPLY(HASH, HG_KS_PAIRS1)                        \
                  : [mask] "=s"(hmask), [junk] "=&s"(hjunk), "=&{v74}"(hlo0), "=&{v78}"(hlo1), "=&{v71}"(hhi), "={v[68:69]}"(zpair)                 \
                  : HG_KS_HASH_INPUTS, "{v[68:69]}"(zpair), HG_KS_IN1                                                  \
                  : HG_KS_HASH_CLOBBERS);
 #define HG_KS_ALL_CASES(X) X(51, 3) X(52, 3) X(53, 3) X(54, 3) X(61, 3) X(62, 3) X(63, 3) X(64, 3) \
                            X(71, 4) X(72, 4) X(73, 4) X(74, 4) X(81, 4) X(82, 4) X(83, 4) X(84, 4)
-    auto kmers_asm = [&](auto checkc) __attribute__((always_inline)) {
+    auto kmers_asm = [&](auto checkc, auto boundedc) __attribute__((always_inline)) {
       constexpr bool CHECK = decltype(checkc)::value;
+      constexpr bool FB = decltype(boundedc)::value;  // first mixup: the bounded text
       if constexpr (ASM_BODY) {
         {
           const uint32_t base = strand_base(std::integral_constant<int, 0>{});
@@ -947,6 +1013,9 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
 #undef HG_KS_EVEN
 #undef HG_KS_ODD
 #undef HG_KS_LAST
+#undef HG_KS_EVEN1
+#undef HG_KS_ODD1
+#undef HG_KS_LAST1
     auto run_kmers = [&](auto checkc) __attribute__((always_inline)) {
       constexpr bool CHECK = decltype(checkc)::value;
       static_for(std::make_integer_sequence<int, M>{}, [&](auto jc) {
@@ -964,8 +1033,19 @@ __global__ __launch_bounds__(WG) void kmer_sample_shared(
     // (Every wave of an interior tile has starts; an edge tile made the test beside its staging test above.)
     if (wave_live) {
       if constexpr (ASM_BODY) {
-        if (!tile_dirty) kmers_asm(std::false_type{});
-        else kmers_asm(std::true_type{});
+        // The first mixup's bounded text holds for every seed where its s is K (K >= 25) and for seeds below
+        // FIRST_SEED_END where s is the seed (K <= 24); a larger seed takes the general text.  A scalar test of the kernel
+        // argument once per tile and a second pair of loop copies in the K <= 24 kernels -- not an instantiation picked at
+        // launch: the set of compiled kernels, their names and the launch table stay what they are, the object grows by
+        // the same two loop copies either way, and the test costs a scalar compare and branch per 3 048 k-mers.
+        constexpr bool ANY_SEED = !HG_KS_BOUNDED_FIRST || NW == 4;  // one text serves every seed
+        if (ANY_SEED || seed < FIRST_SEED_END) {
+          if (!tile_dirty) kmers_asm(std::false_type{}, std::true_type{});
+          else kmers_asm(std::true_type{}, std::true_type{});
+        } else if constexpr (!ANY_SEED) {
+          if (!tile_dirty) kmers_asm(std::false_type{}, std::false_type{});
+          else kmers_asm(std::true_type{}, std::false_type{});
+        }
       } else {
         if (!tile_dirty) run_kmers(std::false_type{});
         else run_kmers(std::true_type{});

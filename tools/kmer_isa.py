@@ -14,7 +14,8 @@ The kernel is compiled to gfx950 assembly with the flags of hyper-gen_amd/csrc/M
     global_load v, v_off, s[base]: all tiles of a genome but its last one or two) is the tile level; the edge tile's
     copy (64-bit vector addresses, genome-end arithmetic) is a rare path.
 Not on the main path ("rare"): the u/U -> T rewrite (HG_NORM_U2T only), the per-base validity mask (tiles with a non-base
-or a genome end), the second copy of the k-mer loop (same instructions, with the validity test in its hit path), hit
+or a genome end), the other copies of the k-mer loop (the same instructions with the validity test in the hit path; both
+again with the first mixup's general text, for seeds of 2^28 and more), hit
 staging (1 k-mer in `scaled`), byte-wise tail loads, prologue / epilogue.
 The per-k-mer budget is what bench.py's valu_issue object is priced with; the dynamic count (SQ_INSTS_VALU * 64 /
 k-mers, profiles/<tag>_pmc.json) must agree with it up to the rare paths and the idle lanes (2 of 256 hash nothing).
@@ -107,8 +108,12 @@ def main():
     cnt = [collections.Counter(o for o, _ in b) for _, b in blocks]
     text = [" ".join(t for _, t in b) for _, b in blocks]
     hash_blocks = [i for i, c in enumerate(cnt) if c["v_mad_u64_u32"] >= 20]
-    assert len(hash_blocks) == 2 * M, "expected two copies of the %d-k-mer loop, found %d hash blocks" % (M, len(hash_blocks))
-    body = hash_blocks[:M]   # (the two copies' main-path blocks are the same instructions)
+    # copies of the 12-k-mer loop: clean and dirty tiles (their main-path blocks are the same instructions), and both once
+    # more with the first mixup's general text, which seeds of 2^28 and more take (HG_KS_BOUNDED_FIRST); the main path is
+    # the first copy with the fewest products
+    assert len(hash_blocks) in (2 * M, 4 * M), "expected two or four copies of the %d-k-mer loop, found %d hash blocks" % (M, len(hash_blocks))
+    copies = [hash_blocks[i:i + M] for i in range(0, len(hash_blocks), M)]
+    body = min(copies, key=lambda c: sum(cnt[i]["v_mad_u64_u32"] for i in c))
     md = blocks[hash_blocks[0]][0]  # loop depth of the tile loop (1 until round 5; 2 since the work items of a group are a loop around it)
     # the edge tile's staging copy: from the block that forms the wave's 64-bit start (or loads through a vector address) to the
     # block in front of the tile's first barrier -- or of the interior copy, should the compiler lay that one out second

@@ -18,6 +18,7 @@ ap.add_argument("--k", type=int, default=21)
 ap.add_argument("--canonical", type=int, default=1)
 ap.add_argument("--reps", type=int, default=15)
 ap.add_argument("--settle", type=int, default=25)
+ap.add_argument("--seed", type=int, default=123, help="hash seed (k = 17..24: 2^28 and more take the first mixup's general text)")
 ap.add_argument("--packed", type=int, default=0, help="1: the genomes are resident as hg_pack2 blobs (hg_sketch_batch_dev_packed)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -28,7 +29,7 @@ seq = torch.empty(a.genomes * stride + 64, dtype=torch.uint8, device=dev)
 ctx.synth_genomes_dev(0, a.genomes, a.L, stride, seq.data_ptr())
 offs = np.arange(a.genomes, dtype=np.uint64) * stride
 lens = np.full(a.genomes, a.L + 1, np.uint64)
-p = hg.default_params(ksize=a.k, canonical=a.canonical)
+p = hg.default_params(ksize=a.k, canonical=a.canonical, seed=a.seed)
 hv = torch.empty((a.genomes, p.hv_d), dtype=torch.int16, device=dev)
 n2 = torch.empty(a.genomes, dtype=torch.int32, device=dev)
 nh = torch.empty(a.genomes, dtype=torch.int32, device=dev)
