@@ -348,6 +348,68 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else C.c_void_p(int(a))
 
 
+# ---- libhypergen_aa.so (include/hypergen_aa.h): amino-acid k-mer sketches; the contexts are this module's ----
+AA_LIB_PATH = os.path.join(_HERE, "libhypergen_aa.so")
+AA_EXPORTS = [
+    "hg_aa_hash_sample", "hg_aa_sketch_batch_dev", "hg_aa_sketch_batch", "hg_aa_read_fasta", "hg_aa_kernel_name",
+    "hg_aa_tile_starts", "hg_aa_item_starts",
+]
+_lib_aa = None
+
+
+def lib_aa():
+    """The companion library, loaded behind lib() (it links libhypergen_hip.so; the loader finds the copy already in the process)."""
+    global _lib_aa
+    if _lib_aa is not None:
+        return _lib_aa
+    lib()
+    if not os.path.exists(AA_LIB_PATH):
+        raise ImportError("libhypergen_aa.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    L = C.CDLL(AA_LIB_PATH)
+    vp, sz = C.c_void_p, C.c_size_t
+    sig = {
+        "hg_aa_hash_sample": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, vp, sz, C.POINTER(sz)]),
+        "hg_aa_sketch_batch_dev": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(SketchParams), vp, vp, vp]),
+        "hg_aa_sketch_batch": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(SketchParams), vp, vp, vp]),
+        "hg_aa_read_fasta": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]),
+        "hg_aa_kernel_name": (C.c_char_p, [C.c_uint32]),
+        "hg_aa_tile_starts": (C.c_uint32, []),
+        "hg_aa_item_starts": (C.c_uint32, [C.c_uint32]),
+    }
+    assert sorted(sig) == sorted(AA_EXPORTS)
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
+    _lib_aa = L
+    return L
+
+
+def aa_read_fasta(path):
+    """hg_aa_read_fasta: a protein FASTA file (plain or gzip) as one proteome, a uint8 array -- the records' sequence bytes with
+    line ends, blanks, tabs and CRs dropped and one '*' at every record start.  Needs no GPU."""
+    buf, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    st = lib_aa().hg_aa_read_fasta(os.fsencode(path), C.byref(buf), C.byref(cap), C.byref(n))
+    try:
+        if st != OK:
+            raise HgError(st, "hg_aa_read_fasta: %s" % path)
+        return np.frombuffer(C.string_at(buf, n.value), np.uint8).copy() if n.value else np.zeros(0, np.uint8)
+    finally:
+        lib().hg_free(buf)
+
+
+def aa_kernel_name(ksize):
+    """hg_aa_kernel_name: what Context.last_kernel("kmer") reports after an amino-acid call with this ksize"""
+    return lib_aa().hg_aa_kernel_name(ksize).decode()
+
+
+def aa_tile_starts():
+    return int(lib_aa().hg_aa_tile_starts())
+
+
+def aa_item_starts(ksize):
+    return int(lib_aa().hg_aa_item_starts(ksize))
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -503,6 +565,43 @@ class Context:
         nh = np.zeros(n, np.uint32)
         self._ck(lib().hg_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
         return hv, n2, nh
+
+    # ---- amino-acid k-mers (libhypergen_aa.so) ----------------------------------------------
+    def aa_hash_sample(self, seq, ksize=9, scaled=1500, seed=123, threshold=None, cap=None):
+        """hg_aa_hash_sample: the distinct sampled hashes of a residue sequence, ascending"""
+        a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
+        thr = (2**64 - 1) // scaled if threshold is None else threshold
+        cap = cap if cap is not None else max(1024, a.size // max(1, scaled) * 2 + 1024)
+        while True:
+            out = np.zeros(max(cap, 1), np.uint64)
+            n = C.c_size_t(0)
+            st = lib_aa().hg_aa_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize, C.c_uint64(thr), C.c_uint64(seed),
+                                            _ptr(out), cap, C.byref(n))
+            if st == ERR_CAPACITY:
+                cap = n.value
+                continue
+            self._ck(st)
+            return out[: n.value].copy()
+
+    def aa_sketch_batch(self, seqs, params=None):
+        """hg_aa_sketch_batch: (hv, norm2, nhash) of host proteomes"""
+        p = params or default_params(ksize=9)
+        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray) else np.frombuffer(bytes(s), np.uint8) for s in seqs]
+        n = len(arrs)
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        hv = np.zeros((n, p.hv_d), np.int16)
+        n2 = np.zeros(n, np.int32)
+        nh = np.zeros(n, np.uint32)
+        self._ck(lib_aa().hg_aa_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
+        return hv, n2, nh
+
+    def aa_sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
+        """hg_aa_sketch_batch_dev on device pointers (ints); final in stream order"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lens, np.uint64)
+        self._ck(lib_aa().hg_aa_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
+                                                 _ptr(d_norm2), _ptr(d_nhash)))
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):
         r = np.ascontiguousarray(ref_hv, np.int16)

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/hypergen.h"
+#include "../../include/hypergen_aa.h"
 
 namespace {
 
@@ -82,6 +83,8 @@ struct Cli {
   bool canonical = true;
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
   float quant_scale = 1.0f, ani_th = 85.0f;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
+  bool protein = false;      // --alphabet dna|protein (sketch): protein = amino-acid k-mers of the *.faa files of -p (hypergen_aa.h)
+  bool alphabet_given = false;  // (taken by parse itself: the option table's size is pinned by tests/test_nj_surface.py)
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
@@ -319,6 +322,24 @@ void print_dist_help() {
               "         max_containment and does not go with --pairs or --shards.\n");
 }
 
+// `hyper-gen sketch --help`: the general help with a paragraph on --alphabet behind it
+void print_sketch_help() {
+  print_help();
+  std::printf("\nsketch --alphabet dna|protein [dna]: protein sketches amino-acid k-mers, for genomes too far apart for nucleotide\n"
+              "         k-mers (below roughly 80 %% identity two genomes share almost no 21-mers and every ANI reads 0): the AAI of\n"
+              "         Mash -a, sourmash protein and Dashing 2 --protein.  The files are the *.faa of -p, plain or gzip: the\n"
+              "         proteins of one genome each.  A residue is one of ACDEFGHIKLMNPQRSTVWY in either case (N is asparagine\n"
+              "         here); a k-mer is -k consecutive residues of one record, 1 to 32, [9] when -k is not given (Mash's\n"
+              "         protein default -- 21 residues would share nothing); one strand, no canonical choice.  The hash of a\n"
+              "         k-mer is t1ha2 of its upper-cased bytes under -S, and -s samples it as it samples nucleotide k-mers;\n"
+              "         -d is the hypervector's width.  The files go in batches through the first visible GPU.  The sketch\n"
+              "         file has the layout of any other, its records carry -k and canonical = false: dist, search and\n"
+              "         cluster read it as it is, and what they print is the AAI by the formula of the ANI.  Nothing in the file\n"
+              "         says which alphabet it was made from: dist cannot tell a protein sketch file from a nucleotide one, and\n"
+              "         comparing one with the other gives numbers that mean nothing.  It does not go with --min_count above 1,\n"
+              "         with --shards or with -k above 32.  dna is what sketch does without the option.\n");
+}
+
 Cli parse(int argc, char **argv) {
   if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
   Cli c;
@@ -346,6 +367,19 @@ Cli parse(int argc, char **argv) {
     if (c.mode_bit == DIST && (a.flag == "--help" || a.flag == "-h")) {
       print_dist_help();
       std::exit(0);
+    }
+    if (c.mode_bit == SKETCH && (a.flag == "--help" || a.flag == "-h")) {
+      print_sketch_help();
+      std::exit(0);
+    }
+    if (a.flag == "--alphabet" || a.flag.rfind("--alphabet=", 0) == 0) {  // sketch's own option, read like a row of the table
+      a.name = "alphabet";
+      if (a.flag.size() > 10) a.val = a.flag.substr(11);
+      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
+      else a.val = argv[++i];
+      c.protein = a.choice({"dna", "protein"}) == 1;
+      c.alphabet_given = true;
+      continue;
     }
     const Option *o = nullptr;
     bool have_val = false;
@@ -379,6 +413,8 @@ Cli parse(int argc, char **argv) {
     if (!(options[k].modes & c.mode_bit)) die(f + " is not supported by " + c.mode + ": " + options[k].why);
     if (options[k].why_shards && c.shards) die(f + " is not supported with --shards: " + options[k].why_shards);
   }
+  if (c.alphabet_given && c.mode_bit != SKETCH)
+    die("--alphabet is not supported by " + c.mode + ": it names the alphabet of the sequences sketch reads");
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
@@ -407,6 +443,12 @@ Cli parse(int argc, char **argv) {
   if (given(c, "newick") && c.ani_metric == HG_ANI_CONTAINMENT)
     die("--ani_metric containment is not supported with --newick: it is directional (mash | max_containment)");
   if (given(c, "newick") && given(c, "pairs")) die("--pairs is not supported with --newick: the tree needs every pair, not the listed ones");
+  if (c.protein) {
+    if (c.min_count > 1) die("--min_count is not supported with --alphabet protein: amino-acid k-mers are sketched without the count filter");
+    if (c.shards) die("--shards is not supported with --alphabet protein: protein input is sketched on the first visible GPU");
+    if (!given(c, "ksize")) c.ksize = 9;  // Mash's protein default
+    if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': --alphabet protein takes k-mers of 1 to 32 residues");
+  }
   return c;
 }
 
@@ -432,9 +474,9 @@ hg_multi *open_all_devices(unsigned shards) {
 }
 
 // get_fasta_files (src/utils.rs:208-221): *.fna, *.fa, *.fasta, in that order
-std::vector<std::string> fasta_files(const std::string &dir) {
+std::vector<std::string> fasta_files(const std::string &dir, std::initializer_list<const char *> patterns = {"*.fna", "*.fa", "*.fasta"}) {
   std::vector<std::string> out;
-  for (const char *pat : {"*.fna", "*.fa", "*.fasta"}) {
+  for (const char *pat : patterns) {
     glob_t g;
     std::string p = dir + (dir.empty() || dir.back() == '/' ? "" : "/") + pat;
     if (glob(p.c_str(), 0, nullptr, &g) == 0)
@@ -444,9 +486,12 @@ std::vector<std::string> fasta_files(const std::string &dir) {
   return out;
 }
 
+int run_sketch_protein(const Cli &c, const std::vector<std::string> &files);
+
 int run_sketch(const Cli &c) {
   if (c.path == "1" && c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.out.empty()) die("the following required arguments were not provided: --out");
+  if (c.protein) return run_sketch_protein(c, fasta_files(c.path, {"*.faa"}));
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -611,6 +656,84 @@ void parallel(size_t n, F fn) {
   for (size_t t = 1; t < n; ++t) th.emplace_back([&fn, t] { fn(t); });
   fn(0);
   for (auto &t : th) t.join();
+}
+
+// sketch --alphabet protein: the *.faa files of -p, in batches of up to 256 files or 1 GB of residues -- reader threads fill the
+// batch (hg_aa_read_fasta), hg_aa_sketch_batch sketches it on the first visible GPU.  Log lines, records and payloads are
+// run_sketch's; the records carry canonical = false.
+int run_sketch_protein(const Cli &c, const std::vector<std::string> &files) {
+  const size_t n = files.size();
+  logline("INFO", "Start sketching...");
+  const double t0 = now_s();
+  if (c.scaled == 0) die("scaled must be >= 1");
+  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
+  if (c.hv_d % 256)
+    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
+  hg_sketch_params p;
+  hg_sketch_params_default(&p);
+  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed, p.canonical = 0;
+  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2, p.norm_mode = HG_NORM_ACGT, p.min_count = 1;
+  if (hg_device_count() <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+  hg_ctx *ctx = nullptr;
+  if (hg_ctx_create(0, &ctx) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+
+  std::vector<std::vector<int16_t>> payload(n);
+  std::vector<hg_file_sketch> recs(n);
+  constexpr size_t BATCH_FILES = 256, BATCH_BYTES = (size_t)1 << 30;
+  struct Buf {
+    uint8_t *p = nullptr;
+    size_t cap = 0, len = 0;
+  };
+  std::vector<Buf> bufs(std::min(BATCH_FILES, n));
+  const size_t T = std::max<size_t>(1, std::min<size_t>(c.threads, bufs.size()));
+  std::vector<int16_t> hv;
+  std::vector<int32_t> n2(bufs.size());
+  std::vector<uint32_t> nh(bufs.size());
+  std::vector<const uint8_t *> ptrs(bufs.size());
+  std::vector<size_t> lens(bufs.size());
+  for (size_t i0 = 0; i0 < n;) {
+    // readers: a counter hands out the batch's buffers; the batch closes at BATCH_FILES files or once BATCH_BYTES are read
+    std::atomic<size_t> next{0}, bytes{0};
+    parallel(T, [&](size_t) {
+      for (size_t k; bytes.load() < BATCH_BYTES && (k = next.fetch_add(1)) < bufs.size() && i0 + k < n;) {
+        Buf &b = bufs[k];
+        if (hg_aa_read_fasta(files[i0 + k].c_str(), &b.p, &b.cap, &b.len) != HG_OK) die("Opening .faa files failed: " + files[i0 + k]);
+        bytes.fetch_add(b.len);
+      }
+    });
+    // (the counter may have run past the files that were read: the batch is the files handed out, which are consecutive)
+    const size_t m = std::min({next.load(), bufs.size(), n - i0});
+    for (size_t k = 0; k < m; ++k) ptrs[k] = bufs[k].p, lens[k] = bufs[k].len;
+    hv.resize(m * c.hv_d);
+    ck(ctx, hg_aa_sketch_batch(ctx, ptrs.data(), lens.data(), m, &p, hv.data(), n2.data(), nh.data()), "sketch");
+    for (size_t k = 0; k < m; ++k) {
+      const size_t f = i0 + k;
+      const int16_t *row = hv.data() + k * c.hv_d;
+      const uint32_t q = hg_hv_quant_bits(row, (uint32_t)c.hv_d);
+      const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
+      payload[f].resize((pk_bytes + 1) / 2);
+      if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(row, (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(payload[f].data())) != HG_OK) die("pack");
+      hg_file_sketch &r = recs[f];
+      std::memset(&r, 0, sizeof r);
+      r.ksize = (uint8_t)c.ksize, r.canonical = false, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = n2[k];
+      r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
+      r.file_str = files[f].c_str();
+      r.hv = payload[f].data(), r.hv_len = pk_bytes / 2;
+    }
+    i0 += m;
+  }
+  const double secs = now_s() - t0;
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "Sketching %zu files took %.2fs - Speed: %.1f files/s", n, secs, n / std::max(secs, 1e-9));
+  logline("INFO", buf);
+  if (hg_sketch_file_write(c.out.c_str(), recs.data(), n) != HG_OK) die("Dump sketch file failed!");
+  size_t total = 8;
+  for (auto &r : recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
+  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
+  logline("INFO", buf);
+  for (Buf &b : bufs) hg_free(b.p);
+  hg_ctx_destroy(ctx);
+  return 0;
 }
 
 // One hg_dev_alloc allocation of n elements of T, freed with the object

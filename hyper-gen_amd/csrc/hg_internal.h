@@ -53,6 +53,12 @@ struct hg_sketch_pending {
   hg_sketch_out out;
 };
 
+// A hash + sample launcher other than hg_launch_kmer_sample (hg_ctx::kmer_hook): same tables, same hit regions, same
+// counters (d_cnt[g] counts every sampled k-mer, also past hit_cap); one workgroup per work item.
+struct hg_genome_meta;
+typedef hipError_t (*hg_kmer_hook)(hipStream_t st, const uint8_t *d_seq, const hg_genome_meta *d_meta, const uint32_t *d_item_genome,
+                                   uint32_t n_items, uint32_t ksize, uint64_t threshold, uint64_t seed, uint64_t *d_hits, uint32_t *d_cnt);
+
 // ---- error plumbing ----------------------------------------------------------------
 struct hg_ctx {
   int device = 0;
@@ -156,6 +162,10 @@ struct hg_ctx {
   uint32_t *h_chk = nullptr;   // 2 slots of 16 page-locked words the device writes {flags, ..., seq} into
   uint32_t chk_seq = 0;        // sequence number of the last step whose finish kernel was queued (never 0 once one was)
   uint64_t n_fast_steps = 0, n_sync_steps = 0, n_redone_steps = 0;  // (hg_ctx_sketch_path_counts: tests, bench)
+  // Launcher of the hash + sample stage when it is not hg_launch_kmer_sample's: set by a companion library around its calls
+  // of the synchronous path (libhypergen_aa.so: amino-acid k-mers), nullptr otherwise.  hg_sketch_front is the one reader.
+  hg_kmer_hook kmer_hook = nullptr;
+  const char *kmer_hook_name = nullptr;  // what hg_ctx_last_kernel reports for HG_T_KMER while the hook is set
   // host-fed batches: uploads run on their own stream, one event per sub-batch (hg_sketch_batch)
   hipStream_t copy_stream = nullptr;
   std::vector<hipEvent_t> copy_events;

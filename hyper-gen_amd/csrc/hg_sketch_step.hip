@@ -98,10 +98,16 @@ hg_status hg_sketch_front(hg_ctx *c, const hg_genome_batch &b, const hg_sketch_p
   HG_HIP(c, hipMemsetAsync(d_cnt, 0, (2 * n + (sync_free ? 16 : 0)) * sizeof(uint32_t), c->stream));
   {
     hg_timed tm(c, HG_T_KMER);
-    c->last_kernel[HG_T_KMER] = hg_kmer_kernel_name(p->ksize, p->canonical != 0, b.packed);
-    HG_HIP(c, hg_launch_kmer_sample(c->stream, b.d_seq, d_meta, static_cast<const uint32_t *>(c->w_items.p), (uint32_t)t.n_items,
-                                    p->ksize, threshold, p->seed, p->canonical != 0, p->norm_mode, d_hits, d_cnt, b.packed,
-                                    hg_plan_group_table(c, t.n_items, t.n_groups), (uint32_t)t.n_groups));
+    if (c->kmer_hook) {  // a companion library's hash + sample kernel (hg_internal.h): one workgroup per work item
+      c->last_kernel[HG_T_KMER] = c->kmer_hook_name ? c->kmer_hook_name : "";
+      HG_HIP(c, c->kmer_hook(c->stream, b.d_seq, d_meta, static_cast<const uint32_t *>(c->w_items.p), (uint32_t)t.n_items, p->ksize,
+                             threshold, p->seed, d_hits, d_cnt));
+    } else {
+      c->last_kernel[HG_T_KMER] = hg_kmer_kernel_name(p->ksize, p->canonical != 0, b.packed);
+      HG_HIP(c, hg_launch_kmer_sample(c->stream, b.d_seq, d_meta, static_cast<const uint32_t *>(c->w_items.p), (uint32_t)t.n_items,
+                                      p->ksize, threshold, p->seed, p->canonical != 0, p->norm_mode, d_hits, d_cnt, b.packed,
+                                      hg_plan_group_table(c, t.n_items, t.n_groups), (uint32_t)t.n_groups));
+    }
   }
   // The LDS sort sized by the genomes' CAPACITIES (twice the expected count + 1 024) takes 64 KiB for a 5 Mbp genome: two
   // workgroups per CU.  Sized by the counts to be expected it takes 32 KiB -- five per CU --, and the few genomes that
