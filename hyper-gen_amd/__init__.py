@@ -410,6 +410,82 @@ def aa_item_starts(ksize):
     return int(lib_aa().hg_aa_item_starts(ksize))
 
 
+# ---- libhypergen_tx.so (include/hypergen_tx.h): six-frame translated protein sketches from DNA ----
+TX_LIB_PATH = os.path.join(_HERE, "libhypergen_tx.so")
+TX_EXPORTS = [
+    "hg_tx_hash_sample", "hg_tx_sketch_batch_dev", "hg_tx_sketch_batch", "hg_tx_translate_frame", "hg_tx_kernel_name",
+    "hg_tx_tile_starts", "hg_tx_item_starts", "hg_tx_plan_describe", "hg_tx_plan_regrows",
+]
+_lib_tx = None
+
+
+def lib_tx():
+    """The second companion library, loaded behind lib() like lib_aa()."""
+    global _lib_tx
+    if _lib_tx is not None:
+        return _lib_tx
+    lib()
+    if not os.path.exists(TX_LIB_PATH):
+        raise ImportError("libhypergen_tx.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    L = C.CDLL(TX_LIB_PATH)
+    vp, sz = C.c_void_p, C.c_size_t
+    sig = {
+        "hg_tx_hash_sample": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, vp, sz, C.POINTER(sz)]),
+        "hg_tx_sketch_batch_dev": (C.c_int, [vp, vp, vp, vp, sz, C.POINTER(SketchParams), vp, vp, vp]),
+        "hg_tx_sketch_batch": (C.c_int, [vp, C.POINTER(vp), C.POINTER(sz), sz, C.POINTER(SketchParams), vp, vp, vp]),
+        "hg_tx_translate_frame": (C.c_int, [vp, sz, C.c_uint32, vp, sz, C.POINTER(sz)]),
+        "hg_tx_kernel_name": (C.c_char_p, [C.c_uint32]),
+        "hg_tx_tile_starts": (C.c_uint32, []),
+        "hg_tx_item_starts": (C.c_uint32, [C.c_uint32]),
+        "hg_tx_plan_describe": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, vp]),
+        "hg_tx_plan_regrows": (C.c_uint64, [vp]),
+    }
+    assert sorted(sig) == sorted(TX_EXPORTS)
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
+    _lib_tx = L
+    return L
+
+
+def tx_translate_frame(seq, frame):
+    """hg_tx_translate_frame: reading frame 0..5 of a nucleotide sequence as bytes, stops '*', codons with a non-base 'X'.
+    Needs no GPU."""
+    a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
+    out = np.zeros(a.size // 3 + 1, np.uint8)
+    n = C.c_size_t(0)
+    st = lib_tx().hg_tx_translate_frame(_ptr(a) if a.size else None, a.size, frame, _ptr(out), out.size, C.byref(n))
+    if st != OK:
+        raise HgError(st, "hg_tx_translate_frame")
+    return out[: n.value].tobytes()
+
+
+def tx_plan_describe(lens, ksize, scaled, offsets=None):
+    """hg_tx_plan_describe: dict of the translated plan's figures for genomes of these lengths (offsets default to a 64-byte grid)"""
+    ln = np.ascontiguousarray(lens, np.uint64)
+    if offsets is None:
+        offsets = np.concatenate(([0], np.cumsum((ln + np.uint64(32 + 63)) // np.uint64(64) * np.uint64(64))[:-1])) if ln.size else []
+    off = np.ascontiguousarray(offsets, np.uint64)
+    counts = np.zeros(6, np.uint64)
+    st = lib_tx().hg_tx_plan_describe(_ptr(off), _ptr(ln), ln.size, ksize, C.c_uint64(scaled), _ptr(counts))
+    if st != OK:
+        raise HgError(st, "hg_tx_plan_describe")
+    return dict(zip(("items", "slots", "max_cap", "min_cap", "max_expect", "item_starts"), (int(x) for x in counts)))
+
+
+def tx_kernel_name(ksize):
+    """hg_tx_kernel_name: what Context.last_kernel("kmer") reports after a translated call with this ksize"""
+    return lib_tx().hg_tx_kernel_name(ksize).decode()
+
+
+def tx_tile_starts():
+    return int(lib_tx().hg_tx_tile_starts())
+
+
+def tx_item_starts(ksize):
+    return int(lib_tx().hg_tx_item_starts(ksize))
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -601,6 +677,47 @@ class Context:
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lens, np.uint64)
         self._ck(lib_aa().hg_aa_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
+                                                 _ptr(d_norm2), _ptr(d_nhash)))
+
+    # ---- six-frame translated k-mers (libhypergen_tx.so) -------------------------------------
+    def tx_hash_sample(self, seq, ksize=9, scaled=1500, seed=123, threshold=None, cap=None):
+        """hg_tx_hash_sample: the distinct sampled hashes of the six frames of a nucleotide sequence, ascending"""
+        a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
+        thr = (2**64 - 1) // scaled if threshold is None else threshold
+        cap = cap if cap is not None else max(1024, 2 * a.size // max(1, scaled) * 2 + 1024)
+        while True:
+            out = np.zeros(max(cap, 1), np.uint64)
+            n = C.c_size_t(0)
+            st = lib_tx().hg_tx_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize, C.c_uint64(thr), C.c_uint64(seed),
+                                            _ptr(out), cap, C.byref(n))
+            if st == ERR_CAPACITY:
+                cap = n.value
+                continue
+            self._ck(st)
+            return out[: n.value].copy()
+
+    def tx_plan_regrows(self):
+        """hg_tx_plan_regrows: how often this ctx's synchronous sketch path rebuilt a plan after a hit region overflowed"""
+        return int(lib_tx().hg_tx_plan_regrows(self._h))
+
+    def tx_sketch_batch(self, seqs, params=None):
+        """hg_tx_sketch_batch: (hv, norm2, nhash) of host genomes (ASCII)"""
+        p = params or default_params(ksize=9)
+        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray) else np.frombuffer(bytes(s), np.uint8) for s in seqs]
+        n = len(arrs)
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+        hv = np.zeros((n, p.hv_d), np.int16)
+        n2 = np.zeros(n, np.int32)
+        nh = np.zeros(n, np.uint32)
+        self._ck(lib_tx().hg_tx_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
+        return hv, n2, nh
+
+    def tx_sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
+        """hg_tx_sketch_batch_dev on device pointers (ints); final in stream order"""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        ln = np.ascontiguousarray(lens, np.uint64)
+        self._ck(lib_tx().hg_tx_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
                                                  _ptr(d_norm2), _ptr(d_nhash)))
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):

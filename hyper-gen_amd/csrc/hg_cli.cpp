@@ -33,6 +33,7 @@
 
 #include "../../include/hypergen.h"
 #include "../../include/hypergen_aa.h"
+#include "../../include/hypergen_tx.h"
 
 namespace {
 
@@ -85,6 +86,7 @@ struct Cli {
   float quant_scale = 1.0f, ani_th = 85.0f;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
   bool protein = false;      // --alphabet dna|protein (sketch): protein = amino-acid k-mers of the *.faa files of -p (hypergen_aa.h)
   bool alphabet_given = false;  // (taken by parse itself: the option table's size is pinned by tests/test_nj_surface.py)
+  bool translate = false;    // --translate (sketch): amino-acid k-mers of the six reading frames of the nucleotide files (hypergen_tx.h); parse's own too
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
@@ -338,6 +340,19 @@ void print_sketch_help() {
               "         says which alphabet it was made from: dist cannot tell a protein sketch file from a nucleotide one, and\n"
               "         comparing one with the other gives numbers that mean nothing.  It does not go with --min_count above 1,\n"
               "         with --shards or with -k above 32.  dna is what sketch does without the option.\n");
+  std::printf("\nsketch --translate: sketches the amino-acid k-mers of all six reading frames of the nucleotide files of -p (the\n"
+              "         files sketch reads anyway: *.fna, *.fa, *.fasta, plain or gzip), so that AAI needs no gene caller first:\n"
+              "         sourmash's sketch translate.  It takes no value.  A base is one of ACGT in either case; codons translate\n"
+              "         by the standard genetic code (NCBI table 1); a codon with any other byte in it (N, IUPAC codes) and a\n"
+              "         stop end a k-mer, as a non-residue does under --alphabet protein.  Frames 1 to 3 start at the first,\n"
+              "         second and third base, frames 4 to 6 are those of the reverse complement; a k-mer is -k consecutive\n"
+              "         residues of one frame, 1 to 32, [9] when -k is not given; both strands contribute, no canonical choice.\n"
+              "         The hash is the one --alphabet protein takes of the same residues, so the k-mers of a genome's called\n"
+              "         proteins are a subset of its translated ones: dist --ani_metric containment of a protein sketch against\n"
+              "         a translated one says whether those proteins are encoded in that assembly.  The files go in batches\n"
+              "         through the first visible GPU; the records carry -k in residues and canonical = false, and dist, search\n"
+              "         and cluster print the AAI.  It does not go with --alphabet protein (protein input is not translated),\n"
+              "         with --min_count above 1, with --shards or with -k above 32.\n");
 }
 
 Cli parse(int argc, char **argv) {
@@ -381,6 +396,10 @@ Cli parse(int argc, char **argv) {
       c.alphabet_given = true;
       continue;
     }
+    if (a.flag == "--translate") {  // sketch's own switch, no value
+      c.translate = true;
+      continue;
+    }
     const Option *o = nullptr;
     bool have_val = false;
     if (a.flag.rfind("--", 0) == 0) {
@@ -415,6 +434,8 @@ Cli parse(int argc, char **argv) {
   }
   if (c.alphabet_given && c.mode_bit != SKETCH)
     die("--alphabet is not supported by " + c.mode + ": it names the alphabet of the sequences sketch reads");
+  if (c.translate && c.mode_bit != SKETCH)
+    die("--translate is not supported by " + c.mode + ": it translates the nucleotide sequences sketch reads");
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
@@ -443,6 +464,13 @@ Cli parse(int argc, char **argv) {
   if (given(c, "newick") && c.ani_metric == HG_ANI_CONTAINMENT)
     die("--ani_metric containment is not supported with --newick: it is directional (mash | max_containment)");
   if (given(c, "newick") && given(c, "pairs")) die("--pairs is not supported with --newick: the tree needs every pair, not the listed ones");
+  if (c.translate) {
+    if (c.protein) die("--translate is not supported with --alphabet protein: protein input is not translated");
+    if (c.min_count > 1) die("--min_count is not supported with --translate: amino-acid k-mers are sketched without the count filter");
+    if (c.shards) die("--shards is not supported with --translate: translated input is sketched on the first visible GPU");
+    if (!given(c, "ksize")) c.ksize = 9;  // as for --alphabet protein
+    if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': --translate takes k-mers of 1 to 32 residues");
+  }
   if (c.protein) {
     if (c.min_count > 1) die("--min_count is not supported with --alphabet protein: amino-acid k-mers are sketched without the count filter");
     if (c.shards) die("--shards is not supported with --alphabet protein: protein input is sketched on the first visible GPU");
@@ -486,12 +514,13 @@ std::vector<std::string> fasta_files(const std::string &dir, std::initializer_li
   return out;
 }
 
-int run_sketch_protein(const Cli &c, const std::vector<std::string> &files);
+int run_sketch_batches(const Cli &c, const std::vector<std::string> &files);
 
 int run_sketch(const Cli &c) {
   if (c.path == "1" && c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.out.empty()) die("the following required arguments were not provided: --out");
-  if (c.protein) return run_sketch_protein(c, fasta_files(c.path, {"*.faa"}));
+  if (c.protein) return run_sketch_batches(c, fasta_files(c.path, {"*.faa"}));
+  if (c.translate) return run_sketch_batches(c, fasta_files(c.path));
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -658,10 +687,13 @@ void parallel(size_t n, F fn) {
   for (auto &t : th) t.join();
 }
 
-// sketch --alphabet protein: the *.faa files of -p, in batches of up to 256 files or 1 GB of residues -- reader threads fill the
-// batch (hg_aa_read_fasta), hg_aa_sketch_batch sketches it on the first visible GPU.  Log lines, records and payloads are
+// sketch --alphabet protein and sketch --translate: the files in batches of up to 256 files or 1 GB of sequence -- reader
+// threads fill the batch (the *.faa files through hg_aa_read_fasta; the nucleotide files through the reader run_sketch uses),
+// hg_aa_sketch_batch or hg_tx_sketch_batch sketches it on the first visible GPU.  Log lines, records and payloads are
 // run_sketch's; the records carry canonical = false.
-int run_sketch_protein(const Cli &c, const std::vector<std::string> &files) {
+int run_sketch_batches(const Cli &c, const std::vector<std::string> &files) {
+  const bool tx = c.translate;
+  const uint32_t read_mode = c.device == "gpu" ? HG_READ_MERGE : HG_READ_NEEDLETAIL;  // (run_sketch's choice)
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
   const double t0 = now_s();
@@ -697,7 +729,9 @@ int run_sketch_protein(const Cli &c, const std::vector<std::string> &files) {
     parallel(T, [&](size_t) {
       for (size_t k; bytes.load() < BATCH_BYTES && (k = next.fetch_add(1)) < bufs.size() && i0 + k < n;) {
         Buf &b = bufs[k];
-        if (hg_aa_read_fasta(files[i0 + k].c_str(), &b.p, &b.cap, &b.len) != HG_OK) die("Opening .faa files failed: " + files[i0 + k]);
+        const char *path = files[i0 + k].c_str();
+        const hg_status rs = tx ? hg_read_fastx_into(path, read_mode, &b.p, &b.cap, &b.len) : hg_aa_read_fasta(path, &b.p, &b.cap, &b.len);
+        if (rs != HG_OK) die(std::string("Opening ") + (tx ? ".fna" : ".faa") + " files failed: " + files[i0 + k]);
         bytes.fetch_add(b.len);
       }
     });
@@ -705,7 +739,7 @@ int run_sketch_protein(const Cli &c, const std::vector<std::string> &files) {
     const size_t m = std::min({next.load(), bufs.size(), n - i0});
     for (size_t k = 0; k < m; ++k) ptrs[k] = bufs[k].p, lens[k] = bufs[k].len;
     hv.resize(m * c.hv_d);
-    ck(ctx, hg_aa_sketch_batch(ctx, ptrs.data(), lens.data(), m, &p, hv.data(), n2.data(), nh.data()), "sketch");
+    ck(ctx, (tx ? hg_tx_sketch_batch : hg_aa_sketch_batch)(ctx, ptrs.data(), lens.data(), m, &p, hv.data(), n2.data(), nh.data()), "sketch");
     for (size_t k = 0; k < m; ++k) {
       const size_t f = i0 + k;
       const int16_t *row = hv.data() + k * c.hv_d;

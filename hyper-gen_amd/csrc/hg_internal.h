@@ -21,6 +21,7 @@ struct hg_sketch_plan {
   std::vector<uint64_t> offs, lens, masks;  // the caller's arrays (masks empty: bitmaps directly behind the codes)
   std::vector<uint32_t> caps;               // hit_cap per genome
   uint32_t ksize = 0;
+  uint32_t span = 0, per_start = 1;         // bytes a k-mer window spans, k-mers a start yields (hg_plan_shape: ksize and 1 but for a hook)
   bool packed = false;
   uint64_t scaled = 0, total_slots = 0;
   uint32_t max_cap = 0;
@@ -162,10 +163,14 @@ struct hg_ctx {
   uint32_t *h_chk = nullptr;   // 2 slots of 16 page-locked words the device writes {flags, ..., seq} into
   uint32_t chk_seq = 0;        // sequence number of the last step whose finish kernel was queued (never 0 once one was)
   uint64_t n_fast_steps = 0, n_sync_steps = 0, n_redone_steps = 0;  // (hg_ctx_sketch_path_counts: tests, bench)
+  uint64_t n_plan_regrows = 0;  // attempts of the synchronous path that rebuilt a plan because a hit region overflowed (hg_tx_plan_regrows: tests)
   // Launcher of the hash + sample stage when it is not hg_launch_kmer_sample's: set by a companion library around its calls
   // of the synchronous path (libhypergen_aa.so: amino-acid k-mers), nullptr otherwise.  hg_sketch_front is the one reader.
   hg_kmer_hook kmer_hook = nullptr;
   const char *kmer_hook_name = nullptr;  // what hg_ctx_last_kernel reports for HG_T_KMER while the hook is set
+  // ... and what its kernel makes of a genome, for the plan: the bytes one k-mer window spans (0: ksize) and the k-mers one
+  // start yields (libhypergen_tx.so: 3 * ksize and 2, a codon per residue and both strands)
+  uint32_t kmer_hook_span = 0, kmer_hook_per_start = 1;
   // host-fed batches: uploads run on their own stream, one event per sub-batch (hg_sketch_batch)
   hipStream_t copy_stream = nullptr;
   std::vector<hipEvent_t> copy_events;

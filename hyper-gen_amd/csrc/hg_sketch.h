@@ -32,17 +32,31 @@ inline const uint32_t *hg_plan_group_table(const hg_ctx *c, size_t n_items, size
   return n_groups ? static_cast<const uint32_t *>(c->w_items.p) + hg_plan_group_offset(n_items) : nullptr;
 }
 
+// What the hash + sample kernel makes of a genome, as far as the plan's sizes go: a k-mer window spans `span` bytes (0: ksize
+// of them) and every start yields `per_start` k-mers.  (ksize, 1) for the nucleotide kernels and the amino-acid hook; a hook
+// that says otherwise sets hg_ctx::kmer_hook_span / kmer_hook_per_start.  A genome of n bytes then has n - span + 1 starts,
+// (n - span + 1) * per_start k-mers -- the bound of its hit region -- and that many / scaled expected hits.
+struct hg_plan_shape {
+  uint32_t span = 0, per_start = 1;
+};
+inline hg_plan_shape hg_ctx_plan_shape(const hg_ctx *c) {
+  return c->kmer_hook ? hg_plan_shape{c->kmer_hook_span, c->kmer_hook_per_start} : hg_plan_shape{};
+}
+
 // want_caps: optional per-genome minimum capacities (retry after overflow); c may be nullptr (hg_sketch_plan_describe)
 hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
-                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t);
+                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t, hg_plan_shape shape = {});
 // The batch's plan: the ctx's cached one when the geometry matches (t.reused; with_meta = false: the totals only -- the
 // sync-free step reads no per-genome record on the host, 400 000 genomes are 16 MB of them), else built afresh.
-hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta = true);
+// The shape is part of the geometry: a plan cached for another shape does not match.
+hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta = true,
+                      hg_plan_shape shape = {});
 // the cached plan's capacities and hit offsets into t.meta (a reused plan's records, for the synchronous path)
 void hg_plan_tables_from_cache(const hg_sketch_plan &pl, size_t n, hg_batch_tables &t, bool with_meta = true);
 // A freshly built plan (not t.reused) goes to w_gmeta / w_items through the page-locked plan staging (stream-ordered,
 // returns at once) and becomes the ctx's cached plan.
-hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled);
+hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
+                         hg_plan_shape shape = {});
 
 // ASCII genomes -> hg_pack2 blobs on the device (synchronises the stream before and after: it uses the ctx's scratch)
 hg_status hg_pack_batch(hg_ctx *c, const uint8_t *d_seq, const uint64_t *seq_offs, const uint64_t *lens, size_t n,

@@ -26,8 +26,9 @@ hg_status hg_check_sketch_params(hg_ctx *c, const hg_sketch_params *p) {
 }
 
 hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
-                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t) {
+                        const std::vector<uint32_t> *want_caps, hg_batch_tables &t, hg_plan_shape shape) {
   const uint64_t item_starts = hg_kmer_item_starts(ksize);
+  const uint64_t span = shape.span ? shape.span : ksize, per_start = shape.per_start ? shape.per_start : 1;
   // groups of work items (one workgroup each): consecutive items of SMALL genomes are put together while the group stays
   // within hg_kmer_item_tiles tiles; an item that fills a work item on its own (a piece of a large genome) stays alone, so
   // that the launch of large genomes keeps its granularity
@@ -47,17 +48,18 @@ hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uin
     m.seq_off = b.offsets[g];
     m.n_bps = b.lens[g];
     m.mask_off = b.mask_offs ? b.mask_offs[g] : m.seq_off + hg_pack2_code_bytes(m.n_bps);  // (read by the packed kernels only)
-    const uint64_t n_starts = m.n_bps >= ksize ? m.n_bps - ksize + 1 : 0;
-    const uint64_t expect = n_starts / scaled;
-    uint64_t cap = expect * 2 + 1024;    // expected n_starts/scaled; sd ~ sqrt of that
-    if (cap > n_starts) cap = n_starts;  // can never exceed the number of k-mers
+    const uint64_t n_starts = m.n_bps >= span ? m.n_bps - span + 1 : 0;
+    const uint64_t n_kmers = n_starts * per_start;
+    const uint64_t expect = n_kmers / scaled;
+    uint64_t cap = expect * 2 + 1024;    // expected n_kmers/scaled; sd ~ sqrt of that
+    if (cap > n_kmers) cap = n_kmers;    // can never exceed the number of k-mers
     if (want_caps && (*want_caps)[g] > cap) cap = (*want_caps)[g];
     if (cap == 0) cap = 1;
     m.hit_cap = round_cap(cap);
     m.hit_off = slot;
     slot += m.hit_cap;
     max_cap = std::max(max_cap, m.hit_cap);
-    max_expect = std::max(max_expect, std::min(expect, n_starts));
+    max_expect = std::max(max_expect, std::min(expect, n_kmers));
     const uint64_t n_items = (n_starts + item_starts - 1) / item_starts;
     if (t.item_genome.size() + n_items > 0x7FFFFFFFull)
       return hg_fail(c, HG_ERR_UNSUPPORTED, "batch too large for one launch; split it");
@@ -86,13 +88,14 @@ hg_status hg_plan_build(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uin
   return HG_OK;
 }
 
-hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta) {
+hg_status hg_plan_get(hg_ctx *c, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled, hg_batch_tables &t, bool with_meta,
+                      hg_plan_shape shape) {
   // the ctx's cached plan has this geometry (its tables are on the device)
   const hg_sketch_plan *pl = c->plan.get();
-  const bool match = pl && pl->ksize == ksize && pl->scaled == scaled && pl->packed == b.packed && pl->offs.size() == b.n &&
+  const bool match = pl && pl->ksize == ksize && pl->span == shape.span && pl->per_start == shape.per_start && pl->scaled == scaled && pl->packed == b.packed && pl->offs.size() == b.n &&
                      std::memcmp(pl->offs.data(), b.offsets, b.n * 8) == 0 && std::memcmp(pl->lens.data(), b.lens, b.n * 8) == 0 &&
                      (b.mask_offs ? pl->masks.size() == b.n && std::memcmp(pl->masks.data(), b.mask_offs, b.n * 8) == 0 : pl->masks.empty());
-  if (!match) return hg_plan_build(c, b, ksize, scaled, nullptr, t);
+  if (!match) return hg_plan_build(c, b, ksize, scaled, nullptr, t, shape);
   hg_plan_tables_from_cache(*pl, b.n, t, with_meta);
   return HG_OK;
 }
@@ -115,7 +118,8 @@ void hg_plan_tables_from_cache(const hg_sketch_plan &pl, size_t n, hg_batch_tabl
   }
 }
 
-hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled) {
+hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_batch &b, uint32_t ksize, uint64_t scaled,
+                         hg_plan_shape shape) {
   if (t.reused) return HG_OK;
   const size_t n = b.n;
   c->plan.reset();  // (the device tables are about to change)
@@ -160,7 +164,7 @@ hg_status hg_plan_commit(hg_ctx *c, const hg_batch_tables &t, const hg_genome_ba
   if (b.mask_offs) pl->masks.assign(b.mask_offs, b.mask_offs + n);
   pl->caps.resize(n);
   for (size_t g = 0; g < n; ++g) pl->caps[g] = t.meta[g].hit_cap;
-  pl->ksize = ksize, pl->scaled = scaled, pl->packed = b.packed;
+  pl->ksize = ksize, pl->span = shape.span, pl->per_start = shape.per_start, pl->scaled = scaled, pl->packed = b.packed;
   pl->total_slots = t.total_slots, pl->max_cap = t.max_cap, pl->max_expect = t.max_expect, pl->n_items = n_items;
   pl->n_groups = t.n_groups;
   c->plan = std::move(pl);

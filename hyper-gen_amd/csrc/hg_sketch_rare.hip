@@ -92,13 +92,14 @@ hg_status hg_sample_batch_sync(hg_ctx *c, const hg_genome_batch &b, const hg_ske
   if (n > 0x7FFFFFFFull) return hg_fail(c, HG_ERR_UNSUPPORTED, "more than 2^31 genomes in one batch");
   ++c->n_sync_steps;
   std::vector<uint32_t> want;
+  const hg_plan_shape shape = hg_ctx_plan_shape(c);  // (a companion library's hook may span more bytes and yield more k-mers per start)
   for (int attempt = 0; attempt < 3; ++attempt) {
     hg_status s;
     // same geometry as the previous call (typical for a stream of equally shaped batches): the work-item table and the
     // per-genome records are still on the device.  A retry after an overflow builds the plan with larger regions.
-    if (attempt) s = hg_plan_build(c, b, p->ksize, p->scaled, &want, pl);
-    else s = planned ? HG_OK : hg_plan_get(c, b, p->ksize, p->scaled, pl);
-    if (s != HG_OK || (s = hg_plan_commit(c, pl, b, p->ksize, p->scaled)) != HG_OK) return s;
+    if (attempt) ++c->n_plan_regrows, s = hg_plan_build(c, b, p->ksize, p->scaled, &want, pl, shape);
+    else s = planned ? HG_OK : hg_plan_get(c, b, p->ksize, p->scaled, pl, true, shape);
+    if (s != HG_OK || (s = hg_plan_commit(c, pl, b, p->ksize, p->scaled, shape)) != HG_OK) return s;
     // page-locked scratch of this path: the counters, the fetch block (count + first hashes of a one-genome call), the redo list
     const size_t cnt_bytes = (n * sizeof(uint32_t) + 63) & ~(size_t)63;
     const size_t fetch_n = (fetch && n == 1) ? std::min<size_t>({fetch->max_hashes, pl.meta[0].hit_cap, (size_t)1 << 16}) : 0;
