@@ -16,8 +16,9 @@
 //    ADDRESS: one v_cndmask picks the image, the hash words are ds_reads with immediate offsets -- no instruction
 //    touches the bytes;
 //  * t1ha2 is specialised per k; for k = 17..32 the whole k-mer body (word reads, three or four mixup64 stages,
-//    final64, candidate compare on the high dword) is one asm statement on fixed register pairs: 55 / 65 vector
-//    instructions, 24 / 29 of them v_mad_u64_u32 (the first mixup multiplies a bounded operand: HG_KS_BOUNDED_FIRST);
+//    final64, candidate compare on the high dword) is one asm statement on fixed register pairs: 54 / 63 vector
+//    instructions, 24 / 29 of them v_mad_u64_u32 (the first mixup multiplies a bounded operand: HG_KS_BOUNDED_FIRST; the
+//    products with P1 and P3 have no carry op: HG_KS_NOCARRY);
 //  * survivors (1/scaled of the k-mers) are staged in a small LDS list and the workgroup reserves its range of the
 //    genome's hit slice with ONE global atomic at the end of its work item; lossless: no 8-slot cap like
 //    src/cuda_kernel.cu:316, hash value 0 is kept;
@@ -43,6 +44,20 @@ constexpr uint64_t P4 = 0x9C06FAF4D023E3ABull;
 constexpr uint64_t P5 = 0xC060724A8424F345ull;
 constexpr uint64_t P6 = 0xCB5AF53AE3AAAC31ull;
 
+// The schoolbook 64 x 64 product below sums its two cross products and the carry dword of the low one in 64 bits:
+// W = x0 p1 + x1 p0 + hi32(x0 p0) <= (2^32 - 1) (p0 + p1) + p0 - 1.  Where that worst case stays below 2^64 -- in effect
+// p0 + p1 < 2^32 -- the sum has no carry-out for ANY x, and the v_addc that would fold it into the high dword of the
+// result adds zero.  True for P1 (largest W = 0.567 x 2^64) and P3 (0.914), false for P2 (1.447), P4 (1.423) and P5 (1.268).
+constexpr bool mul128_cross_fits(uint64_t P) {
+  const unsigned __int128 m = 0xFFFFFFFFull, p0 = (uint32_t)P, p1 = P >> 32;
+  return ((m * p1 + m * p0 + ((m * p0) >> 32)) >> 64) == 0;
+}
+static_assert(mul128_cross_fits(P1) && mul128_cross_fits(P3), "the mixups with P1 and P3 run without the carry op");
+static_assert(!mul128_cross_fits(P2) && !mul128_cross_fits(P4) && !mul128_cross_fits(P5), "P2, P4 and P5 need the carry op");
+#ifndef HG_KS_NOCARRY
+#define HG_KS_NOCARRY 1  /* no carry op in the 128-bit products with P1 and P3 (0: the text with the carry for every prime, A/B) */
+#endif
+
 __device__ __forceinline__ uint64_t mk64(uint32_t lo, uint32_t hi) {
   return (uint64_t)lo | ((uint64_t)hi << 32);
 }
@@ -64,7 +79,8 @@ __device__ __forceinline__ uint64_t rot64(uint64_t v, unsigned s) {  // rotate r
 // compiler's expansion of a 128-bit multiply spends 5 v_mov + one 64-bit add on zero-extending
 // partial words; here the third product takes the second as its 64-bit addend and hands its carry
 // out in an SGPR pair, and that carry plus the caller's addend are folded into the addend of the
-// last product with three 32-bit ops.
+// last product with three 32-bit ops.  A prime whose cross sum fits 64 bits (mul128_cross_fits: P1, P3) has no such carry:
+// the third product's carry-out is dead, and neither the v_addc nor, with a zero addend, the v_cndmask is there.
 template <uint64_t P, bool ZERO_ADDEND = false, bool UNI_ADDEND = false>
 __device__ __forceinline__ uint64_t mul128_lo_hiadd(uint64_t x, uint64_t addend, uint64_t &hi_plus) {
   constexpr uint32_t p0 = (uint32_t)P, p1 = (uint32_t)(P >> 32);
@@ -73,7 +89,18 @@ __device__ __forceinline__ uint64_t mul128_lo_hiadd(uint64_t x, uint64_t addend,
   const uint64_t T = (uint64_t)x1 * p0 + (A >> 32);  // cannot overflow
   uint64_t W, cm;                                     // W = x0*p1 + T (mod 2^64), cm = carry-out lanes
   asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(W), "=s"(cm) : "v"(x0), "s"(p1), "v"(T));
-  if (ZERO_ADDEND) {  // S = {hi32(W), carry}
+  if constexpr (HG_KS_NOCARRY && mul128_cross_fits(P)) {  // W is the whole sum: cm is zero in every lane and unused
+    if (ZERO_ADDEND) {
+      hi_plus = (uint64_t)x1 * p1 + (W >> 32);
+    } else {  // (the "x 1" product as below: it leaves addend + hi32(W) in an aligned pair)
+      uint64_t t, junk;
+      if (UNI_ADDEND)
+        asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(t), "=s"(junk) : "v"((uint32_t)(W >> 32)), "s"(addend));
+      else
+        asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(t), "=s"(junk) : "v"((uint32_t)(W >> 32)), "v"(addend));
+      hi_plus = (uint64_t)x1 * p1 + t;
+    }
+  } else if (ZERO_ADDEND) {  // S = {hi32(W), carry}
     uint32_t shi;
     asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(shi) : "s"(cm));
     hi_plus = (uint64_t)x1 * p1 + mk64((uint32_t)(W >> 32), shi);
@@ -257,7 +284,8 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 // pair that consumes it, carries go through VCC into a VOP2 v_addc (no SGPR read hazard), and what is left is what the
 // ISA forces: the high dword of a product is an ODD register and a 64-bit addend has to start at an EVEN one -- one
 // v_mov per 128-bit product (into the pair Z = {x, 0}).  56 vector instructions per hash + candidate compare instead of 64
-// (55 with the bounded first mixup, HG_KS_MUL128_BOUNDED below).
+// (55 with the bounded first mixup, HG_KS_MUL128_BOUNDED below; 54 without the carry op of the P1 stage, HG_KS_MUL128_NC).
+// HG_KS_MUL128: lo64(x P) -> {v74, v76}, hi64(x P) + ADDEND -> OUT; 7 instructions, the carry of the cross sum through VCC.
 //   v[56:61] / v[62:67]  hash words of k-mer j / j+1 (filled by HG_KS_READ one k-mer ahead)
 //   Z v[68:69]  H v71 (hash high dword)  X v[72:73]  A v[74:75]  T v[76:77]  U v[78:79]  S1 v[80:81]  S2 v[82:83]  R v[84:85]
 //   Y v[86:87]  C v[88:89]
@@ -269,13 +297,35 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_mad_u64_u32 " OUT ", %[junk], v77, 1, " ADDEND "\n\t"                                     \
   "v_mad_u64_u32 " OUT ", %[junk], " XHI ", " PHI ", " OUT "\n\t"                              \
   "v_addc_co_u32_e32 " OUTHI ", vcc, 0, " OUTHI ", vcc\n\t"
+// The same product for a prime whose cross sum fits 64 bits (mul128_cross_fits): the third product's carry-out is zero
+// for every operand, so it goes to %[junk], VCC is not touched and the v_addc is not there -- 6 instructions, not 7.
+#define HG_KS_MUL128_NC(XLO, XHI, PLO, PHI, ADDEND, OUT, OUTHI)                                \
+  "v_mad_u64_u32 v[74:75], %[junk], " XLO ", " PLO ", 0\n\t"                                   \
+  "v_mov_b32 v68, v75\n\t"                                                                     \
+  "v_mad_u64_u32 v[76:77], %[junk], " XHI ", " PLO ", v[68:69]\n\t"                            \
+  "v_mad_u64_u32 v[76:77], %[junk], " XLO ", " PHI ", v[76:77]\n\t"                            \
+  "v_mad_u64_u32 " OUT ", %[junk], v77, 1, " ADDEND "\n\t"                                     \
+  "v_mad_u64_u32 " OUT ", %[junk], " XHI ", " PHI ", " OUT "\n\t"
+// The stages name their prime through these, so that the text without the carry cannot meet another prime than the
+// two the predicate admits: P1 (the last stage) and P3 (the general first mixup of k <= 24, the second stage of k >= 25).
+#if HG_KS_NOCARRY
+static_assert(mul128_cross_fits(P1), "HG_KS_MUL128_P1 drops the carry op");
+static_assert(mul128_cross_fits(P3), "HG_KS_MUL128_P3 drops the carry op");
+#define HG_KS_MUL128_P1(XLO, XHI, ADDEND, OUT, OUTHI) HG_KS_MUL128_NC(XLO, XHI, "%[p1l]", "%[p1h]", ADDEND, OUT, OUTHI)
+#define HG_KS_MUL128_P3(XLO, XHI, ADDEND, OUT, OUTHI) HG_KS_MUL128_NC(XLO, XHI, "%[p3l]", "%[p3h]", ADDEND, OUT, OUTHI)
+#else
+#define HG_KS_MUL128_P1(XLO, XHI, ADDEND, OUT, OUTHI) HG_KS_MUL128(XLO, XHI, "%[p1l]", "%[p1h]", ADDEND, OUT, OUTHI)
+#define HG_KS_MUL128_P3(XLO, XHI, ADDEND, OUT, OUTHI) HG_KS_MUL128(XLO, XHI, "%[p3l]", "%[p3h]", ADDEND, OUT, OUTHI)
+#endif
 // The FIRST mixup's multiplicand is x = s + w0 with s wave-uniform and small (the seed, k <= 24; the length K, k >= 25)
 // and w0 eight staged bytes, each one of "ACGT" in every k-mer that is KEPT: both phase images are written from the
 // code -> ASCII lookups, whatever the input byte was, so w0.lo, w0.hi <= 0x54545454.  (Lanes whose k-mers are discarded
 // anyway -- lookahead lanes, slots a dead wave did not stage -- may multiply anything: the stage is arithmetic only, no
 // address depends on it.)  With s below FIRST_SEED_END (first_mixup_bounded() below evaluates the worst case):
 //   * no carry leaves the low dword of s + w0: x0 = w0.lo + s is one 32-bit add and x1 is w0.hi as read;
-//   * W = x0 p1 + x1 p0 + hi32(x0 p0) < 2^64: the third product has no carry-out, so the v_addc goes;
+//   * W = x0 p1 + x1 p0 + hi32(x0 p0) < 2^64: the third product has no carry-out, so the v_addc goes.  For P3 (k <= 24)
+//     that needs no bound at all -- mul128_cross_fits(P3) holds for every operand; for P4 (k >= 25), whose cross sum can
+//     reach 1.423 x 2^64, it is the bound on x0 and x1 that does it;
 //   * hi32(W) + s < 2^32 (the stage's addend is s as well): the "x 1" product is one 32-bit add into Z's low half, and
 //     the last product takes Z as its addend, as HG_KS_FINAL's does.
 // One v_lshl_add_u64, one v_mad_u64_u32 and one v_addc_co_u32 become two v_add_u32: 7 instructions instead of 8.
@@ -388,7 +438,7 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
 //   25 <= K <= 32, mixup64<P4>(a, b, w0): x = K + w0; a = seed ^ lo; b = K + hi
 #define HG_KS_FIRST_FULL_3(W0L, W0H, W0)                                                                             \
   "v_lshl_add_u64 v[72:73], " W0 ", 0, %[seed]\n\t"                                                                  \
-  HG_KS_MUL128("v72", "v73", "%[p3l]", "%[p3h]", "%[seed]", "v[78:79]", "v79")
+  HG_KS_MUL128_P3("v72", "v73", "%[seed]", "v[78:79]", "v79")
 #define HG_KS_FIRST_FULL_4(W0L, W0H, W0)                                                                             \
   "v_lshl_add_u64 v[72:73], " W0 ", 0, %[kk]\n\t"                                                                    \
   HG_KS_MUL128("v72", "v73", "%[p4l]", "%[p4h]", "%[kk]", "v[78:79]", "v79")
@@ -410,7 +460,7 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v83, v79, v76\n\t"                                                                                  \
   /* mixup64<P1>(b, a, w2): x = a + w2; b ^= lo; a += hi   (a = S2, b = R -> b = S1, a = U) */                       \
   "v_lshl_add_u64 v[72:73], v[82:83], 0, " W2 "\n\t"                                                                 \
-  HG_KS_MUL128("v72", "v73", "%[p1l]", "%[p1h]", "v[82:83]", "v[78:79]", "v79")                                      \
+  HG_KS_MUL128_P1("v72", "v73", "v[82:83]", "v[78:79]", "v79")                                                       \
   "v_xor_b32_e32 v80, v84, v74\n\t"                                                                                  \
   "v_xor_b32_e32 v81, v85, v76\n\t"                                                                                  \
   HG_KS_FINAL("v[78:79]", "v78", "v79", "v[80:81]", "v80", "v81")
@@ -423,7 +473,7 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v81, %[seedh], v76\n\t"                                                                             \
   /* mixup64<P3>(b, a, w1): x = a + w1; b ^= lo; a += hi   (a = S1, b = U -> b = S2, a = R) */                       \
   "v_lshl_add_u64 v[72:73], v[80:81], 0, " W1 "\n\t"                                                                 \
-  HG_KS_MUL128("v72", "v73", "%[p3l]", "%[p3h]", "v[80:81]", "v[84:85]", "v85")                                      \
+  HG_KS_MUL128_P3("v72", "v73", "v[80:81]", "v[84:85]", "v85")                                                       \
   "v_xor_b32_e32 v82, v78, v74\n\t"                                                                                  \
   "v_xor_b32_e32 v83, v79, v76\n\t"                                                                                  \
   /* mixup64<P2>(a, b, w2): x = b + w2; a ^= lo; b += hi   (a = R, b = S2 -> a = S1, b = U) */                       \
@@ -433,7 +483,7 @@ __device__ __forceinline__ bool dense_sampling(uint64_t threshold) { return thre
   "v_xor_b32_e32 v81, v85, v76\n\t"                                                                                  \
   /* mixup64<P1>(b, a, w3): x = a + w3; b ^= lo; a += hi   (a = S1, b = U -> b = S2, a = R) */                       \
   "v_lshl_add_u64 v[72:73], v[80:81], 0, " W3 "\n\t"                                                                 \
-  HG_KS_MUL128("v72", "v73", "%[p1l]", "%[p1h]", "v[80:81]", "v[84:85]", "v85")                                      \
+  HG_KS_MUL128_P1("v72", "v73", "v[80:81]", "v[84:85]", "v85")                                                       \
   "v_xor_b32_e32 v82, v78, v74\n\t"                                                                                  \
   "v_xor_b32_e32 v83, v79, v76\n\t"                                                                                  \
   HG_KS_FINAL("v[84:85]", "v84", "v85", "v[82:83]", "v82", "v83")

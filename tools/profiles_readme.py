@@ -99,6 +99,8 @@ L += ["", "## the other files", "",
       "| `%s_kmer_traffic.json`, `%s_kmer_ascii_traffic.json`, `%s_dist_traffic.json` | the `roofline.traffic` figures `bench.py` reports | idem |" % (tag, tag, tag),
       "| `%s_kmer_packed_isa.*`, `%s_kmer_isa.*` | static instruction budget of `kmer_sample_shared<21, true, PACKED>` by class, per k-mer | `tools/kmer_isa.py %s [packed]` |" % (tag, tag, tag),
       # (rows of single changes name their own files, like the r06 .. r01 rows below: `tag` is the round of the full profile set)
+      "| `r12_kmer_ab.txt`, `r12_kmer_packed_isa.*`, `r12_kmer_isa.*` | no carry op in the 128-bit products with P1 and P3 (`mul128_cross_fits`): the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32, and k = 21 with a seed of 2^28, `SQ_INSTS_VALU` at k = 21 and 32, bench line), the register table, and the static budgets | `tools/kmer_time.py [--seed]`, `tools/kmer_isa.py r12 [packed]` |",
+      *(["| `r12_kernel_stats.csv`, `r12_rocprofv3_kernel_stats_full.csv`, `r12_pmc.json`, `r12_derived.md`, `r12_kmer_traffic.json`, `r12_kmer_ascii_traffic.json` | the bench command's kernel stats and counters on the sources of that change (the k-mer kernel's `roofline.valu_issue` and `roofline.traffic` in `bench.py`; no dist-only run: the dist figures stay r06's) | `tools/profile_gpu.sh r12`, `tools/derive_prof.py r12` |"] if os.path.exists(os.path.join(P, "r12_pmc.json")) else []),
       "| `r11_kmer_ab.txt`, `r11_kmer_packed_isa.*`, `r11_kmer_isa.*` | first t1ha2 mixup of `kmer_sample_shared` (k = 17..32) on bounded operands: the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32, and k = 21 with a seed of 2^28 that takes the general text, `SQ_INSTS_VALU`, bench line), the register table, and the static budgets | `tools/kmer_time.py [--seed]`, `tools/kmer_isa.py r11 [packed]` |",
       *(["| `r11_kernel_stats.csv`, `r11_rocprofv3_kernel_stats_full.csv`, `r11_pmc.json`, `r11_derived.md`, `r11_kmer_traffic.json`, `r11_kmer_ascii_traffic.json` | the bench command's kernel stats and counters on the sources of that change (the k-mer kernel's `roofline.valu_issue` and `roofline.traffic` in `bench.py`; no dist-only run: the dist figures stay r06's) | `tools/profile_gpu.sh r11`, `tools/derive_prof.py r11` |"] if os.path.exists(os.path.join(P, "r11_pmc.json")) else []),
       "| `r10_kmer_ab.txt`, `r10_kmer_packed_isa.*`, `r10_kmer_isa.*` | interior tiles of `kmer_sample_shared` staged with scalar addressing: the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32 and forward-only k = 16, `SQ_INSTS_VALU`, bench line), the register table, and the static budgets with the interior staging copy as the tile level | `tools/kmer_time.py`, `tools/kmer_isa.py r10 [packed]` |",
