@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- HyperGen sketch + ANI hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]      the headline alone
+    python bench.py --gpus N --steps K --warmup W --full                    ... and every other leg
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: it generates and packs the genomes, settles and warms up,
+times the K steps, writes the step's outputs if asked to and prints the line (the headline, its kernel times and the
+roofline figures that follow from them).  --full adds every other leg after the headline's timed steps -- the
+ASCII-resident form, the realistic inputs, the 10k-genome job, the host-fed and per-call legs, dist, the Hamming search,
+the CLI end to end, the CPU baselines and the parity gates against the CPU oracle (20 s on one GPU, where the plain
+run spends 2.5 s beside its steps); the options that size or skip one of those legs mean something only beside it.
 
 One "step" = one pass of the sketch hot path (k-mer hash + FracMinHash sample -> set ->
 HV encode -> norm; what src/sketch.rs:35-48 does per file) over one batch of synthetic genomes
 that are already resident in HBM.  Workload at every N: BASELINE.json configs[1] per GPU
 (1 000 synthetic 5 Mbp genomes, k=21 scaled=1500 D=4096) -- genomes shard embarrassingly, no
 data-path collective, weak scaling.  The secondary metric (M ANI-pairs/s, configs[3]:
-10 000 x 10 000 HVs, ani_th=85) is reported in the "dist" object of the same line; its only
+10 000 x 10 000 HVs, ani_th=85) is reported in the "dist" object of a --full run's line; its only
 exchange step is the RCCL all-gather of the reference HV matrix.
 
 Prints ONE JSON line on rank 0.
@@ -40,6 +48,9 @@ def parse():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--genomes", type=int, default=1000, help="genomes per GPU and step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg too (ascii_resident, realistic, sketch_10k, host_fed, per_call, dist, "
+                         "hamming, cli, the CPU baselines and the parity gates); without it the options of those legs are not used")
     ap.add_argument("--dist-n", type=int, default=10000, help="R = Q of the ANI matrix (0 = skip)")
     ap.add_argument("--hamming-refs", type=int, default=50000, help="refs of the bit-packed D=16384 search (0 = skip)")
     ap.add_argument("--hamming-queries", type=int, default=10000, help="queries of the bit-packed search")
@@ -384,6 +395,22 @@ def main():
         if rank == 0:
             print("[bench] " + msg, file=sys.stderr, flush=True)
 
+    def finish():
+        """the end of every run, plain or --full: the process group goes, rank 0 prints the line, exit code 4 if an auxiliary leg failed"""
+        if coll:
+            out["collectives"] = {"backend": torch.distributed.get_backend(), "world": world,
+                                  "steps": ("chunked all-gather of the prepared reference operands + control records (dist), query broadcast + hit "
+                                            "gather (hamming), " if a.full else "") + "barrier / max-reduce around every timed region"}
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        if aux_failures:
+            out["aux_failures"] = aux_failures
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        ctx.close()
+        if aux_failures:
+            sys.exit(4)
+
     # No cyclic-GC passes inside the timed loops: with torch loaded a full collection takes ~10 ms, more than a step
     # (one run of round 3 showed exactly such a step: 20 steps at 8.73 ms of kernels averaged 9.34 ms).
     import gc
@@ -411,7 +438,7 @@ def main():
     # The headline runs on 2-bit PACKED bases (north_star: "coalesced HBM reads of packed bases"): the synthetic ASCII
     # genomes are packed once, on the device and outside every timed region (hg_pack2_batch_dev = the host's hg_pack2
     # byte for byte), and the step is hg_sketch_batch_dev_packed on the blobs.  The ASCII-resident form of the same step
-    # is timed right after it (`ascii_resident`) and must give identical sketches.
+    # is timed right after it in a --full run (`ascii_resident`) and must give identical sketches.
     blob_sz = hg.lib().hg_pack2_size(L_GENOME + 1)
     boffs = np.arange(N, dtype=np.uint64) * blob_sz
     blobs = torch.empty(N * blob_sz + 64, dtype=torch.uint8, device=dev)
@@ -460,26 +487,6 @@ def main():
     value = N * world * a.steps / dt
     log("sketch: %.1f genomes/s, kmer kernel %.3f ms/launch (%d launches), nhash mean %.1f" % (
         value, kmer_avg_ms, kmer_launches, nh.float().mean().item()))
-    # the same step on ASCII-resident genomes (1 byte per base in HBM), identical sketches required
-    hv_a, n2_a, nh_a = torch.empty_like(hv), torch.empty_like(n2), torch.empty_like(nh)
-    settle(step_ascii, 5)
-    ctx.enable_timing(True)
-    ctx.timings()
-    steps_a = max(2, min(a.steps, 10))
-    barrier_sync(world)
-    t0 = time.perf_counter()
-    for _ in range(steps_a):
-        step_ascii()
-    barrier_sync(world)
-    dt_a = max_over_ranks(time.perf_counter() - t0, world, dev)
-    tm_a = ctx.timings()
-    ctx.enable_timing(False)
-    ascii_kernel = ctx.last_kernel("kmer")
-    if not (torch.equal(hv_a, hv) and torch.equal(n2_a, n2) and torch.equal(nh_a, nh)):
-        raise SystemExit("PARITY GATE FAILED: sketches of the packed and of the ASCII-resident genomes differ")
-    ascii_ms = tm_a["kmer"][0] / max(tm_a["kmer"][1], 1)
-    log("sketch, ASCII-resident: %.1f genomes/s, kmer kernel %.3f ms/launch" % (N * world * steps_a / dt_a, ascii_ms))
-    del hv_a, n2_a, nh_a
     isa_path = newest_profile("_kmer_packed_isa.json")
     try:
         isa_valu = json.load(open(isa_path))["per_kmer"]["valu"]
@@ -519,14 +526,39 @@ def main():
                          "The step queues k-mer -> sort -> encode without a host round trip (hg_sketch_step.hip); its check word is "
                          "read while the NEXT step is already queued",
         "sketch_steps": dict(zip(("sync_free", "synchronous", "rerun"), ctx.sketch_step_counts())),
-        "ascii_resident": {"value": N * world * steps_a / dt_a, "unit": "genomes/sec", "steps": steps_a,
-                           "ms_per_step": dt_a / steps_a * 1e3, "kernel": ascii_kernel, "launch_ms": ascii_ms,
-                           "frac_of_hbm_peak": bytes_per_launch / (ascii_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                           "config": {"workload": "the same %d genomes resident as ASCII (1 B per base, %.1f GB), "
-                                                  "hg_sketch_batch_dev; sketches identical to the headline's" % (N, N * stride / 1e9)}},
     }
     if dumped:
         out["dump_outputs"] = dumped
+    if not a.full:  # a plain run ends here: every leg below is one that the headline does not need
+        finish()
+        return
+
+    # the same step on ASCII-resident genomes (1 byte per base in HBM), identical sketches required
+    hv_a, n2_a, nh_a = torch.empty_like(hv), torch.empty_like(n2), torch.empty_like(nh)
+    settle(step_ascii, 5)
+    ctx.enable_timing(True)
+    ctx.timings()
+    steps_a = max(2, min(a.steps, 10))
+    barrier_sync(world)
+    t0 = time.perf_counter()
+    for _ in range(steps_a):
+        step_ascii()
+    barrier_sync(world)
+    dt_a = max_over_ranks(time.perf_counter() - t0, world, dev)
+    tm_a = ctx.timings()
+    ctx.enable_timing(False)
+    ascii_kernel = ctx.last_kernel("kmer")
+    if not (torch.equal(hv_a, hv) and torch.equal(n2_a, n2) and torch.equal(nh_a, nh)):
+        raise SystemExit("PARITY GATE FAILED: sketches of the packed and of the ASCII-resident genomes differ")
+    ascii_ms = tm_a["kmer"][0] / max(tm_a["kmer"][1], 1)
+    log("sketch, ASCII-resident: %.1f genomes/s, kmer kernel %.3f ms/launch" % (N * world * steps_a / dt_a, ascii_ms))
+    del hv_a, n2_a, nh_a
+    out["ascii_resident"] = {"value": N * world * steps_a / dt_a, "unit": "genomes/sec", "steps": steps_a,
+                             "ms_per_step": dt_a / steps_a * 1e3, "kernel": ascii_kernel, "launch_ms": ascii_ms,
+                             "frac_of_hbm_peak": bytes_per_launch / (ascii_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                             "config": {"workload": "the same %d genomes resident as ASCII (1 B per base, %.1f GB), "
+                                                    "hg_sketch_batch_dev; sketches identical to the headline's" % (N, N * stride / 1e9)}}
+    out["sketch_steps"] = dict(zip(("sync_free", "synchronous", "rerun"), ctx.sketch_step_counts()))  # (with this leg's steps)
 
     # ---------------- the inputs real users have (never `value`) ----------------------------------------------------
     # Every timed leg above runs on clean, single-contig, iid-uniform genomes.  (a) `draft_assemblies`: the SAME N genomes
@@ -1317,19 +1349,7 @@ def main():
         out["parity_gate"] = dict(gate, status="passed")
     elif rank == 0:
         out["parity_gate"] = {"status": "skipped (no CPU leg: N > 1 or --no-cpu-baseline); hamming / 10k / host-fed self-checks ran"}
-    if coll:
-        out["collectives"] = {"backend": torch.distributed.get_backend(), "world": world,
-                              "steps": "chunked all-gather of the prepared reference operands + control records (dist), query broadcast + hit "
-                                       "gather (hamming), barrier / max-reduce around every timed region"}
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
-    if aux_failures:
-        out["aux_failures"] = aux_failures
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    ctx.close()
-    if aux_failures:
-        sys.exit(4)
+    finish()
 
 
 if __name__ == "__main__":

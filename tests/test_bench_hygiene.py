@@ -36,6 +36,17 @@ def test_profiled_requires_matching_stamp_and_kernel(tmp_path, monkeypatch):
     assert bench.profiled("_nothing.json", "x")[0] is None
 
 
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """a plain `bench.py --gpus 1 --steps K --warmup W` is the headline alone; the other legs are asked for with --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup, a.dump_outputs) == (1, 3, 2, None)
+    monkeypatch.setattr(sys, "argv", sys.argv + ["--full"])
+    assert bench.parse().full is True
+
+
 def test_committed_profiles_carry_stamps():
     import glob
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r03_*.json")))

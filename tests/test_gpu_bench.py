@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--genomes", "16", "--dist-n", "1024", "--hamming-refs", "4096", "--cpu-seconds", "0.5", "--small-genomes", "3000",
                         "--cli-sketch-files", "48"],
                        capture_output=True, text=True, timeout=600)
@@ -47,7 +47,33 @@ def test_bench_json_contract():
     assert j["parity_gate"]["status"] == "passed" and j["parity_gate"]["ani_two_sets_hits_checked"] > 0
 
 
-TWO_RANK_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--genomes", "24", "--genomes-10k", "50", "--dist-n", "2048",
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the line.  The headline's keys say what they say in a
+    --full run; none of the legs behind --full runs, whatever the options that size them say."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--genomes", "16", "--dist-n", "1024", "--hamming-refs", "4096", "--small-genomes", "3000",
+                        "--cli-sketch-files", "48", "--dump-outputs", str(tmp_path / "dump")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["metric"] == "genomes/sec sketch (k=21,s=1500,D=4096)" and j["unit"] == "genomes/sec" and j["dtype"] == "u64"
+    assert j["higher_is_better"] is True and j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 1
+    assert j["ms_per_step"] > 0 and abs(j["value"] * j["ms_per_step"] / 16e3 - 1) < 1e-9  # 16 genomes per step
+    rf = j["roofline"]  # (priced from the timed steps' own kernel times: no run of its own)
+    assert rf["bound"] == "hbm" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9 and j["kernel_ms_per_step"]["kmer"] > 0
+    for k in ("ascii_resident", "realistic", "sketch_10k", "host_fed", "per_call", "dist", "hamming", "cli", "cpu_baseline",
+              "speedup_vs_cpu_baseline", "parity_gate", "collectives"):
+        assert k not in j, k
+    assert [l for l in r.stderr.splitlines() if l.startswith("[bench]")] == [l for l in r.stderr.splitlines() if l.startswith("[bench] sketch:")]
+    hv, n2, nh = (np.load(tmp_path / "dump" / f) for f in ("hv.npy", "hv_norm_2.npy", "nhash.npy"))
+    assert j["dump_outputs"]["genomes"] == 16 and hv.shape == (16, 4096) and hv.dtype == np.float32
+    assert np.array_equal((hv.astype(np.float64) ** 2).sum(1), n2) and (nh > 3000).all()  # 5 Mbp / 1500: ~3 333 hashes
+
+
+TWO_RANK_ARGS =["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--genomes", "24", "--genomes-10k", "50", "--dist-n", "2048",
                  "--hamming-refs", "6001", "--hamming-queries", "300", "--backend", "gloo", "--share-gpu"]
 
 
@@ -100,7 +126,7 @@ def test_bench_rccl_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--genomes", "16", "--genomes-10k", "40", "--hostfed-genomes", "0", "--dist-n", "2048",
                         "--hamming-refs", "4096", "--hamming-queries", "300", "--backend", "nccl", "--collectives",
                         "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=900, env=env)

@@ -216,6 +216,7 @@ def prep_ops(hg, c, hv):
     ops = torch.full((rows, rb), 0x5A, dtype=torch.uint8, device="cuda")
     meta = torch.full((rows, mb), 0x5A, dtype=torch.uint8, device="cuda")
     flag = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()  # (the fills run on torch's stream, the library on the context's own: without this a fill may land last)
     c.dist_prep_ops_dev(t.data_ptr(), rows, hv_d, ops.data_ptr(), meta.data_ptr(), flag.data_ptr())
     c.sync()
     return ops, meta, flag

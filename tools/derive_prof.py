@@ -84,7 +84,7 @@ def row(name, d):
 
 
 lines = ["# Derived metrics from `%s_pmc.json` / `%s_dist_pmc.json` (per launch)" % (tag, tag), "",
-         "Source: separate `rocprofv3 --pmc` passes of `bench.py --steps 3 --warmup 1` (`tools/profile_gpu.sh`) and of",
+         "Source: separate `rocprofv3 --pmc` passes of `bench.py --full --steps 3 --warmup 1` (`tools/profile_gpu.sh`) and of",
          "`tools/dist_only.py` (`tools/profile_dist.sh`).  `GRBM_GUI_ACTIVE` is summed over the 8 XCDs (/8 = kernel cycles);",
          "SIMDs = 1024; the wave-time split is SQ_ACTIVE_INST_ANY / SQ_WAIT_INST_ANY / SQ_WAIT_ANY over SQ_WAVE_CYCLES; HBM bytes = FETCH_SIZE*1024*2 (gfx950 wide-read correction)",
          "+ WRITE_SIZE*1024.  Generated by `tools/derive_prof.py`.", "",
@@ -127,7 +127,7 @@ for other in kms:
 json.dump({"kernel": km, "_stamp": pmc["_stamp"], "hbm_bytes_per_launch": pmc[km]["hbm_bytes_per_launch"],
            "hbm_read_bytes_per_launch_corrected": pmc[km]["hbm_read_bytes_per_launch_corrected"],
            "hbm_write_bytes_per_launch": pmc[km]["hbm_write_bytes_per_launch"],
-           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --steps 3 --warmup 1`; "
+           "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --full --steps 3 --warmup 1`; "
                      "FETCH_SIZE (KiB) x1024 x2 (gfx950 wide-read correction) + WRITE_SIZE (KiB) x1024, averaged per launch"},
           open(os.path.join(out, tag + "_kmer_traffic.json"), "w"), indent=1)
 dm = sorted([k for k in pmcd if k.startswith("dist_mfma")], key=lambda k: -pmcd[k].get("GRBM_GUI_ACTIVE", 0))

@@ -31,7 +31,7 @@ L = ["# profiles/", "",
      "was copied in at; `bench.py` quotes a file's counters only for the same sources and the kernel the library reports it launched.",
      "**This file is generated** (`tools/profiles_readme.py %s`) from the summaries beside it." % tag, "",
      "## `%s_kernel_stats.csv` -- `rocprofv3 --kernel-trace --stats` of the bench command" % tag, "",
-     "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --genomes-10k 0",
+     "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --genomes-10k 0",
      "--hostfed-genomes 0` (`tools/profile_gpu.sh %s`; only the headline shapes are launched, so that per-kernel averages are per shape;" % tag,
      "profiled passes run at a lower clock than un-profiled ones).", ""]
 L += table(tag + "_kernel_stats.csv")
@@ -49,7 +49,7 @@ bl = os.path.join(P, tag + "_bench_line.json")
 if os.path.exists(bl):
     j = json.load(open(bl))
     rf = j["roofline"]
-    L += ["", "## `%s_bench_line.json` -- `python bench.py --steps 20 --warmup 3` on the committed sources" % tag, "",
+    L += ["", "## `%s_bench_line.json` -- `python bench.py --full --steps 20 --warmup 3` on the committed sources" % tag, "",
           "| | |", "|---|---|",
           "| sketch, packed bases resident | %.0f genomes/s, kernel `%s` %.3f ms / launch = %.4f of the HBM peak (algorithmic L + 2 D bytes) |" % (
               j["value"], rf["kernel"], rf["launch_ms"], rf["frac"]),
