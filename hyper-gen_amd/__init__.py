@@ -486,6 +486,101 @@ def tx_item_starts(ksize):
     return int(lib_tx().hg_tx_item_starts(ksize))
 
 
+# ---- libhypergen_rec.so (include/hypergen_rec.h): one multi-FASTA text split into its records on the device ----
+REC_LIB_PATH = os.path.join(_HERE, "libhypergen_rec.so")
+REC_EXPORTS = [
+    "hg_rec_count_dev", "hg_rec_split_dev", "hg_rec_split", "hg_rec_split_host", "hg_rec_read_text", "hg_rec_sketch_text_dev",
+    "hg_rec_block_bytes", "hg_rec_kernel_names", "hg_rec_launch_counts",
+]
+REC_DTYPE = np.dtype([("hdr_off", np.uint64), ("hdr_len", np.uint32), ("id_len", np.uint32), ("seq_off", np.uint64),
+                      ("seq_len", np.uint64)])  # hg_rec_entry
+REC_ROWS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p)
+_lib_rec = None
+
+
+def lib_rec():
+    """The third companion library, loaded behind lib() like lib_aa()."""
+    global _lib_rec
+    if _lib_rec is not None:
+        return _lib_rec
+    lib()
+    if not os.path.exists(REC_LIB_PATH):
+        raise ImportError("libhypergen_rec.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    L = C.CDLL(REC_LIB_PATH)
+    vp, sz = C.c_void_p, C.c_size_t
+    sig = {
+        "hg_rec_count_dev": (C.c_int, [vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_split_dev": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_split": (C.c_int, [vp, vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_split_host": (C.c_int, [vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_read_text": (C.c_int, [C.c_char_p, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_sketch_text_dev": (C.c_int, [vp, vp, sz, C.POINTER(SketchParams), C.c_uint64, REC_ROWS_FN, vp, C.POINTER(sz), C.POINTER(sz)]),
+        "hg_rec_block_bytes": (C.c_uint32, []),
+        "hg_rec_kernel_names": (C.c_char_p, []),
+        "hg_rec_launch_counts": (C.c_uint32, [vp, C.c_uint32]),
+    }
+    assert sorted(sig) == sorted(REC_EXPORTS)
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = res, args
+    _lib_rec = L
+    return L
+
+
+def rec_block_bytes():
+    """hg_rec_block_bytes: bytes of text per workgroup of the per-block kernels"""
+    return int(lib_rec().hg_rec_block_bytes())
+
+
+def rec_kernel_names():
+    """hg_rec_kernel_names: the library's kernels as rocprofv3 spells them, in launch order"""
+    return lib_rec().hg_rec_kernel_names().decode().split("\n")
+
+
+def rec_launch_counts():
+    """hg_rec_launch_counts: {kernel name: launches of this process so far}"""
+    names = rec_kernel_names()
+    counts = np.zeros(len(names), np.uint64)
+    assert lib_rec().hg_rec_launch_counts(_ptr(counts), counts.size) == len(names)
+    return dict(zip(names, (int(x) for x in counts)))
+
+
+def _rec_host_call(fn, text, seq_cap, rec_cap, fill):
+    """one of the host-memory splitters on `text`: (status, n_recs, seq_bytes, record table of rec_cap entries, buffer of seq_cap
+    bytes); both outputs are filled with `fill` before the call"""
+    a = np.frombuffer(bytes(text), np.uint8)
+    seq = np.full(seq_cap, fill, np.uint8)
+    recs = np.frombuffer(np.full(rec_cap * REC_DTYPE.itemsize, fill, np.uint8).tobytes(), REC_DTYPE).copy()
+    n_recs, seq_bytes = C.c_size_t(0), C.c_size_t(0)
+    st = fn(_ptr(a) if a.size else None, a.size, _ptr(seq) if seq_cap else None, seq_cap, _ptr(recs) if rec_cap else None, rec_cap,
+            C.byref(n_recs), C.byref(seq_bytes))
+    return st, int(n_recs.value), int(seq_bytes.value), recs, seq
+
+
+def rec_split_host(text, seq_cap=None, rec_cap=None, fill=0xEE):
+    """hg_rec_split_host (one host thread, needs no GPU).  Without capacities: a first call sizes the outputs, rec_cap = n_recs and
+    seq_cap = seq_bytes + 32.  Returns (status, n_recs, seq_bytes, recs, seq)."""
+    fn = lib_rec().hg_rec_split_host
+    if seq_cap is None or rec_cap is None:
+        st, n_recs, seq_bytes, _, _ = _rec_host_call(fn, text, 0, 0, fill)
+        if st != ERR_CAPACITY:
+            return st, n_recs, seq_bytes, np.zeros(0, REC_DTYPE), np.zeros(0, np.uint8)
+        seq_cap, rec_cap = seq_bytes + 32, n_recs
+    return _rec_host_call(fn, text, seq_cap, rec_cap, fill)
+
+
+def rec_read_text(path):
+    """hg_rec_read_text: the bytes of a file, gzip inflated, read into page-locked memory (needs the HIP runtime)"""
+    buf, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    st = lib_rec().hg_rec_read_text(os.fsencode(path), C.byref(buf), C.byref(cap), C.byref(n))
+    try:
+        if st != OK:
+            raise HgError(st, "hg_rec_read_text: %s" % path)
+        return C.string_at(buf, n.value)
+    finally:
+        lib().hg_pinned_free(buf)
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -719,6 +814,58 @@ class Context:
         ln = np.ascontiguousarray(lens, np.uint64)
         self._ck(lib_tx().hg_tx_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
                                                  _ptr(d_norm2), _ptr(d_nhash)))
+
+    # ---- one multi-FASTA text into records (libhypergen_rec.so) --------------------------------
+    def rec_count_dev(self, d_text, n):
+        """hg_rec_count_dev on a device pointer (int): (status, n_recs, seq_bytes); raises unless OK or HG_ERR_IO"""
+        n_recs, seq_bytes = C.c_size_t(0), C.c_size_t(0)
+        st = self._ck(lib_rec().hg_rec_count_dev(self._h, _ptr(d_text), n, C.byref(n_recs), C.byref(seq_bytes)), allow=(ERR_IO,))
+        return st, int(n_recs.value), int(seq_bytes.value)
+
+    def rec_split_dev(self, d_text, n, d_seq, seq_cap, d_recs, rec_cap):
+        """hg_rec_split_dev on device pointers (ints): (status, n_recs, seq_bytes); raises unless OK, HG_ERR_IO or HG_ERR_CAPACITY"""
+        n_recs, seq_bytes = C.c_size_t(0), C.c_size_t(0)
+        st = self._ck(lib_rec().hg_rec_split_dev(self._h, _ptr(d_text), n, _ptr(d_seq), seq_cap, _ptr(d_recs), rec_cap,
+                                                 C.byref(n_recs), C.byref(seq_bytes)), allow=(ERR_IO, ERR_CAPACITY))
+        return st, int(n_recs.value), int(seq_bytes.value)
+
+    def rec_split(self, text, seq_cap=None, rec_cap=None, fill=0xEE):
+        """hg_rec_split, host memory in and out, with the arguments and results of rec_split_host()"""
+        def fn(*a):
+            return self._ck(lib_rec().hg_rec_split(self._h, *a), allow=(ERR_IO, ERR_CAPACITY))
+        if seq_cap is None or rec_cap is None:
+            st, n_recs, seq_bytes, _, _ = _rec_host_call(fn, text, 0, 0, fill)
+            if st != ERR_CAPACITY:
+                return st, n_recs, seq_bytes, np.zeros(0, REC_DTYPE), np.zeros(0, np.uint8)
+            seq_cap, rec_cap = seq_bytes + 32, n_recs
+        return _rec_host_call(fn, text, seq_cap, rec_cap, fill)
+
+    def rec_sketch_text_dev(self, d_text, n, params, min_length=0):
+        """hg_rec_sketch_text_dev on a device pointer (int): (record table, indices of the sketched records, hv, norm2, nhash),
+        the rows in the order of the indices"""
+        got = {"recs": np.zeros(0, REC_DTYPE), "which": [], "hv": [], "n2": [], "nh": [], "calls": 0}
+
+        def rows(user, recs, n_recs, which, m, hv, n2, nh):
+            got["calls"] += 1
+            if m == 0:
+                got["recs"] = np.frombuffer(C.string_at(recs, n_recs * REC_DTYPE.itemsize), REC_DTYPE).copy()
+                return 0
+            got["which"].append(np.frombuffer(C.string_at(which, m * 4), np.uint32).copy())
+            got["hv"].append(np.frombuffer(C.string_at(hv, m * params.hv_d * 2), np.int16).reshape(m, params.hv_d).copy())
+            got["n2"].append(np.frombuffer(C.string_at(n2, m * 4), np.int32).copy())
+            got["nh"].append(np.frombuffer(C.string_at(nh, m * 4), np.uint32).copy())
+            return 0
+
+        n_recs, n_kept = C.c_size_t(0), C.c_size_t(0)
+        self._ck(lib_rec().hg_rec_sketch_text_dev(self._h, _ptr(d_text), n, C.byref(params), C.c_uint64(min_length), REC_ROWS_FN(rows), None,
+                                                  C.byref(n_recs), C.byref(n_kept)))
+        assert got["recs"].size == n_recs.value
+        which = np.concatenate(got["which"]) if got["which"] else np.zeros(0, np.uint32)
+        assert which.size == n_kept.value
+        hv = np.concatenate(got["hv"]) if got["hv"] else np.zeros((0, params.hv_d), np.int16)
+        n2 = np.concatenate(got["n2"]) if got["n2"] else np.zeros(0, np.int32)
+        nh = np.concatenate(got["nh"]) if got["nh"] else np.zeros(0, np.uint32)
+        return got["recs"], which, hv, n2, nh
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):
         r = np.ascontiguousarray(ref_hv, np.int16)

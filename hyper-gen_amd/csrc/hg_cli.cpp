@@ -33,6 +33,7 @@
 
 #include "../../include/hypergen.h"
 #include "../../include/hypergen_aa.h"
+#include "../../include/hypergen_rec.h"
 #include "../../include/hypergen_tx.h"
 
 namespace {
@@ -87,6 +88,9 @@ struct Cli {
   bool protein = false;      // --alphabet dna|protein (sketch): protein = amino-acid k-mers of the *.faa files of -p (hypergen_aa.h)
   bool alphabet_given = false;  // (taken by parse itself: the option table's size is pinned by tests/test_nj_surface.py)
   bool translate = false;    // --translate (sketch): amino-acid k-mers of the six reading frames of the nucleotide files (hypergen_tx.h); parse's own too
+  bool individual = false;   // --individual (sketch): one sketch per FASTA record of every file, the files split on the device (hypergen_rec.h); parse's own too
+  unsigned long long min_length = 0;  // --min_length N (sketch --individual): leave out records with fewer than N sequence bytes
+  bool min_length_given = false;
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
@@ -352,7 +356,17 @@ void print_sketch_help() {
               "         a translated one says whether those proteins are encoded in that assembly.  The files go in batches\n"
               "         through the first visible GPU; the records carry -k in residues and canonical = false, and dist, search\n"
               "         and cluster print the AAI.  It does not go with --alphabet protein (protein input is not translated),\n"
-              "         with --min_count above 1, with --shards or with -k above 32.\n");
+              "         with --min_count above 1, with --shards or with -k above 32.\n"
+              "sketch --individual [--min_length N]: one sketch per FASTA record instead of one per file, for the collections that\n"
+              "         come as one multi-FASTA -- plasmid and viral databases, the contigs of an assembly: Mash -i, sourmash\n"
+              "         --singleton, skani -i.  It takes no value.  Every file of -p (plain or gzip, below 4 GiB inflated) goes to\n"
+              "         the first visible GPU as it is and is split into its records there; the sketch parameters are those of\n"
+              "         sketch without the option (-k up to 255, -s, -S, -C, --min_count, --pack_layout, -D).  A record starts at a\n"
+              "         line that begins with '>'; its name in the sketch file is its identifier, the header up to the first\n"
+              "         blank, without the file's path; files go in the order sketch reads them, records in file order.  Names\n"
+              "         that repeat are kept, a record without an identifier and sequence in front of the first header are\n"
+              "         errors.  --min_length N [0] leaves out the records with fewer than N sequence bytes; it needs --individual.\n"
+              "         It does not go with --alphabet protein, with --translate or with --shards.\n");
 }
 
 Cli parse(int argc, char **argv) {
@@ -400,6 +414,20 @@ Cli parse(int argc, char **argv) {
       c.translate = true;
       continue;
     }
+    if (a.flag == "--individual") {  // likewise
+      c.individual = true;
+      continue;
+    }
+    if (a.flag == "--min_length" || a.flag.rfind("--min_length=", 0) == 0) {  // belongs to --individual, read like a row of the table
+      a.name = "min_length";
+      if (a.flag.size() > 12) a.val = a.flag.substr(13);
+      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
+      else a.val = argv[++i];
+      a.flag = "--min_length";
+      c.min_length = a.uint(~0ull);
+      c.min_length_given = true;
+      continue;
+    }
     const Option *o = nullptr;
     bool have_val = false;
     if (a.flag.rfind("--", 0) == 0) {
@@ -436,6 +464,10 @@ Cli parse(int argc, char **argv) {
     die("--alphabet is not supported by " + c.mode + ": it names the alphabet of the sequences sketch reads");
   if (c.translate && c.mode_bit != SKETCH)
     die("--translate is not supported by " + c.mode + ": it translates the nucleotide sequences sketch reads");
+  if (c.individual && c.mode_bit != SKETCH)
+    die("--individual is not supported by " + c.mode + ": it splits the FASTA files sketch reads into their records");
+  if (c.min_length_given && c.mode_bit != SKETCH)
+    die("--min_length is not supported by " + c.mode + ": it belongs to sketch --individual");
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
@@ -471,6 +503,12 @@ Cli parse(int argc, char **argv) {
     if (!given(c, "ksize")) c.ksize = 9;  // as for --alphabet protein
     if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': --translate takes k-mers of 1 to 32 residues");
   }
+  if (c.individual) {
+    if (c.protein) die("--individual is not supported with --alphabet protein: protein input is sketched one file at a time");
+    if (c.translate) die("--individual is not supported with --translate: translated input is sketched one file at a time");
+    if (c.shards) die("--shards is not supported with --individual: the records are sketched on the first visible GPU");
+  }
+  if (c.min_length_given && !c.individual) die("--min_length needs --individual: without it sketch makes one sketch per file, whatever its length");
   if (c.protein) {
     if (c.min_count > 1) die("--min_count is not supported with --alphabet protein: amino-acid k-mers are sketched without the count filter");
     if (c.shards) die("--shards is not supported with --alphabet protein: protein input is sketched on the first visible GPU");
@@ -515,12 +553,14 @@ std::vector<std::string> fasta_files(const std::string &dir, std::initializer_li
 }
 
 int run_sketch_batches(const Cli &c, const std::vector<std::string> &files);
+int run_sketch_individual(const Cli &c, const std::vector<std::string> &files);
 
 int run_sketch(const Cli &c) {
   if (c.path == "1" && c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.out.empty()) die("the following required arguments were not provided: --out");
   if (c.protein) return run_sketch_batches(c, fasta_files(c.path, {"*.faa"}));
   if (c.translate) return run_sketch_batches(c, fasta_files(c.path));
+  if (c.individual) return run_sketch_individual(c, fasta_files(c.path));
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -792,6 +832,102 @@ class DevBuf {
   void upload(const T *host, size_t n) { ck(ctx, hg_copy_h2d(ctx, p, host, n * sizeof(T)), "upload"); }
   void download(T *host, size_t n) const { ck(ctx, hg_copy_d2h(ctx, host, p, n * sizeof(T)), "download"); }
 };
+
+// sketch --individual: every file goes to the first visible GPU as text (hg_rec_read_text: gzip inflated, page-locked),
+// hg_rec_sketch_text_dev splits it into its records there and sketches them in sub-batches, and the rows come back through
+// take_rows, which packs them.  The parameters are run_sketch's; a record's file_str is its identifier.
+struct IndividualRows {
+  const Cli *c;
+  const std::string *file;
+  const uint8_t *text;
+  unsigned long long min_length;
+  std::deque<std::string> names;                 // (a deque: the records point into the strings)
+  std::deque<std::vector<int16_t>> payload;
+  std::vector<hg_file_sketch> recs;
+};
+int take_rows(void *user, const hg_rec_entry *table, size_t n_recs, const uint32_t *which, size_t m, const int16_t *hv, const int32_t *n2,
+              const uint32_t *) {
+  IndividualRows &o = *static_cast<IndividualRows *>(user);
+  const Cli &c = *o.c;
+  if (m == 0) {  // the table alone: every record must have a name, also one that --min_length leaves out
+    for (size_t r = 0; r < n_recs; ++r)
+      if (!table[r].id_len) die(*o.file + ": record " + std::to_string(r + 1) + " has an empty identifier");
+    return 0;
+  }
+  for (size_t k = 0; k < m; ++k) {
+    const hg_rec_entry &e = table[which[k]];
+    const int16_t *row = hv + k * c.hv_d;
+    const uint32_t q = hg_hv_quant_bits(row, (uint32_t)c.hv_d);
+    const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
+    o.payload.emplace_back((pk_bytes + 1) / 2);
+    if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(row, (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(o.payload.back().data())) != HG_OK) die("pack");
+    o.names.emplace_back(reinterpret_cast<const char *>(o.text + e.hdr_off + 1), e.id_len);
+    hg_file_sketch r;
+    std::memset(&r, 0, sizeof r);
+    r.ksize = (uint8_t)c.ksize, r.canonical = c.canonical, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = n2[k];
+    r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
+    r.file_str = o.names.back().c_str();
+    r.hv = o.payload.back().data(), r.hv_len = pk_bytes / 2;
+    o.recs.push_back(r);
+  }
+  return 0;
+}
+
+int run_sketch_individual(const Cli &c, const std::vector<std::string> &files) {
+  logline("INFO", "Start sketching...");
+  const double t0 = now_s();
+  if (c.scaled == 0) die("scaled must be >= 1");
+  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
+  if (c.hv_d % 256)
+    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
+  hg_sketch_params p;
+  hg_sketch_params_default(&p);
+  const bool gpu_mode = c.device == "gpu";  // (run_sketch's reading of -C and -D)
+  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed;
+  p.canonical = gpu_mode ? (c.canonical ? 1u : 0u) : 1u;
+  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2;
+  p.norm_mode = gpu_mode ? HG_NORM_ACGT : HG_NORM_U2T;
+  p.min_count = c.min_count;
+  if (hg_device_count() <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+  hg_ctx *ctx = nullptr;
+  if (hg_ctx_create(0, &ctx) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+
+  IndividualRows rows{&c, nullptr, nullptr, c.min_length, {}, {}, {}};
+  uint8_t *text = nullptr;
+  size_t cap = 0, n_total = 0;
+  for (const std::string &file : files) {
+    size_t n = 0;
+    const hg_status rs = hg_rec_read_text(file.c_str(), &text, &cap, &n);
+    if (rs == HG_ERR_UNSUPPORTED) die(file + ": the file holds 2^32 bytes or more after inflation, --individual takes files below 4 GiB");
+    if (rs != HG_OK) die("Opening .fna files failed: " + file);
+    DevBuf<uint8_t> d_text(ctx, ((n + 15) & ~(size_t)15) + 16);
+    d_text.upload(text, n);
+    rows.file = &file, rows.text = text;
+    size_t n_recs = 0, n_kept = 0;
+    const hg_status ss = hg_rec_sketch_text_dev(ctx, d_text.get(), n, &p, c.min_length, take_rows, &rows, &n_recs, &n_kept);
+    if (ss != HG_OK) die(file + ": " + hg_status_str(ss) + " (" + hg_last_error(ctx) + ")");
+    debugf("%s: %zu bytes, %zu records, %zu sketched", file.c_str(), n, n_recs, n_kept);
+    n_total += n_recs;
+  }
+  hg_pinned_free(text);
+  const size_t n = rows.recs.size();
+  const double secs = now_s() - t0;
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "Sketching %zu records of %zu files took %.2fs - Speed: %.1f records/s", n, files.size(), secs,
+                n / std::max(secs, 1e-9));
+  logline("INFO", buf);
+  if (n < n_total) {
+    std::snprintf(buf, sizeof buf, "%zu records shorter than %llu were left out", n_total - n, c.min_length);
+    logline("INFO", buf);
+  }
+  if (hg_sketch_file_write(c.out.c_str(), rows.recs.data(), n) != HG_OK) die("Dump sketch file failed!");
+  size_t total = 8;
+  for (auto &r : rows.recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
+  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
+  logline("INFO", buf);
+  hg_ctx_destroy(ctx);
+  return 0;
+}
 
 // A loaded .sketch file: the records (names, norms, widths) on the host, the bit-packed payloads still inside the file
 // image.  decompress_file_sketch (src/hd.rs:171-180) happens on the device: the image's payload bytes go over the link as
