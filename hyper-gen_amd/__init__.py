@@ -11,6 +11,7 @@ Note for processes that also use PyTorch-ROCm: import torch BEFORE this module l
 (torch bundles its own copy of the HIP runtime; loaded second it finds no devices).
 """
 import ctypes as C
+import functools
 import os
 import threading
 import subprocess
@@ -155,6 +156,19 @@ def build(force=False):
     subprocess.check_call(["make", "-s", "-j4", "-C", os.path.join(_HERE, "csrc"), "all"])
 
 
+def _load(name, path, sig, exports=None, note=""):
+    """The shared library `name` at `path` with restype / argtypes set from sig = {symbol: (restype, argtypes)}; sig must
+    name exactly the symbols of `exports`, if given."""
+    if not os.path.exists(path):
+        raise ImportError("%s is not built: run `python -c 'import __graft_entry__ as g; g.build()'`%s" % (name, note))
+    assert exports is None or sorted(sig) == sorted(exports)
+    L = C.CDLL(path)
+    for sym, (res, args) in sig.items():
+        fn = getattr(L, sym)  # AttributeError here == the ABI lost a symbol
+        fn.restype, fn.argtypes = res, args
+    return L
+
+
 _lib = None
 
 
@@ -162,10 +176,6 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("libhypergen_hip.so is not built: run `python -c 'import __graft_entry__ as g; "
-                          "g.build()'` (there is no CPU fallback)")
-    L = C.CDLL(LIB_PATH)
     vp, sz = C.c_void_p, C.c_size_t
     u8p, u64p, i16p, i32p, u32p, f32p = (C.POINTER(t) for t in (
         C.c_uint8, C.c_uint64, C.c_int16, C.c_int32, C.c_uint32, C.c_float))
@@ -337,15 +347,41 @@ def lib():
         "hg_search_topk_multi_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(vp), sz,
                                                C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, vp]),
     }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)  # AttributeError here == the ABI lost a symbol
-        fn.restype, fn.argtypes = res, args
-    _lib = L
-    return L
+    _lib = _load("libhypergen_hip.so", LIB_PATH, sig, note=" (there is no CPU fallback)")
+    return _lib
 
 
 def _ptr(a):
     return C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else C.c_void_p(int(a))
+
+
+def _u8(seq):
+    """bytes or an array as a contiguous uint8 array"""
+    return np.ascontiguousarray(seq if isinstance(seq, np.ndarray) else np.frombuffer(bytes(seq), np.uint8), dtype=np.uint8)
+
+
+def _sketch_batch_host(ck, fn, handle, seqs, p):
+    """one of the host-memory batch sketchers on a list of sequences: (hv, norm2, nhash)"""
+    arrs = [_u8(s) for s in seqs]
+    n = len(arrs)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    hv = np.zeros((n, p.hv_d), np.int16)
+    n2 = np.zeros(n, np.int32)
+    nh = np.zeros(n, np.uint32)
+    ck(fn(handle, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
+    return hv, n2, nh
+
+
+def _sized_then_called(call, seq_cap, rec_cap):
+    """a splitter call(seq_cap, rec_cap) -> (status, n_recs, seq_bytes, recs, seq); without capacities a first call sizes
+    the outputs: rec_cap = n_recs and seq_cap = seq_bytes + 32"""
+    if seq_cap is None or rec_cap is None:
+        st, n_recs, seq_bytes, _, _ = call(0, 0)
+        if st != ERR_CAPACITY:
+            return st, n_recs, seq_bytes, np.zeros(0, REC_DTYPE), np.zeros(0, np.uint8)
+        seq_cap, rec_cap = seq_bytes + 32, n_recs
+    return call(seq_cap, rec_cap)
 
 
 # ---- libhypergen_aa.so (include/hypergen_aa.h): amino-acid k-mer sketches; the contexts are this module's ----
@@ -354,18 +390,12 @@ AA_EXPORTS = [
     "hg_aa_hash_sample", "hg_aa_sketch_batch_dev", "hg_aa_sketch_batch", "hg_aa_read_fasta", "hg_aa_kernel_name",
     "hg_aa_tile_starts", "hg_aa_item_starts",
 ]
-_lib_aa = None
 
 
+@functools.lru_cache(None)
 def lib_aa():
     """The companion library, loaded behind lib() (it links libhypergen_hip.so; the loader finds the copy already in the process)."""
-    global _lib_aa
-    if _lib_aa is not None:
-        return _lib_aa
     lib()
-    if not os.path.exists(AA_LIB_PATH):
-        raise ImportError("libhypergen_aa.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(AA_LIB_PATH)
     vp, sz = C.c_void_p, C.c_size_t
     sig = {
         "hg_aa_hash_sample": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, vp, sz, C.POINTER(sz)]),
@@ -376,25 +406,25 @@ def lib_aa():
         "hg_aa_tile_starts": (C.c_uint32, []),
         "hg_aa_item_starts": (C.c_uint32, [C.c_uint32]),
     }
-    assert sorted(sig) == sorted(AA_EXPORTS)
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib_aa = L
-    return L
+    return _load("libhypergen_aa.so", AA_LIB_PATH, sig, AA_EXPORTS)
+
+
+def _read_file(read, free, what, path):
+    """read(path, byref(buffer), byref(capacity), byref(n)) -> status; the n bytes it left in the buffer, which free() releases"""
+    buf, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    st = read(os.fsencode(path), C.byref(buf), C.byref(cap), C.byref(n))
+    try:
+        if st != OK:
+            raise HgError(st, "%s: %s" % (what, path))
+        return C.string_at(buf, n.value)
+    finally:
+        free(buf)
 
 
 def aa_read_fasta(path):
     """hg_aa_read_fasta: a protein FASTA file (plain or gzip) as one proteome, a uint8 array -- the records' sequence bytes with
     line ends, blanks, tabs and CRs dropped and one '*' at every record start.  Needs no GPU."""
-    buf, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-    st = lib_aa().hg_aa_read_fasta(os.fsencode(path), C.byref(buf), C.byref(cap), C.byref(n))
-    try:
-        if st != OK:
-            raise HgError(st, "hg_aa_read_fasta: %s" % path)
-        return np.frombuffer(C.string_at(buf, n.value), np.uint8).copy() if n.value else np.zeros(0, np.uint8)
-    finally:
-        lib().hg_free(buf)
+    return np.frombuffer(_read_file(lib_aa().hg_aa_read_fasta, lib().hg_free, "hg_aa_read_fasta", path), np.uint8).copy()
 
 
 def aa_kernel_name(ksize):
@@ -416,18 +446,12 @@ TX_EXPORTS = [
     "hg_tx_hash_sample", "hg_tx_sketch_batch_dev", "hg_tx_sketch_batch", "hg_tx_translate_frame", "hg_tx_kernel_name",
     "hg_tx_tile_starts", "hg_tx_item_starts", "hg_tx_plan_describe", "hg_tx_plan_regrows",
 ]
-_lib_tx = None
 
 
+@functools.lru_cache(None)
 def lib_tx():
     """The second companion library, loaded behind lib() like lib_aa()."""
-    global _lib_tx
-    if _lib_tx is not None:
-        return _lib_tx
     lib()
-    if not os.path.exists(TX_LIB_PATH):
-        raise ImportError("libhypergen_tx.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(TX_LIB_PATH)
     vp, sz = C.c_void_p, C.c_size_t
     sig = {
         "hg_tx_hash_sample": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, C.c_uint64, vp, sz, C.POINTER(sz)]),
@@ -440,18 +464,13 @@ def lib_tx():
         "hg_tx_plan_describe": (C.c_int, [vp, vp, sz, C.c_uint32, C.c_uint64, vp]),
         "hg_tx_plan_regrows": (C.c_uint64, [vp]),
     }
-    assert sorted(sig) == sorted(TX_EXPORTS)
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib_tx = L
-    return L
+    return _load("libhypergen_tx.so", TX_LIB_PATH, sig, TX_EXPORTS)
 
 
 def tx_translate_frame(seq, frame):
     """hg_tx_translate_frame: reading frame 0..5 of a nucleotide sequence as bytes, stops '*', codons with a non-base 'X'.
     Needs no GPU."""
-    a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
+    a = _u8(seq)
     out = np.zeros(a.size // 3 + 1, np.uint8)
     n = C.c_size_t(0)
     st = lib_tx().hg_tx_translate_frame(_ptr(a) if a.size else None, a.size, frame, _ptr(out), out.size, C.byref(n))
@@ -495,18 +514,12 @@ REC_EXPORTS = [
 REC_DTYPE = np.dtype([("hdr_off", np.uint64), ("hdr_len", np.uint32), ("id_len", np.uint32), ("seq_off", np.uint64),
                       ("seq_len", np.uint64)])  # hg_rec_entry
 REC_ROWS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p)
-_lib_rec = None
 
 
+@functools.lru_cache(None)
 def lib_rec():
     """The third companion library, loaded behind lib() like lib_aa()."""
-    global _lib_rec
-    if _lib_rec is not None:
-        return _lib_rec
     lib()
-    if not os.path.exists(REC_LIB_PATH):
-        raise ImportError("libhypergen_rec.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(REC_LIB_PATH)
     vp, sz = C.c_void_p, C.c_size_t
     sig = {
         "hg_rec_count_dev": (C.c_int, [vp, vp, sz, C.POINTER(sz), C.POINTER(sz)]),
@@ -519,12 +532,7 @@ def lib_rec():
         "hg_rec_kernel_names": (C.c_char_p, []),
         "hg_rec_launch_counts": (C.c_uint32, [vp, C.c_uint32]),
     }
-    assert sorted(sig) == sorted(REC_EXPORTS)
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    _lib_rec = L
-    return L
+    return _load("libhypergen_rec.so", REC_LIB_PATH, sig, REC_EXPORTS)
 
 
 def rec_block_bytes():
@@ -560,25 +568,12 @@ def _rec_host_call(fn, text, seq_cap, rec_cap, fill):
 def rec_split_host(text, seq_cap=None, rec_cap=None, fill=0xEE):
     """hg_rec_split_host (one host thread, needs no GPU).  Without capacities: a first call sizes the outputs, rec_cap = n_recs and
     seq_cap = seq_bytes + 32.  Returns (status, n_recs, seq_bytes, recs, seq)."""
-    fn = lib_rec().hg_rec_split_host
-    if seq_cap is None or rec_cap is None:
-        st, n_recs, seq_bytes, _, _ = _rec_host_call(fn, text, 0, 0, fill)
-        if st != ERR_CAPACITY:
-            return st, n_recs, seq_bytes, np.zeros(0, REC_DTYPE), np.zeros(0, np.uint8)
-        seq_cap, rec_cap = seq_bytes + 32, n_recs
-    return _rec_host_call(fn, text, seq_cap, rec_cap, fill)
+    return _sized_then_called(lambda sc, rc: _rec_host_call(lib_rec().hg_rec_split_host, text, sc, rc, fill), seq_cap, rec_cap)
 
 
 def rec_read_text(path):
     """hg_rec_read_text: the bytes of a file, gzip inflated, read into page-locked memory (needs the HIP runtime)"""
-    buf, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
-    st = lib_rec().hg_rec_read_text(os.fsencode(path), C.byref(buf), C.byref(cap), C.byref(n))
-    try:
-        if st != OK:
-            raise HgError(st, "hg_rec_read_text: %s" % path)
-        return C.string_at(buf, n.value)
-    finally:
-        lib().hg_pinned_free(buf)
+    return _read_file(lib_rec().hg_rec_read_text, lib().hg_pinned_free, "hg_rec_read_text", path)
 
 
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
@@ -688,29 +683,28 @@ class Context:
         return {name: (float(ms[i]), int(n[i])) for i, name in enumerate(T_NAMES)}
 
     # ---- host-buffer entry points -----------------------------------------------------------
-    def kmer_hash_sample(self, seq, ksize=21, scaled=1500, seed=123, canonical=True,
-                         norm=NORM_ACGT, threshold=None, cap=None, min_count=1):
-        """The distinct sampled hashes, ascending; min_count > 1: those that occur at least that often (hg_kmer_hash_sample_min_count)."""
-        a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq,
-                                 dtype=np.uint8)
+    def _hash_sample(self, call, seq, scaled, threshold, cap, per_start=1):
+        """call(seq pointer, seq bytes, threshold, out pointer, cap, byref(n)) -> status, with an output that grows to what
+        the call asks for while it returns ERR_CAPACITY; the default capacity allows for per_start k-mers per start"""
+        a = _u8(seq)
         thr = (2**64 - 1) // scaled if threshold is None else threshold
-        cap = cap if cap is not None else max(1024, a.size // max(1, scaled) * 2 + 1024)
+        cap = cap if cap is not None else max(1024, per_start * a.size // max(1, scaled) * 2 + 1024)
         while True:
             out = np.zeros(max(cap, 1), np.uint64)
             n = C.c_size_t(0)
-            if min_count > 1:
-                st = lib().hg_kmer_hash_sample_min_count(self._h, _ptr(a) if a.size else None, a.size, ksize,
-                                                         C.c_uint64(thr), C.c_uint64(seed), int(canonical), norm, min_count,
-                                                         _ptr(out), cap, C.byref(n))
-            else:
-                st = lib().hg_kmer_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize,
-                                               C.c_uint64(thr), C.c_uint64(seed), int(canonical), norm,
-                                               _ptr(out), cap, C.byref(n))
+            st = call(_ptr(a) if a.size else None, a.size, C.c_uint64(thr), _ptr(out), cap, C.byref(n))
             if st == ERR_CAPACITY:
                 cap = n.value
                 continue
             self._ck(st)
             return out[: n.value].copy()
+
+    def kmer_hash_sample(self, seq, ksize=21, scaled=1500, seed=123, canonical=True,
+                         norm=NORM_ACGT, threshold=None, cap=None, min_count=1):
+        """The distinct sampled hashes, ascending; min_count > 1: those that occur at least that often (hg_kmer_hash_sample_min_count)."""
+        fn, more = (lib().hg_kmer_hash_sample_min_count, (min_count,)) if min_count > 1 else (lib().hg_kmer_hash_sample, ())
+        return self._hash_sample(lambda a, n, thr, *out: fn(self._h, a, n, ksize, thr, C.c_uint64(seed), int(canonical), norm, *more, *out),
+                                 seq, scaled, threshold, cap)
 
     def unpack2_dev(self, d_blob, n_bps, d_out):
         """hg_unpack2_dev on device pointers (ints)"""
@@ -725,71 +719,27 @@ class Context:
         return hv, int(n2.value)
 
     def sketch_batch(self, seqs, params=None):
-        p = params or default_params()
-        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray)
-                else np.frombuffer(bytes(s), np.uint8) for s in seqs]
-        n = len(arrs)
-        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-        hv = np.zeros((n, p.hv_d), np.int16)
-        n2 = np.zeros(n, np.int32)
-        nh = np.zeros(n, np.uint32)
-        self._ck(lib().hg_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
-        return hv, n2, nh
+        return _sketch_batch_host(self._ck, lib().hg_sketch_batch, self._h, seqs, params or default_params())
 
     # ---- amino-acid k-mers (libhypergen_aa.so) ----------------------------------------------
     def aa_hash_sample(self, seq, ksize=9, scaled=1500, seed=123, threshold=None, cap=None):
         """hg_aa_hash_sample: the distinct sampled hashes of a residue sequence, ascending"""
-        a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
-        thr = (2**64 - 1) // scaled if threshold is None else threshold
-        cap = cap if cap is not None else max(1024, a.size // max(1, scaled) * 2 + 1024)
-        while True:
-            out = np.zeros(max(cap, 1), np.uint64)
-            n = C.c_size_t(0)
-            st = lib_aa().hg_aa_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize, C.c_uint64(thr), C.c_uint64(seed),
-                                            _ptr(out), cap, C.byref(n))
-            if st == ERR_CAPACITY:
-                cap = n.value
-                continue
-            self._ck(st)
-            return out[: n.value].copy()
+        return self._hash_sample(lambda a, n, thr, *out: lib_aa().hg_aa_hash_sample(self._h, a, n, ksize, thr, C.c_uint64(seed), *out),
+                                 seq, scaled, threshold, cap)
 
     def aa_sketch_batch(self, seqs, params=None):
         """hg_aa_sketch_batch: (hv, norm2, nhash) of host proteomes"""
-        p = params or default_params(ksize=9)
-        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray) else np.frombuffer(bytes(s), np.uint8) for s in seqs]
-        n = len(arrs)
-        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-        hv = np.zeros((n, p.hv_d), np.int16)
-        n2 = np.zeros(n, np.int32)
-        nh = np.zeros(n, np.uint32)
-        self._ck(lib_aa().hg_aa_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
-        return hv, n2, nh
+        return _sketch_batch_host(self._ck, lib_aa().hg_aa_sketch_batch, self._h, seqs, params or default_params(ksize=9))
 
     def aa_sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
         """hg_aa_sketch_batch_dev on device pointers (ints); final in stream order"""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        ln = np.ascontiguousarray(lens, np.uint64)
-        self._ck(lib_aa().hg_aa_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
-                                                 _ptr(d_norm2), _ptr(d_nhash)))
+        self._sketch_batch_dev(lib_aa().hg_aa_sketch_batch_dev, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash)
 
     # ---- six-frame translated k-mers (libhypergen_tx.so) -------------------------------------
     def tx_hash_sample(self, seq, ksize=9, scaled=1500, seed=123, threshold=None, cap=None):
         """hg_tx_hash_sample: the distinct sampled hashes of the six frames of a nucleotide sequence, ascending"""
-        a = np.ascontiguousarray(np.frombuffer(bytes(seq), np.uint8) if not isinstance(seq, np.ndarray) else seq, dtype=np.uint8)
-        thr = (2**64 - 1) // scaled if threshold is None else threshold
-        cap = cap if cap is not None else max(1024, 2 * a.size // max(1, scaled) * 2 + 1024)
-        while True:
-            out = np.zeros(max(cap, 1), np.uint64)
-            n = C.c_size_t(0)
-            st = lib_tx().hg_tx_hash_sample(self._h, _ptr(a) if a.size else None, a.size, ksize, C.c_uint64(thr), C.c_uint64(seed),
-                                            _ptr(out), cap, C.byref(n))
-            if st == ERR_CAPACITY:
-                cap = n.value
-                continue
-            self._ck(st)
-            return out[: n.value].copy()
+        return self._hash_sample(lambda a, n, thr, *out: lib_tx().hg_tx_hash_sample(self._h, a, n, ksize, thr, C.c_uint64(seed), *out),
+                                 seq, scaled, threshold, cap, per_start=2)
 
     def tx_plan_regrows(self):
         """hg_tx_plan_regrows: how often this ctx's synchronous sketch path rebuilt a plan after a hit region overflowed"""
@@ -797,23 +747,11 @@ class Context:
 
     def tx_sketch_batch(self, seqs, params=None):
         """hg_tx_sketch_batch: (hv, norm2, nhash) of host genomes (ASCII)"""
-        p = params or default_params(ksize=9)
-        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray) else np.frombuffer(bytes(s), np.uint8) for s in seqs]
-        n = len(arrs)
-        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-        hv = np.zeros((n, p.hv_d), np.int16)
-        n2 = np.zeros(n, np.int32)
-        nh = np.zeros(n, np.uint32)
-        self._ck(lib_tx().hg_tx_sketch_batch(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
-        return hv, n2, nh
+        return _sketch_batch_host(self._ck, lib_tx().hg_tx_sketch_batch, self._h, seqs, params or default_params(ksize=9))
 
     def tx_sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
         """hg_tx_sketch_batch_dev on device pointers (ints); final in stream order"""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        ln = np.ascontiguousarray(lens, np.uint64)
-        self._ck(lib_tx().hg_tx_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv),
-                                                 _ptr(d_norm2), _ptr(d_nhash)))
+        self._sketch_batch_dev(lib_tx().hg_tx_sketch_batch_dev, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash)
 
     # ---- one multi-FASTA text into records (libhypergen_rec.so) --------------------------------
     def rec_count_dev(self, d_text, n):
@@ -833,12 +771,7 @@ class Context:
         """hg_rec_split, host memory in and out, with the arguments and results of rec_split_host()"""
         def fn(*a):
             return self._ck(lib_rec().hg_rec_split(self._h, *a), allow=(ERR_IO, ERR_CAPACITY))
-        if seq_cap is None or rec_cap is None:
-            st, n_recs, seq_bytes, _, _ = _rec_host_call(fn, text, 0, 0, fill)
-            if st != ERR_CAPACITY:
-                return st, n_recs, seq_bytes, np.zeros(0, REC_DTYPE), np.zeros(0, np.uint8)
-            seq_cap, rec_cap = seq_bytes + 32, n_recs
-        return _rec_host_call(fn, text, seq_cap, rec_cap, fill)
+        return _sized_then_called(lambda sc, rc: _rec_host_call(fn, text, sc, rc, fill), seq_cap, rec_cap)
 
     def rec_sketch_text_dev(self, d_text, n, params, min_length=0):
         """hg_rec_sketch_text_dev on a device pointer (int): (record table, indices of the sketched records, hv, norm2, nhash),
@@ -896,18 +829,17 @@ class Context:
             return out[: n.value].copy()
 
     # ---- device-resident entry points (pointers are ints, e.g. torch.Tensor.data_ptr()) -------
-    def sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
+    def _sketch_batch_dev(self, fn, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
         off = np.ascontiguousarray(offsets, np.uint64)
         ln = np.ascontiguousarray(lens, np.uint64)
-        self._ck(lib().hg_sketch_batch_dev(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size,
-                                           C.byref(params), _ptr(d_hv), _ptr(d_norm2), _ptr(d_nhash)))
+        self._ck(fn(self._h, _ptr(d_seq), _ptr(off), _ptr(ln), off.size, C.byref(params), _ptr(d_hv), _ptr(d_norm2), _ptr(d_nhash)))
+
+    def sketch_batch_dev(self, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash):
+        self._sketch_batch_dev(lib().hg_sketch_batch_dev, d_seq, offsets, lens, params, d_hv, d_norm2, d_nhash)
 
     def sketch_batch_dev_packed(self, d_blobs, offsets, n_bps, params, d_hv, d_norm2, d_nhash):
         """hg_sketch_batch_dev_packed: genome i is the hg_pack2 blob at d_blobs + offsets[i] (multiples of 16)"""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        ln = np.ascontiguousarray(n_bps, np.uint64)
-        self._ck(lib().hg_sketch_batch_dev_packed(self._h, _ptr(d_blobs), _ptr(off), _ptr(ln), off.size,
-                                                  C.byref(params), _ptr(d_hv), _ptr(d_norm2), _ptr(d_nhash)))
+        self._sketch_batch_dev(lib().hg_sketch_batch_dev_packed, d_blobs, offsets, n_bps, params, d_hv, d_norm2, d_nhash)
 
     def pack2_batch_dev(self, d_seq, offsets, lens, d_blobs, blob_offsets, norm_mode=NORM_ACGT):
         """hg_pack2_batch_dev: ASCII genomes resident in HBM -> hg_pack2 blobs (device pointers are ints)"""
@@ -1381,17 +1313,7 @@ class Multi:
         return lib().hg_multi_gather_report(self._h).decode()
 
     def sketch_batch(self, seqs, params=None):
-        p = params or default_params()
-        arrs = [np.ascontiguousarray(s, dtype=np.uint8) if isinstance(s, np.ndarray)
-                else np.frombuffer(bytes(s), np.uint8) for s in seqs]
-        n = len(arrs)
-        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data if a.size else None for a in arrs])
-        lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
-        hv = np.zeros((n, p.hv_d), np.int16)
-        n2 = np.zeros(n, np.int32)
-        nh = np.zeros(n, np.uint32)
-        self._ck(lib().hg_sketch_batch_multi(self._h, ptrs, lens, n, C.byref(p), _ptr(hv), _ptr(n2), _ptr(nh)))
-        return hv, n2, nh
+        return _sketch_batch_host(self._ck, lib().hg_sketch_batch_multi, self._h, seqs, params or default_params())
 
     def dist(self, ref_hv, ref_n2, qry_hv=None, qry_n2=None, ksize=21, symmetric=False, ani_th=85.0, cap=None):
         r = np.ascontiguousarray(ref_hv, np.int16)

@@ -1,17 +1,12 @@
-// hg_aa.h -- what the two translation units of libhypergen_aa.so share (not installed): the kernel's geometry, the residue
-// test and t1ha2 for at most 32 bytes, both as plain C++ for host and device (the host forms are what a stand-alone CPU check
-// of the kernel's arithmetic compiles), and the launcher.
+// hg_aa.h -- what the two translation units of libhypergen_aa.so share (not installed): the residue test and t1ha2 for at
+// most 32 bytes, both as plain C++ for host and device (the host forms are what a stand-alone CPU check of the kernel's
+// arithmetic compiles), and the launcher.  The kernel's geometry (HG_AA_*) is hg_kmer_window.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hg_internal.h"
-
-constexpr uint32_t HG_AA_WG = 256;                        // lanes per workgroup
-constexpr uint32_t HG_AA_BYTES = 16 * HG_AA_WG;           // staged bytes per tile: 16 per lane, one wide load
-constexpr uint32_t HG_AA_TILE = HG_AA_BYTES - 64;         // k-mer starts per tile: the last start reads up to 40 bytes
-constexpr uint32_t HG_AA_STAGE = 1024;                    // entries of the LDS hit stage
-static_assert(HG_AA_TILE % 4 == 0 && HG_AA_TILE + 40 <= HG_AA_BYTES, "amino-acid tile geometry");
+#include "hg_kmer_window.h"
 
 // bit (c - 'A') set <=> upper-case letter c is one of ACDEFGHIKLMNPQRSTVWY
 constexpr uint32_t HG_AA_LETTERS = (1u << 0) | (1u << 2) | (1u << 3) | (1u << 4) | (1u << 5) | (1u << 6) | (1u << 7) | (1u << 8) |

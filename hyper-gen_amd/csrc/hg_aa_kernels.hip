@@ -22,50 +22,19 @@
 //    stage full (every window of a repeat samples the same hash) reserve their slots with one atomic per wave.
 // Templated on KW = ceil(k / 8); k itself is a kernel argument: four instantiations.  Plain C++, no inline assembly.
 // 12.8 KiB of LDS per workgroup, 48 VGPRs; the kernel is integer-VALU bound like its nucleotide twins.
-#include "hg_aa.h"
+// The window test and the gather are hg_kmer_window.h's, the hit stage, the sample step and the KW dispatch hg_sample_core.h's
+// (shared with tx_kmer_sample_kernel); staging, the residue test, the tile walk and the clean-tile shortcut are this file's.
+#include "hg_sample_core.h"
 
 namespace {
 
 constexpr uint32_t WG = HG_AA_WG;
-constexpr uint32_t INV_WORDS = HG_AA_BYTES / 32 + 2;  // the bit image, two zero words of slack behind it
 
 struct AaLds {
-  uint32_t img[HG_AA_BYTES / 4];   // the tile's bytes, bit 5 cleared
-  uint32_t inv[INV_WORDS];         // bit i set <=> staged byte i is not a residue
-  uint64_t hits[HG_AA_STAGE];      // sampled hashes waiting for a flush
-  uint32_t n_hits, base;
+  uint32_t img[HG_AA_IMG_WORDS];   // the tile's bytes, bit 5 cleared
+  uint32_t inv[HG_AA_INV_WORDS];   // bit i set <=> staged byte i is not a residue
+  HgHitStage<HG_AA_STAGE> stage;   // sampled hashes waiting for a flush
 };
-
-// the hit region's slots [base, base + n) reserved with one atomic for all lanes of the wave that are here together
-__device__ __forceinline__ void append_hit(uint64_t h, const hg_genome_meta &gm, uint32_t g, uint64_t *__restrict__ hits,
-                                           uint32_t *__restrict__ cnt) {
-  const unsigned long long m = __ballot(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t base = 0;
-  if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&cnt[g], (uint32_t)__popcll(m));
-  base = __builtin_amdgcn_readfirstlane(base);  // (the first active lane is the one that asked)
-  const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (idx < gm.hit_cap) hits[gm.hit_off + idx] = h;
-}
-
-// Empties the stage into the proteome's hit region (the raw counter keeps counting past hit_cap).  Two barriers; every lane
-// of the workgroup calls it.  The caller's next barrier lies between this call's reads and the next hit.
-__device__ __forceinline__ void flush_stage(AaLds &s, const hg_genome_meta &gm, uint32_t g, uint64_t *__restrict__ hits,
-                                            uint32_t *__restrict__ cnt) {
-  __syncthreads();
-  const uint32_t n = s.n_hits < HG_AA_STAGE ? s.n_hits : HG_AA_STAGE;
-  if (threadIdx.x == 0 && n) s.base = atomicAdd(&cnt[g], n);
-  __syncthreads();
-  const uint32_t base = s.base;
-  for (uint32_t i = threadIdx.x; i < n; i += WG) {
-    const uint32_t idx = base + i;
-    if (idx < gm.hit_cap) hits[gm.hit_off + idx] = s.hits[i];
-  }
-  __syncthreads();  // (n_hits and base have been read by every lane)
-  if (threadIdx.x == 0) s.n_hits = 0;
-}
-
-typedef uint32_t __attribute__((ext_vector_type(4), aligned(4))) u32x4_a4;  // 16 bytes at a 4-byte aligned address
 
 template <int KW>
 __global__ __launch_bounds__(WG) void aa_kmer_sample_kernel(const uint8_t *__restrict__ seq, const hg_genome_meta *__restrict__ meta,
@@ -82,16 +51,14 @@ __global__ __launch_bounds__(WG) void aa_kmer_sample_kernel(const uint8_t *__res
   const uint8_t *__restrict__ gseq = seq + gm.seq_off;
   const uint64_t item_start = (uint64_t)(item - gm.item_first) * item_starts;  // a multiple of 4, like every tile's first start
   const uint64_t item_end = item_start + item_starts < n_starts ? item_start + item_starts : n_starts;
-  if (tid == 0) s.n_hits = 0;
+  if (tid == 0) s.stage.n_hits = 0;
   if (tid < 2) s.inv[HG_AA_BYTES / 32 + tid] = 0u;
-  const uint32_t win_mask = ksize >= 32 ? ~0u : (1u << ksize) - 1u;               // bits of a window in the bit image
-  const uint32_t tail_bytes = ksize - 8u * (KW - 1);                             // bytes of the k-mer's last word, 1..8
-  const uint64_t tail_mask = tail_bytes >= 8 ? ~0ull : (1ull << (8u * tail_bytes)) - 1ull;
-  const uint32_t sh8 = 8u * (tid & 3u);                                          // the lane's byte phase, as a bit shift
+  const HgWindowParams wn = {ksize, hg_win_mask(ksize), hg_win_tail_mask(ksize, KW), threshold, seed};
+  const uint32_t sh8 = 8u * (tid & 3u);  // the lane's byte phase, as a bit shift
 
   for (uint64_t tile0 = item_start; tile0 < item_end; tile0 += HG_AA_TILE) {
     __syncthreads();  // the previous tile's readers are done, its hits are counted
-    if (s.n_hits >= HG_AA_STAGE / 4) flush_stage(s, gm, g, hits, cnt);  // (workgroup-uniform)
+    if (s.stage.n_hits >= HG_AA_STAGE / 4) flush_stage<WG>(s.stage, gm, g, hits, cnt);  // (workgroup-uniform)
     // ---- stage: the lane's 16 bytes [q, q + 16)
     uint32_t bad16 = 0xFFFFu;
     {
@@ -118,32 +85,13 @@ __global__ __launch_bounds__(WG) void aa_kmer_sample_kernel(const uint8_t *__res
     const uint64_t left_starts = item_end - tile0;  // > 0
     const uint32_t lim = left_starts < HG_AA_TILE ? (uint32_t)left_starts : HG_AA_TILE;
     for (uint32_t p = tid; p < lim; p += WG) {
-      if (dirty) {  // a non-residue inside [p, p + k)?
-        const uint32_t dw = p >> 5, sh = p & 31u;
-        const uint64_t two = (uint64_t)s.inv[dw] | ((uint64_t)s.inv[dw + 1] << 32);
-        if (((uint32_t)(two >> sh) & win_mask) != 0u) continue;
-      }
-      const uint32_t *d = s.img + (p >> 2);  // the k-mer's bytes start sh8 bits into d[0]
+      if (dirty && hg_win_any_bit(s.inv, p, wn.win_mask)) continue;  // a non-residue inside [p, p + k)
       uint64_t w[KW];
-      uint32_t lo = d[0];
-#pragma unroll
-      for (int i = 0; i < KW; ++i) {
-        const uint32_t mid = d[2 * i + 1], hi = d[2 * i + 2];
-        const uint32_t w_lo = (uint32_t)(((uint64_t)lo | ((uint64_t)mid << 32)) >> sh8);
-        const uint32_t w_hi = (uint32_t)(((uint64_t)mid | ((uint64_t)hi << 32)) >> sh8);
-        w[i] = (uint64_t)w_lo | ((uint64_t)w_hi << 32);
-        lo = hi;
-      }
-      w[KW - 1] &= tail_mask;
-      const uint64_t h = hg_aa_t1ha2::hash_words<KW>(w, ksize, seed);
-      if (h < threshold) {
-        const uint32_t idx = atomicAdd(&s.n_hits, 1u);
-        if (idx < HG_AA_STAGE) s.hits[idx] = h;
-        else append_hit(h, gm, g, hits, cnt);
-      }
+      hg_win_gather(s.img + (p >> 2), sh8, KW, wn.tail_mask, w);
+      sample_kmer<KW>(s.stage, w, wn, gm, g, hits, cnt);
     }
   }
-  flush_stage(s, gm, g, hits, cnt);
+  flush_stage<WG>(s.stage, gm, g, hits, cnt);
 }
 
 }  // namespace
@@ -153,15 +101,7 @@ hipError_t hg_aa_launch_kmer_sample(hipStream_t st, const uint8_t *d_seq, const 
   if (n_items == 0) return hipSuccess;
   if (ksize < 1 || ksize > 32) return hipErrorInvalidValue;
   const uint32_t item_starts = hg_kmer_item_starts(ksize);  // the plan's
-#define HG_AA_LAUNCH(KW)                                                                                                          \
-  hipLaunchKernelGGL((aa_kmer_sample_kernel<KW>), dim3(n_items), dim3(WG), 0, st, d_seq, d_meta, d_item_genome, ksize, item_starts, \
-                     threshold, seed, d_hits, d_cnt)
-  switch ((ksize + 7) / 8) {
-    case 1: HG_AA_LAUNCH(1); break;
-    case 2: HG_AA_LAUNCH(2); break;
-    case 3: HG_AA_LAUNCH(3); break;
-    default: HG_AA_LAUNCH(4); break;
-  }
-#undef HG_AA_LAUNCH
+  HG_LAUNCH_BY_KW(aa_kmer_sample_kernel, ksize, n_items, WG, st, d_seq, d_meta, d_item_genome, ksize, item_starts, threshold, seed,
+                  d_hits, d_cnt);
   return hipGetLastError();
 }

@@ -369,6 +369,15 @@ void print_sketch_help() {
               "         It does not go with --alphabet protein, with --translate or with --shards.\n");
 }
 
+// what --translate and --alphabet protein (`opt`; its input is `input`) have in common: neither goes with --min_count or
+// --shards, k defaults to 9 and is at most 32
+void amino_acid_mode(Cli &c, const std::string &opt, const std::string &input) {
+  if (c.min_count > 1) die("--min_count is not supported with " + opt + ": amino-acid k-mers are sketched without the count filter");
+  if (c.shards) die("--shards is not supported with " + opt + ": " + input + " input is sketched on the first visible GPU");
+  if (!given(c, "ksize")) c.ksize = 9;
+  if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': " + opt + " takes k-mers of 1 to 32 residues");
+}
+
 Cli parse(int argc, char **argv) {
   if (argc < 2) die("usage: hyper-gen <sketch|dist|search|cluster> [options]   (see --help)");
   Cli c;
@@ -498,10 +507,7 @@ Cli parse(int argc, char **argv) {
   if (given(c, "newick") && given(c, "pairs")) die("--pairs is not supported with --newick: the tree needs every pair, not the listed ones");
   if (c.translate) {
     if (c.protein) die("--translate is not supported with --alphabet protein: protein input is not translated");
-    if (c.min_count > 1) die("--min_count is not supported with --translate: amino-acid k-mers are sketched without the count filter");
-    if (c.shards) die("--shards is not supported with --translate: translated input is sketched on the first visible GPU");
-    if (!given(c, "ksize")) c.ksize = 9;  // as for --alphabet protein
-    if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': --translate takes k-mers of 1 to 32 residues");
+    amino_acid_mode(c, "--translate", "translated");  // (k defaults as for --alphabet protein)
   }
   if (c.individual) {
     if (c.protein) die("--individual is not supported with --alphabet protein: protein input is sketched one file at a time");
@@ -509,12 +515,7 @@ Cli parse(int argc, char **argv) {
     if (c.shards) die("--shards is not supported with --individual: the records are sketched on the first visible GPU");
   }
   if (c.min_length_given && !c.individual) die("--min_length needs --individual: without it sketch makes one sketch per file, whatever its length");
-  if (c.protein) {
-    if (c.min_count > 1) die("--min_count is not supported with --alphabet protein: amino-acid k-mers are sketched without the count filter");
-    if (c.shards) die("--shards is not supported with --alphabet protein: protein input is sketched on the first visible GPU");
-    if (!given(c, "ksize")) c.ksize = 9;  // Mash's protein default
-    if (c.ksize > 32) die("invalid value '" + std::to_string(c.ksize) + "' for '--ksize': --alphabet protein takes k-mers of 1 to 32 residues");
-  }
+  if (c.protein) amino_acid_mode(c, "--alphabet protein", "protein");  // (Mash's protein default for k)
   return c;
 }
 
@@ -552,6 +553,68 @@ std::vector<std::string> fasta_files(const std::string &dir, std::initializer_li
   return out;
 }
 
+// ---- what the four sketch drivers share: the parameters, the records, the closing lines ---------------------------------
+// --scaled and --hv_d checked, then the sketch parameters of the command line.  companion: --alphabet protein and --translate,
+// which hash one strand and have no count filter.
+hg_sketch_params sketch_params(const Cli &c, bool companion) {
+  if (c.scaled == 0) die("scaled must be >= 1");
+  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
+  if (c.hv_d % 256)  // the reference packs whole 256-blocks only (src/hd.rs:147) and says nothing; same bytes here
+    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
+  hg_sketch_params p;
+  hg_sketch_params_default(&p);
+  const bool gpu_mode = c.device == "gpu";
+  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed;
+  // -C is honoured by the reference's CUDA kernel only (src/cuda_kernel.cu:312-314); its CPU path always takes
+  // needletail's canonical_kmers (src/sketch.rs:89) -- the flag still goes into the .sketch records as given
+  p.canonical = companion ? 0u : gpu_mode ? (c.canonical ? 1u : 0u) : 1u;
+  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2;
+  p.norm_mode = companion || gpu_mode ? HG_NORM_ACGT : HG_NORM_U2T;
+  p.min_count = companion ? 1 : c.min_count;
+  return p;
+}
+
+// The records of a .sketch file while they are collected; they point into the names and payloads, which are owned here
+// (deques: growing them moves no element).
+struct SketchRecords {
+  const Cli &c;
+  std::deque<std::string> names;
+  std::deque<std::vector<int16_t>> payload;
+  std::vector<hg_file_sketch> recs;
+  explicit SketchRecords(const Cli &cli, size_t n = 0) : c(cli), recs(n) {}
+  // record `at` (recs.size(): one more) from a sketched row: the hypervector compressed, the rest from the command line
+  void put(size_t at, const int16_t *hv, int32_t norm2, std::string name, bool canonical) {
+    const uint32_t q = hg_hv_quant_bits(hv, (uint32_t)c.hv_d);  // if_compressed is hard-wired true (utils.rs:200)
+    const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
+    payload.emplace_back((pk_bytes + 1) / 2);  // (the i16 view of the bytes, src/hd.rs:155-157)
+    if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(hv, (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(payload.back().data())) != HG_OK) die("pack");
+    names.push_back(std::move(name));
+    if (at == recs.size()) recs.emplace_back();
+    hg_file_sketch &r = recs[at];
+    std::memset(&r, 0, sizeof r);
+    r.ksize = (uint8_t)c.ksize, r.canonical = canonical, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = norm2;
+    r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
+    r.file_str = names.back().c_str();
+    r.hv = payload.back().data(), r.hv_len = pk_bytes / 2;  // align_to::<i16>().1: whole i16s
+  }
+};
+
+// The closing lines of a sketch run started at t0: `head` ("Sketching N files") with the time and the speed in `unit`s, `note`
+// if there is one, the .sketch file written, its size.
+void finish_sketch(const Cli &c, double t0, const std::string &head, const char *unit, const SketchRecords &out, const std::string &note = "") {
+  const size_t n = out.recs.size();
+  const double secs = now_s() - t0;
+  char buf[256];
+  std::snprintf(buf, sizeof buf, "%s took %.2fs - Speed: %.1f %s/s", head.c_str(), secs, n / std::max(secs, 1e-9), unit);
+  logline("INFO", buf);
+  if (!note.empty()) logline("INFO", note);
+  if (hg_sketch_file_write(c.out.c_str(), out.recs.data(), n) != HG_OK) die("Dump sketch file failed!");
+  size_t total = 8;
+  for (auto &r : out.recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
+  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
+  logline("INFO", buf);
+}
+
 int run_sketch_batches(const Cli &c, const std::vector<std::string> &files);
 int run_sketch_individual(const Cli &c, const std::vector<std::string> &files);
 
@@ -565,24 +628,9 @@ int run_sketch(const Cli &c) {
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
   const double t0 = now_s();
-  if (c.scaled == 0) die("scaled must be >= 1");
-  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
-  if (c.hv_d % 256)  // the reference packs whole 256-blocks only (src/hd.rs:147) and says nothing; same bytes here
-    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
-  hg_sketch_params p;
-  hg_sketch_params_default(&p);
-  const bool gpu_mode = c.device == "gpu";
-  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed;
-  // -C is honoured by the reference's CUDA kernel only (src/cuda_kernel.cu:312-314); its CPU path always takes
-  // needletail's canonical_kmers (src/sketch.rs:89) -- the flag still goes into the .sketch records as given
-  p.canonical = gpu_mode ? (c.canonical ? 1u : 0u) : 1u;
-  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2;
-  p.norm_mode = gpu_mode ? HG_NORM_ACGT : HG_NORM_U2T;
-  p.min_count = c.min_count;
-  const uint32_t read_mode = gpu_mode ? HG_READ_MERGE : HG_READ_NEEDLETAIL;
-
-  std::vector<std::vector<int16_t>> payload(n);
-  std::vector<hg_file_sketch> recs(n);
+  const hg_sketch_params p = sketch_params(c, false);
+  const uint32_t read_mode = c.device == "gpu" ? HG_READ_MERGE : HG_READ_NEEDLETAIL;
+  SketchRecords out(c, n);
 
   // Reader side: -t persistent threads pull file indices from one counter; every thread owns S page-locked buffers
   // and fills them round robin (hg_read_fastx_pinned: the device then fetches the sequence by DMA at the PCIe rate
@@ -680,16 +728,7 @@ int run_sketch(const Cli &c) {
     }
     cv_space[owner].notify_one();
     const double ts1 = now_s();
-    const uint32_t q = hg_hv_quant_bits(hv.data(), (uint32_t)c.hv_d);  // if_compressed is hard-wired true (utils.rs:200)
-    const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
-    payload[f].resize((pk_bytes + 1) / 2);  // (the i16 view of the bytes, src/hd.rs:155-157)
-    if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(hv.data(), (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(payload[f].data())) != HG_OK) die("pack");
-    hg_file_sketch &r = recs[f];
-    std::memset(&r, 0, sizeof r);
-    r.ksize = (uint8_t)c.ksize, r.canonical = c.canonical, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = n2;
-    r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
-    r.file_str = files[f].c_str();
-    r.hv = payload[f].data(), r.hv_len = pk_bytes / 2;  // align_to::<i16>().1: whole i16s
+    out.put(f, hv.data(), n2, files[f], c.canonical);
     t_wait += ts1 - tw0, t_pack += now_s() - ts1;
   }
   for (auto &t : readers) t.join();
@@ -702,15 +741,7 @@ int run_sketch(const Cli &c) {
   debugf("collector: waited %.1f ms for results, sketch compression %.1f ms; readers: %.2f ms per file and thread, "
          "%zu of %zu files sent 2-bit packed", t_wait * 1e3, t_pack * 1e3, n ? read_ns.load() / 1e6 / n : 0.0,
          n_packed.load(), n);
-  const double secs = now_s() - t0;
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "Sketching %zu files took %.2fs - Speed: %.1f files/s", n, secs, n / std::max(secs, 1e-9));
-  logline("INFO", buf);
-  if (hg_sketch_file_write(c.out.c_str(), recs.data(), n) != HG_OK) die("Dump sketch file failed!");
-  size_t total = 8;
-  for (auto &r : recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
-  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
-  logline("INFO", buf);
+  finish_sketch(c, t0, "Sketching " + std::to_string(n) + " files", "files", out);
   const double tf0 = now_s();
   hg_sketch_stream_close(stream);
   for (auto &sl : slots) hg_pinned_free(sl.p);
@@ -737,20 +768,12 @@ int run_sketch_batches(const Cli &c, const std::vector<std::string> &files) {
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
   const double t0 = now_s();
-  if (c.scaled == 0) die("scaled must be >= 1");
-  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
-  if (c.hv_d % 256)
-    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
-  hg_sketch_params p;
-  hg_sketch_params_default(&p);
-  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed, p.canonical = 0;
-  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2, p.norm_mode = HG_NORM_ACGT, p.min_count = 1;
+  const hg_sketch_params p = sketch_params(c, true);
   if (hg_device_count() <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
   hg_ctx *ctx = nullptr;
   if (hg_ctx_create(0, &ctx) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
 
-  std::vector<std::vector<int16_t>> payload(n);
-  std::vector<hg_file_sketch> recs(n);
+  SketchRecords out(c, n);
   constexpr size_t BATCH_FILES = 256, BATCH_BYTES = (size_t)1 << 30;
   struct Buf {
     uint8_t *p = nullptr;
@@ -780,31 +803,10 @@ int run_sketch_batches(const Cli &c, const std::vector<std::string> &files) {
     for (size_t k = 0; k < m; ++k) ptrs[k] = bufs[k].p, lens[k] = bufs[k].len;
     hv.resize(m * c.hv_d);
     ck(ctx, (tx ? hg_tx_sketch_batch : hg_aa_sketch_batch)(ctx, ptrs.data(), lens.data(), m, &p, hv.data(), n2.data(), nh.data()), "sketch");
-    for (size_t k = 0; k < m; ++k) {
-      const size_t f = i0 + k;
-      const int16_t *row = hv.data() + k * c.hv_d;
-      const uint32_t q = hg_hv_quant_bits(row, (uint32_t)c.hv_d);
-      const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
-      payload[f].resize((pk_bytes + 1) / 2);
-      if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(row, (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(payload[f].data())) != HG_OK) die("pack");
-      hg_file_sketch &r = recs[f];
-      std::memset(&r, 0, sizeof r);
-      r.ksize = (uint8_t)c.ksize, r.canonical = false, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = n2[k];
-      r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
-      r.file_str = files[f].c_str();
-      r.hv = payload[f].data(), r.hv_len = pk_bytes / 2;
-    }
+    for (size_t k = 0; k < m; ++k) out.put(i0 + k, hv.data() + k * c.hv_d, n2[k], files[i0 + k], false);
     i0 += m;
   }
-  const double secs = now_s() - t0;
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "Sketching %zu files took %.2fs - Speed: %.1f files/s", n, secs, n / std::max(secs, 1e-9));
-  logline("INFO", buf);
-  if (hg_sketch_file_write(c.out.c_str(), recs.data(), n) != HG_OK) die("Dump sketch file failed!");
-  size_t total = 8;
-  for (auto &r : recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
-  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
-  logline("INFO", buf);
+  finish_sketch(c, t0, "Sketching " + std::to_string(n) + " files", "files", out);
   for (Buf &b : bufs) hg_free(b.p);
   hg_ctx_destroy(ctx);
   return 0;
@@ -837,18 +839,14 @@ class DevBuf {
 // hg_rec_sketch_text_dev splits it into its records there and sketches them in sub-batches, and the rows come back through
 // take_rows, which packs them.  The parameters are run_sketch's; a record's file_str is its identifier.
 struct IndividualRows {
-  const Cli *c;
   const std::string *file;
   const uint8_t *text;
-  unsigned long long min_length;
-  std::deque<std::string> names;                 // (a deque: the records point into the strings)
-  std::deque<std::vector<int16_t>> payload;
-  std::vector<hg_file_sketch> recs;
+  SketchRecords out;
 };
 int take_rows(void *user, const hg_rec_entry *table, size_t n_recs, const uint32_t *which, size_t m, const int16_t *hv, const int32_t *n2,
               const uint32_t *) {
   IndividualRows &o = *static_cast<IndividualRows *>(user);
-  const Cli &c = *o.c;
+  const Cli &c = o.out.c;
   if (m == 0) {  // the table alone: every record must have a name, also one that --min_length leaves out
     for (size_t r = 0; r < n_recs; ++r)
       if (!table[r].id_len) die(*o.file + ": record " + std::to_string(r + 1) + " has an empty identifier");
@@ -856,19 +854,8 @@ int take_rows(void *user, const hg_rec_entry *table, size_t n_recs, const uint32
   }
   for (size_t k = 0; k < m; ++k) {
     const hg_rec_entry &e = table[which[k]];
-    const int16_t *row = hv + k * c.hv_d;
-    const uint32_t q = hg_hv_quant_bits(row, (uint32_t)c.hv_d);
-    const size_t pk_bytes = c.pack_naive ? hg_hv_packed_bytes_naive((uint32_t)c.hv_d, q) : hg_hv_packed_bytes((uint32_t)c.hv_d, q);
-    o.payload.emplace_back((pk_bytes + 1) / 2);
-    if ((c.pack_naive ? hg_hv_pack_naive : hg_hv_pack)(row, (uint32_t)c.hv_d, q, reinterpret_cast<uint8_t *>(o.payload.back().data())) != HG_OK) die("pack");
-    o.names.emplace_back(reinterpret_cast<const char *>(o.text + e.hdr_off + 1), e.id_len);
-    hg_file_sketch r;
-    std::memset(&r, 0, sizeof r);
-    r.ksize = (uint8_t)c.ksize, r.canonical = c.canonical, r.hv_quant_bits = (uint8_t)q, r.hv_norm_2 = n2[k];
-    r.scaled = c.scaled, r.seed = c.seed, r.hv_d = c.hv_d;
-    r.file_str = o.names.back().c_str();
-    r.hv = o.payload.back().data(), r.hv_len = pk_bytes / 2;
-    o.recs.push_back(r);
+    o.out.put(o.out.recs.size(), hv + k * c.hv_d, n2[k], std::string(reinterpret_cast<const char *>(o.text + e.hdr_off + 1), e.id_len),
+              c.canonical);
   }
   return 0;
 }
@@ -876,23 +863,12 @@ int take_rows(void *user, const hg_rec_entry *table, size_t n_recs, const uint32
 int run_sketch_individual(const Cli &c, const std::vector<std::string> &files) {
   logline("INFO", "Start sketching...");
   const double t0 = now_s();
-  if (c.scaled == 0) die("scaled must be >= 1");
-  if (c.hv_d == 0 || c.hv_d > 32768) die("hv_d must be in 1..32768");
-  if (c.hv_d % 256)
-    logline("WARN", "hv_d is not a multiple of 256: the dimensions behind the last whole block are lost in the .sketch file (as in the reference)");
-  hg_sketch_params p;
-  hg_sketch_params_default(&p);
-  const bool gpu_mode = c.device == "gpu";  // (run_sketch's reading of -C and -D)
-  p.ksize = c.ksize, p.scaled = c.scaled, p.seed = c.seed;
-  p.canonical = gpu_mode ? (c.canonical ? 1u : 0u) : 1u;
-  p.hv_d = (uint32_t)c.hv_d, p.hv_layout = HG_LAYOUT_AVX2;
-  p.norm_mode = gpu_mode ? HG_NORM_ACGT : HG_NORM_U2T;
-  p.min_count = c.min_count;
+  const hg_sketch_params p = sketch_params(c, false);  // (run_sketch's reading of -C and -D)
   if (hg_device_count() <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
   hg_ctx *ctx = nullptr;
   if (hg_ctx_create(0, &ctx) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
 
-  IndividualRows rows{&c, nullptr, nullptr, c.min_length, {}, {}, {}};
+  IndividualRows rows{nullptr, nullptr, SketchRecords(c)};
   uint8_t *text = nullptr;
   size_t cap = 0, n_total = 0;
   for (const std::string &file : files) {
@@ -910,21 +886,10 @@ int run_sketch_individual(const Cli &c, const std::vector<std::string> &files) {
     n_total += n_recs;
   }
   hg_pinned_free(text);
-  const size_t n = rows.recs.size();
-  const double secs = now_s() - t0;
-  char buf[256];
-  std::snprintf(buf, sizeof buf, "Sketching %zu records of %zu files took %.2fs - Speed: %.1f records/s", n, files.size(), secs,
-                n / std::max(secs, 1e-9));
-  logline("INFO", buf);
-  if (n < n_total) {
-    std::snprintf(buf, sizeof buf, "%zu records shorter than %llu were left out", n_total - n, c.min_length);
-    logline("INFO", buf);
-  }
-  if (hg_sketch_file_write(c.out.c_str(), rows.recs.data(), n) != HG_OK) die("Dump sketch file failed!");
-  size_t total = 8;
-  for (auto &r : rows.recs) total += 47 + std::strlen(r.file_str) + r.hv_len * 2;
-  std::snprintf(buf, sizeof buf, "Dump sketch file to %s with size %.2f MB", c.out.c_str(), total / 1024.0 / 1024.0);
-  logline("INFO", buf);
+  const size_t n = rows.out.recs.size();
+  char note[128] = "";
+  if (n < n_total) std::snprintf(note, sizeof note, "%zu records shorter than %llu were left out", n_total - n, c.min_length);
+  finish_sketch(c, t0, "Sketching " + std::to_string(n) + " records of " + std::to_string(files.size()) + " files", "records", rows.out, note);
   hg_ctx_destroy(ctx);
   return 0;
 }

@@ -1,22 +1,12 @@
-// hg_tx.h -- what the two translation units of libhypergen_tx.so share (not installed): the kernel's geometry, the base
-// classification and the codon translation as plain C++ for host and device -- the kernel fills its LDS tables from the very
-// functions hg_tx_translate_frame runs on the host, so a CPU test of the frame strings is a test of the kernel's tables --
-// and the launcher.  t1ha2 for at most 32 bytes is hg_aa.h's.
+// hg_tx.h -- what the two translation units of libhypergen_tx.so share (not installed): the base classification and the
+// codon translation as plain C++ for host and device -- the kernel fills its LDS tables from the very functions
+// hg_tx_translate_frame runs on the host, so a CPU test of the frame strings is a test of the kernel's tables -- and the
+// launcher.  t1ha2 for at most 32 bytes is hg_aa.h's, the kernel's geometry (HG_TX_*) hg_kmer_window.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hg_aa.h"
-
-constexpr uint32_t HG_TX_WG = 256;                   // lanes per workgroup
-constexpr uint32_t HG_TX_BYTES = 16 * HG_TX_WG;      // staged nucleotides per tile: 16 per lane, one wide load
-constexpr uint32_t HG_TX_TILE = HG_TX_BYTES - 96;    // nucleotide starts per tile: the last start's window spans 3 * 32 bytes
-constexpr uint32_t HG_TX_STAGE = 1024;               // entries of the LDS hit stage
-constexpr uint32_t HG_TX_CHUNK = 24;                 // codon starts one lane translates: 8 residues of each of the 3 phases
-constexpr uint32_t HG_TX_CHUNKS = (HG_TX_BYTES + HG_TX_CHUNK - 1) / HG_TX_CHUNK;  // 171
-constexpr uint32_t HG_TX_PHASE_LEN = 8 * HG_TX_CHUNKS;                            // residues of one phase image: 1 368
-static_assert(HG_TX_TILE % 4 == 0 && HG_TX_TILE + 96 <= HG_TX_BYTES, "translated tile geometry");
-static_assert(HG_TX_CHUNKS <= HG_TX_WG, "one chunk per lane");
 
 // ---- bases --------------------------------------------------------------------------------------------------------------
 // The code of byte value c (0..255): 0 A, 1 C, 2 T, 3 G -- bits 1..2 of the ASCII letter, in either case -- or HG_TX_NOT_A_BASE

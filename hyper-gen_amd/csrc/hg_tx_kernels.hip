@@ -29,14 +29,16 @@
 // 21 992 bytes of LDS per workgroup (4.0 KiB codes, 8.3 images, 1.1 bit images, 0.1 tables, 8.0 hit stage) and 80 VGPRs
 // (78 for KW = 4), no scratch: six workgroups per CU by registers, seven by LDS.  Integer-VALU bound like
 // its twins: two hashes per byte.
+// The window test and the gather are hg_kmer_window.h's, the hit stage, the sample step and the KW dispatch hg_sample_core.h's
+// (shared with aa_kmer_sample_kernel); the two staging steps and the walk over the phase images are this file's.
+#include "hg_sample_core.h"
 #include "hg_tx.h"
 
 namespace {
 
 constexpr uint32_t WG = HG_TX_WG;
 constexpr uint32_t CODE_WORDS = HG_TX_BYTES / 4 + 4;       // the code image, 16 bytes of "not a base" behind it
-constexpr uint32_t IMG_WORDS = HG_TX_PHASE_LEN / 4 + 10;   // one phase image; a window's dword reads end at most 9 words behind its first
-constexpr uint32_t INV_WORDS = HG_TX_PHASE_LEN / 32 + 4;   // one bit image; a window reads two words
+constexpr uint32_t IMG_WORDS = HG_TX_IMG_WORDS, INV_WORDS = HG_TX_INV_WORDS;
 static_assert(6 * (HG_TX_CHUNKS - 1) + 7 <= CODE_WORDS, "a chunk reads 26 code bytes as 7 dwords");
 
 struct TxLds {
@@ -44,77 +46,19 @@ struct TxLds {
   uint32_t img[6][IMG_WORDS];     // residues: [r] forward, [3 + r] reverse strand (descending), r = start mod 3
   uint32_t inv[6][INV_WORDS];     // bit i set <=> byte i of the image is not a residue
   uint8_t tab[2][64];             // hg_tx_table_fwd, hg_tx_table_rev
-  uint64_t hits[HG_TX_STAGE];     // sampled hashes waiting for a flush
-  uint32_t n_hits, base;
+  HgHitStage<HG_TX_STAGE> stage;  // sampled hashes waiting for a flush
 };
 
-// the hit region's slots [base, base + n) reserved with one atomic for all lanes of the wave that are here together
-__device__ __forceinline__ void append_hit(uint64_t h, const hg_genome_meta &gm, uint32_t g, uint64_t *__restrict__ hits,
-                                           uint32_t *__restrict__ cnt) {
-  const unsigned long long m = __ballot(1);
-  const uint32_t lane = threadIdx.x & 63u;
-  uint32_t base = 0;
-  if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&cnt[g], (uint32_t)__popcll(m));
-  base = __builtin_amdgcn_readfirstlane(base);  // (the first active lane is the one that asked)
-  const uint32_t idx = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  if (idx < gm.hit_cap) hits[gm.hit_off + idx] = h;
-}
-
-// Empties the stage into the genome's hit region (the raw counter keeps counting past hit_cap).  Two barriers; every lane
-// of the workgroup calls it.  The caller's next barrier lies between this call's reads and the next hit.
-__device__ __forceinline__ void flush_stage(TxLds &s, const hg_genome_meta &gm, uint32_t g, uint64_t *__restrict__ hits,
-                                            uint32_t *__restrict__ cnt) {
-  __syncthreads();
-  const uint32_t n = s.n_hits < HG_TX_STAGE ? s.n_hits : HG_TX_STAGE;
-  if (threadIdx.x == 0 && n) s.base = atomicAdd(&cnt[g], n);
-  __syncthreads();
-  const uint32_t base = s.base;
-  for (uint32_t i = threadIdx.x; i < n; i += WG) {
-    const uint32_t idx = base + i;
-    if (idx < gm.hit_cap) hits[gm.hit_off + idx] = s.hits[i];
-  }
-  __syncthreads();  // (n_hits and base have been read by every lane)
-  if (threadIdx.x == 0) s.n_hits = 0;
-}
-
-// what a window needs beside its place: the same for every window of a launch
-struct TxWindow {
-  uint32_t ksize, win_mask;
-  uint64_t tail_mask, threshold, seed;
-};
-
-// the k-mer of the k bytes from byte a of one phase image: tested, hashed, sampled
+// the k-mer of the k bytes from byte a of one phase image: tested (a stop or an 'X' inside [a, a + k)?), hashed, sampled
 template <int KW>
 __device__ __forceinline__ void sample_window(TxLds &s, const uint32_t *__restrict__ img, const uint32_t *__restrict__ inv, uint32_t a,
-                                              const TxWindow &wn, const hg_genome_meta &gm, uint32_t g, uint64_t *__restrict__ hits,
-                                              uint32_t *__restrict__ cnt) {
-  {  // a stop or an 'X' inside [a, a + k)?
-    const uint32_t dw = a >> 5, sh = a & 31u;
-    const uint64_t two = (uint64_t)inv[dw] | ((uint64_t)inv[dw + 1] << 32);
-    if (((uint32_t)(two >> sh) & wn.win_mask) != 0u) return;
-  }
-  const uint32_t *d = img + (a >> 2);
-  const uint32_t sh8 = 8u * (a & 3u);  // the k-mer's bytes start sh8 bits into d[0]
+                                              const HgWindowParams &wn, const hg_genome_meta &gm, uint32_t g,
+                                              uint64_t *__restrict__ hits, uint32_t *__restrict__ cnt) {
+  if (hg_win_any_bit(inv, a, wn.win_mask)) return;
   uint64_t w[KW];
-  uint32_t lo = d[0];
-#pragma unroll
-  for (int i = 0; i < KW; ++i) {
-    const uint32_t mid = d[2 * i + 1], hi = d[2 * i + 2];
-    const uint32_t w_lo = (uint32_t)(((uint64_t)lo | ((uint64_t)mid << 32)) >> sh8);
-    const uint32_t w_hi = (uint32_t)(((uint64_t)mid | ((uint64_t)hi << 32)) >> sh8);
-    w[i] = (uint64_t)w_lo | ((uint64_t)w_hi << 32);
-    lo = hi;
-  }
-  w[KW - 1] &= wn.tail_mask;
-  const uint64_t h = hg_aa_t1ha2::hash_words<KW>(w, wn.ksize, wn.seed);
-  if (h < wn.threshold) {
-    const uint32_t idx = atomicAdd(&s.n_hits, 1u);
-    if (idx < HG_TX_STAGE) s.hits[idx] = h;
-    else append_hit(h, gm, g, hits, cnt);
-  }
+  hg_win_gather(img + (a >> 2), 8u * (a & 3u), KW, wn.tail_mask, w);
+  sample_kmer<KW>(s.stage, w, wn, gm, g, hits, cnt);
 }
-
-typedef uint32_t __attribute__((ext_vector_type(4), aligned(4))) u32x4_a4;  // 16 bytes at a 4-byte aligned address
 
 template <int KW>
 __global__ __launch_bounds__(WG) void tx_kmer_sample_kernel(const uint8_t *__restrict__ seq, const hg_genome_meta *__restrict__ meta,
@@ -132,22 +76,18 @@ __global__ __launch_bounds__(WG) void tx_kmer_sample_kernel(const uint8_t *__res
   const uint8_t *__restrict__ gseq = seq + gm.seq_off;
   const uint64_t item_start = (uint64_t)(item - gm.item_first) * item_starts;  // a multiple of 4, like every tile's first start
   const uint64_t item_end = item_start + item_starts < n_starts ? item_start + item_starts : n_starts;
-  if (tid == 0) s.n_hits = 0;
+  if (tid == 0) s.stage.n_hits = 0;
   if (tid < 4) s.codes[HG_TX_BYTES / 4 + tid] = 0x04040404u;  // behind the staged bytes: not bases
   if (tid < 64) s.tab[0][tid] = hg_tx_table_fwd(tid), s.tab[1][tid] = hg_tx_table_rev(tid);
   for (uint32_t i = tid; i < 6 * INV_WORDS; i += WG) (&s.inv[0][0])[i] = 0u;
   // the words behind an image's residues: a window near the top reads them (and shifts or masks them away); staging never writes them
   if (tid < 6 * (IMG_WORDS - HG_TX_PHASE_LEN / 4)) s.img[tid / (IMG_WORDS - HG_TX_PHASE_LEN / 4)][HG_TX_PHASE_LEN / 4 + tid % (IMG_WORDS - HG_TX_PHASE_LEN / 4)] = 0u;
-  TxWindow wn;
-  wn.ksize = ksize, wn.threshold = threshold, wn.seed = seed;
-  wn.win_mask = ksize >= 32 ? ~0u : (1u << ksize) - 1u;       // bits of a window in a bit image
-  const uint32_t tail_bytes = ksize - 8u * (KW - 1);          // bytes of the k-mer's last word, 1..8
-  wn.tail_mask = tail_bytes >= 8 ? ~0ull : (1ull << (8u * tail_bytes)) - 1ull;
+  const HgWindowParams wn = {ksize, hg_win_mask(ksize), hg_win_tail_mask(ksize, KW), threshold, seed};
   const uint32_t rev_top = HG_TX_PHASE_LEN - ksize;           // first byte of the reverse window of j = 0
 
   for (uint64_t tile0 = item_start; tile0 < item_end; tile0 += HG_TX_TILE) {
     __syncthreads();  // the previous tile's readers are done, its hits are counted (first tile: the tables are written)
-    if (s.n_hits >= HG_TX_STAGE / 4) flush_stage(s, gm, g, hits, cnt);  // (workgroup-uniform)
+    if (s.stage.n_hits >= HG_TX_STAGE / 4) flush_stage<WG>(s.stage, gm, g, hits, cnt);  // (workgroup-uniform)
     // ---- stage 1: the lane's 16 bytes [q, q + 16) as codes
     {
       const uint64_t q = tile0 + 16ull * tid;
@@ -214,7 +154,7 @@ __global__ __launch_bounds__(WG) void tx_kmer_sample_kernel(const uint8_t *__res
       }
     }
   }
-  flush_stage(s, gm, g, hits, cnt);
+  flush_stage<WG>(s.stage, gm, g, hits, cnt);
 }
 
 }  // namespace
@@ -224,15 +164,7 @@ hipError_t hg_tx_launch_kmer_sample(hipStream_t st, const uint8_t *d_seq, const 
   if (n_items == 0) return hipSuccess;
   if (ksize < 1 || ksize > 32) return hipErrorInvalidValue;
   const uint32_t item_starts = hg_kmer_item_starts(ksize);  // the plan's
-#define HG_TX_LAUNCH(KW)                                                                                                          \
-  hipLaunchKernelGGL((tx_kmer_sample_kernel<KW>), dim3(n_items), dim3(WG), 0, st, d_seq, d_meta, d_item_genome, ksize, item_starts, \
-                     threshold, seed, d_hits, d_cnt)
-  switch ((ksize + 7) / 8) {
-    case 1: HG_TX_LAUNCH(1); break;
-    case 2: HG_TX_LAUNCH(2); break;
-    case 3: HG_TX_LAUNCH(3); break;
-    default: HG_TX_LAUNCH(4); break;
-  }
-#undef HG_TX_LAUNCH
+  HG_LAUNCH_BY_KW(tx_kmer_sample_kernel, ksize, n_items, WG, st, d_seq, d_meta, d_item_genome, ksize, item_starts, threshold, seed,
+                  d_hits, d_cnt);
   return hipGetLastError();
 }

@@ -58,3 +58,16 @@ def test_hostfed_batch_layout_under_asan_ubsan(tmp_path):
                            "-o", str(exe)])
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "hostfed layout driver ok" in out.stdout, out.stdout + out.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_kmer_window_arithmetic_under_asan_ubsan(tmp_path):
+    """the window test and the gather the amino-acid and the translated k-mer kernel share (hg_kmer_window.h, compiled
+    without HIP): every k in 1..32 at every start byte 0..71 against bit-wise and byte-wise references, and the read extent
+    of the kernels' largest starts inside heap blocks of the size of their LDS images"""
+    exe = tmp_path / "aa_window_driver"
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "native", "aa_window_driver.cpp"),
+                           "-o", str(exe)])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "aa window driver ok" in out.stdout, out.stdout + out.stderr
