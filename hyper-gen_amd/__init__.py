@@ -1134,37 +1134,43 @@ class Context:
         """rounds of the last tree call on this ctx, summed over its blocks (hg_ctx_cluster_tree_rounds)"""
         return int(lib().hg_ctx_cluster_tree_rounds(self._h))
 
-    # ---- average linkage, UPGMA (hg_cluster_average*) ---------------------------------------------
-    def cluster_average(self, hv, n2, ksize=21, ani_th=95.0):
-        """hg_cluster_average on host sketches: numpy (rep, cluster, into, level, size, n_clusters) -- rep[i] = the smallest
-        index of i's cluster, cluster[i] = its dense id in order of rep; the dendrogram: into[b] = the name b was absorbed
-        into (b itself if never), level[b] = the average ANI of that merge (0 if never), size[b] = the size of the merged
-        cluster (of b's own final cluster if never)"""
+    # ---- the three forms of a linkage scheme on the dense matrix (average, complete), given its C function ----
+    def _linkage_host(self, fn, hv, n2, ksize, ani_th):
         h = np.ascontiguousarray(hv, np.int16)
         nn = np.ascontiguousarray(n2, np.int32)
         n = h.shape[0]
         rep, cl, into, size = (np.zeros(n, np.uint32) for _ in range(4))
         level = np.zeros(n, np.float32)
         nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_average(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th), _ptr(rep), _ptr(cl),
-                                          _ptr(into), _ptr(level), _ptr(size), C.byref(nc)))
+        self._ck(fn(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th), _ptr(rep), _ptr(cl), _ptr(into), _ptr(level),
+                    _ptr(size), C.byref(nc)))
         return rep, cl, into, level, size, nc.value
+
+    def _linkage_dev(self, fn, head, ani_th, d_rep, d_cluster, d_into, d_level, d_size):
+        """head: fn's arguments in front of ani_th -- the resident sketches, or the matrix"""
+        nc = C.c_size_t(0)
+        self._ck(fn(self._h, *head, C.c_float(ani_th), _ptr(d_rep or 0), _ptr(d_cluster or 0), _ptr(d_into or 0), _ptr(d_level or 0),
+                    _ptr(d_size or 0), C.byref(nc)))
+        return nc.value
+
+    # ---- average linkage, UPGMA (hg_cluster_average*) ---------------------------------------------
+    def cluster_average(self, hv, n2, ksize=21, ani_th=95.0):
+        """hg_cluster_average on host sketches: numpy (rep, cluster, into, level, size, n_clusters) -- rep[i] = the smallest
+        index of i's cluster, cluster[i] = its dense id in order of rep; the dendrogram: into[b] = the name b was absorbed
+        into (b itself if never), level[b] = the average ANI of that merge (0 if never), size[b] = the size of the merged
+        cluster (of b's own final cluster if never)"""
+        return self._linkage_host(lib().hg_cluster_average, hv, n2, ksize, ani_th)
 
     def cluster_average_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_into=None, d_level=None, d_size=None, ksize=21, ani_th=95.0):
         """hg_cluster_average_dev on resident sketches (device pointers; d_into, d_level and d_size may each be None);
         returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_average_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep or 0),
-                                              _ptr(d_cluster or 0), _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
-        return nc.value
+        return self._linkage_dev(lib().hg_cluster_average_dev, (_ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize), ani_th,
+                                 d_rep, d_cluster, d_into, d_level, d_size)
 
     def cluster_average_matrix_dev(self, d_ani, n, ani_th, d_rep, d_cluster, d_into=None, d_level=None, d_size=None):
         """hg_cluster_average_matrix_dev on a device-resident n x n float matrix, of which [i, j] with i < j is read
         (d_into, d_level and d_size may each be None); returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_average_matrix_dev(self._h, _ptr(d_ani or 0), n, C.c_float(ani_th), _ptr(d_rep or 0), _ptr(d_cluster or 0),
-                                                     _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
-        return nc.value
+        return self._linkage_dev(lib().hg_cluster_average_matrix_dev, (_ptr(d_ani or 0), n), ani_th, d_rep, d_cluster, d_into, d_level, d_size)
 
     def cluster_average_rounds(self):
         """rounds of the last average-linkage call on this ctx (hg_ctx_cluster_average_rounds)"""
@@ -1176,31 +1182,18 @@ class Context:
         index of i's cluster, cluster[i] = its dense id in order of rep; the dendrogram: into[b] = the name b was absorbed
         into (b itself if never), level[b] = the minimum ANI between the two merged clusters (0 if never), size[b] = the size of the merged
         cluster (of b's own final cluster if never)"""
-        h = np.ascontiguousarray(hv, np.int16)
-        nn = np.ascontiguousarray(n2, np.int32)
-        n = h.shape[0]
-        rep, cl, into, size = (np.zeros(n, np.uint32) for _ in range(4))
-        level = np.zeros(n, np.float32)
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_complete(self._h, _ptr(h), _ptr(nn), n, h.shape[1], ksize, C.c_float(ani_th), _ptr(rep), _ptr(cl),
-                                          _ptr(into), _ptr(level), _ptr(size), C.byref(nc)))
-        return rep, cl, into, level, size, nc.value
+        return self._linkage_host(lib().hg_cluster_complete, hv, n2, ksize, ani_th)
 
     def cluster_complete_dev(self, d_hv, d_n2, n, hv_d, d_rep, d_cluster, d_into=None, d_level=None, d_size=None, ksize=21, ani_th=95.0):
         """hg_cluster_complete_dev on resident sketches (device pointers; d_into, d_level and d_size may each be None);
         returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_complete_dev(self._h, _ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize, C.c_float(ani_th), _ptr(d_rep or 0),
-                                              _ptr(d_cluster or 0), _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
-        return nc.value
+        return self._linkage_dev(lib().hg_cluster_complete_dev, (_ptr(d_hv or 0), _ptr(d_n2 or 0), n, hv_d, ksize), ani_th,
+                                 d_rep, d_cluster, d_into, d_level, d_size)
 
     def cluster_complete_matrix_dev(self, d_ani, n, ani_th, d_rep, d_cluster, d_into=None, d_level=None, d_size=None):
         """hg_cluster_complete_matrix_dev on a device-resident n x n float matrix, of which [i, j] with i < j is read
         (d_into, d_level and d_size may each be None); returns the number of clusters"""
-        nc = C.c_size_t(0)
-        self._ck(lib().hg_cluster_complete_matrix_dev(self._h, _ptr(d_ani or 0), n, C.c_float(ani_th), _ptr(d_rep or 0), _ptr(d_cluster or 0),
-                                                     _ptr(d_into or 0), _ptr(d_level or 0), _ptr(d_size or 0), C.byref(nc)))
-        return nc.value
+        return self._linkage_dev(lib().hg_cluster_complete_matrix_dev, (_ptr(d_ani or 0), n), ani_th, d_rep, d_cluster, d_into, d_level, d_size)
 
     def cluster_complete_rounds(self):
         """rounds of the last complete-linkage call on this ctx (hg_ctx_cluster_complete_rounds)"""

@@ -26,12 +26,13 @@
 //
 // Memory: n_clusters accumulators of 48 bytes, n node records of 24 bytes when the caller wants none, and for resident
 // sketches one block of the ANI matrix -- rows [r0, r1) x all n columns from hg_dist_full_dev in the search's scratch
-// block, at most HG_SEARCH_BLOCK_BYTES ("stats_block_rows" forces the row count).  No n x n matrix is held.
+// block, at most HG_SEARCH_BLOCK_BYTES ("stats_block_rows" forces the row count; the row-block driver is
+// hg_dense_matrix.h's, with whole rows in the place of the triangle).  No n x n matrix is held.
 #include <algorithm>
 
 #include "hg_average_cmp.h"
 #include "hg_cluster_common.h"
-#include "hg_internal.h"
+#include "hg_dense_matrix.h"
 
 static_assert(sizeof(hg_node_stat) == 24 && sizeof(hg_cluster_stat) == 48, "the records of include/hypergen.h");
 
@@ -273,20 +274,13 @@ extern "C" hg_status hg_cluster_stats_dev(hg_ctx *c, const int16_t *d_hv, const 
   HG_ENTER(c);
   if (n == 0) return stats_empty(c, n_clusters, d_stat);
   if (!d_hv || !d_norm2 || !d_cluster) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
-  if (hv_d == 0 || hv_d > 65536) return hg_fail(c, HG_ERR_UNSUPPORTED, "hv_d must be in 1..65536");
-  if (ksize == 0) return hg_fail(c, HG_ERR_INVALID, "ksize must be >= 1");
-  // the scratch block: rows [r0, r0 + rb) x all n columns of the ANI matrix
-  const size_t fit = std::max<size_t>(1, HG_SEARCH_BLOCK_BYTES / (sizeof(float) * n));
-  const size_t rb = std::min<size_t>(n, c->dbg_stats_block_rows ? (size_t)c->dbg_stats_block_rows : fit);
-  if ((s = hg_ensure(c, c->w_srch_blk, rb * n * sizeof(float))) != HG_OK) return s;
-  auto *blk = static_cast<float *>(c->w_srch_blk.p);
+  if ((s = hg_sketch_dims_check(c, hv_d, ksize)) != HG_OK) return s;
+  // rows [r0, r0 + rows) x all n columns of the ANI matrix per block
   Stats g{};
-  if ((s = stats_begin(c, n, d_cluster, n_clusters, d_node, g)) != HG_OK) return s;
-  for (size_t r0 = 0; r0 < n; r0 += rb) {
-    const size_t rows = std::min(rb, n - r0);
-    if ((s = hg_dist_full_dev(c, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, rows, d_hv, d_norm2, n, hv_d, ksize, blk)) != HG_OK) return s;
-    if ((s = stats_rows(c, g, blk, r0, rows, n, d_cluster)) != HG_OK) return s;
-  }
+  s = hg_matrix_row_blocks(
+      c, d_hv, d_norm2, n, hv_d, ksize, c->dbg_stats_block_rows, false, [&] { return stats_begin(c, n, d_cluster, n_clusters, d_node, g); },
+      [&](const float *blk, size_t, size_t, size_t r0, size_t rows) { return stats_rows(c, g, blk, r0, rows, n, d_cluster); });
+  if (s != HG_OK) return s;
   return stats_finish(c, g, n, d_cluster, n_clusters, d_stat);
 }
 

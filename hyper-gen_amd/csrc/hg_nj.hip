@@ -30,18 +30,15 @@
 // results Q (i64), live[] and the row results j (u32); live of a padding column is 0.  hg_nj_dev fills the upper triangle
 // from row blocks of hg_dist_full_dev (rows [r0, r1) x columns [r0, n) in the search's scratch block, at most
 // HG_SEARCH_BLOCK_BYTES; "nj_block_rows" forces the row count) and mirrors it: the rounds read rows a and b whole.
-#include <algorithm>
-
+// The matrix, its fill and mirror and the row blocks are hg_dense_matrix.h's, shared with average and complete linkage.
 #include "hg_cluster_common.h"
-#include "hg_internal.h"
+#include "hg_dense_matrix.h"
 #include "hg_nj_math.h"
 
 static_assert(HG_NJ_MATH_FRAC_BITS == HG_NJ_FRAC_BITS, "hg_nj_math.h and hypergen.h agree on the fixed point");
 static_assert(sizeof(hg_nj_join) == 24, "hg_nj_join is 24 bytes");
 
 namespace {
-constexpr uint32_t NJ_NONE = 0xFFFFFFFFu;
-constexpr uint32_t MIRROR_TILE = 32;
 constexpr uint32_t SCAN_STEP = 1024;  // columns one step of the row scan covers: 256 lanes x 4
 constexpr uint32_t PICK_LANES = 1024;
 
@@ -51,52 +48,23 @@ struct Nj {
   int64_t *r;      // ld: r(i) of a live name
   int64_t *row_q;  // ld: Q of the row's best pair
   uint32_t *live;  // ld: 1 of a live name, 0 of a dead one and of the padding
-  uint32_t *row_j; // ld: the higher name of the row's best pair, NJ_NONE = none (dead rows, the last live row)
+  uint32_t *row_j; // ld: the higher name of the row's best pair, DENSE_NONE = none (dead rows, the last live row)
 };
 
-// the matrix, released when the call returns (hipFree waits for the device)
-struct MatrixHold {
-  void *p = nullptr;
-  ~MatrixHold() {
-    if (p) (void)hipFree(p);
-  }
+struct NjDist {
+  __device__ __forceinline__ uint32_t operator()(float ani) const { return hg_nj_dist(ani); }
 };
 
 __global__ __launch_bounds__(256) void nj_init_kernel(uint32_t *__restrict__ live, uint32_t *__restrict__ row_j, uint32_t n, uint32_t ld) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ld; i += stride) live[i] = i < n ? 1u : 0u, row_j[i] = NJ_NONE;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < ld; i += stride) live[i] = i < n ? 1u : 0u, row_j[i] = DENSE_NONE;
 }
 
-// Rows [r0, r0 + rows) of the matrix from a block of ANI values: blk[r * pitch + (j - c0)] is ani(r0 + r, j), c0 <= r0.
-// Only j > row is read; the diagonal, the lower triangle (the mirror kernel writes it) and the padding columns become 0.
 __global__ __launch_bounds__(256) void nj_fill_kernel(const float *__restrict__ blk, size_t pitch, uint32_t c0, uint32_t r0, uint32_t rows,
                                                       uint32_t n, size_t ld, uint32_t *__restrict__ M) {
-  for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
-    const uint32_t gi = r0 + r;
-    const float *src = blk + (size_t)r * pitch;
-    uint32_t *dst = M + (size_t)gi * ld;
-    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < ld; j += (size_t)gridDim.x * blockDim.x)
-      dst[j] = (j > gi && j < n) ? hg_nj_dist(src[j - c0]) : 0u;
-  }
+  matrix_fill_body<uint32_t, NjDist>(blk, pitch, c0, r0, rows, n, ld, M, HG_LANE0, HG_LANES);
 }
-
-// M[j][i] = M[i][j] for i < j: tiles of 32 x 32 through LDS (the column padded by one word against bank conflicts), the
-// workgroups of the upper triangle of tiles each write their transposed tile (a diagonal tile its own lower half).
-// blockDim = (32, 8).
-__global__ __launch_bounds__(256) void nj_mirror_kernel(uint32_t *M, uint32_t n, size_t ld) {
-  __shared__ uint32_t tile[MIRROR_TILE][MIRROR_TILE + 1];
-  if (blockIdx.x < blockIdx.y) return;  // (uniform over the workgroup)
-  const uint32_t row0 = blockIdx.y * MIRROR_TILE, col0 = blockIdx.x * MIRROR_TILE;
-  for (uint32_t k = threadIdx.y; k < MIRROR_TILE; k += 8) {
-    const uint32_t i = row0 + k, j = col0 + threadIdx.x;
-    tile[k][threadIdx.x] = (i < n && j < n) ? M[(size_t)i * ld + j] : 0u;
-  }
-  __syncthreads();
-  for (uint32_t k = threadIdx.y; k < MIRROR_TILE; k += 8) {
-    const uint32_t j = col0 + k, i = row0 + threadIdx.x;  // writes M[j][i], the value of M[i][j]
-    if (j < n && i < j) M[(size_t)j * ld + i] = tile[threadIdx.x][k];
-  }
-}
+__global__ __launch_bounds__(256) void nj_mirror_kernel(uint32_t *M, uint32_t n, size_t ld) { matrix_mirror_body(M, n, ld); }
 
 __device__ __forceinline__ int64_t block_sum_i64(int64_t v, int64_t *s_wave) {
   for (int d = 32; d >= 1; d >>= 1) v += (int64_t)__shfl_xor((long long)v, d);
@@ -149,7 +117,7 @@ __global__ __launch_bounds__(256) void nj_best_kernel(const uint32_t *__restrict
   const uint4 *row = reinterpret_cast<const uint4 *>(M + (size_t)i * ld);
   const uint4 *lv = reinterpret_cast<const uint4 *>(live);
   int64_t bk = INT64_MAX;
-  uint32_t bj = NJ_NONE;
+  uint32_t bj = DENSE_NONE;
   // from the piece that holds column i + 1; two steps per trip while both are inside the row, their loads independent of
   // each other, then at most one step more
   uint32_t j = ((i + 1u) & ~3u) + 4u * t;
@@ -170,7 +138,7 @@ __global__ __launch_bounds__(256) void nj_best_kernel(const uint32_t *__restrict
   if (t == 0) {
     for (uint32_t w = 1; w < 4; ++w) take_min(bk, bj, s_k[w], s_j[w]);
     row_j[i] = bj;
-    row_q[i] = bj != NJ_NONE ? bk - r[i] : 0;
+    row_q[i] = bj != DENSE_NONE ? bk - r[i] : 0;
   }
 }
 
@@ -184,10 +152,10 @@ __global__ __launch_bounds__(PICK_LANES) void nj_pick_kernel(const uint32_t *__r
   __shared__ uint32_t s_i[PICK_LANES / 64];
   const uint32_t t = threadIdx.x;
   int64_t bk = INT64_MAX;
-  uint32_t bi = NJ_NONE;
+  uint32_t bi = DENSE_NONE;
   for (uint32_t i = t; i < n; i += PICK_LANES) {
-    const bool counts = live[i] != 0u && row_j[i] != NJ_NONE;
-    take_min(bk, bi, counts ? row_q[i] : INT64_MAX, counts ? i : NJ_NONE);
+    const bool counts = live[i] != 0u && row_j[i] != DENSE_NONE;
+    take_min(bk, bi, counts ? row_q[i] : INT64_MAX, counts ? i : DENSE_NONE);
   }
   for (int d = 32; d >= 1; d >>= 1) {
     const int64_t yk = (int64_t)__shfl_xor((long long)bk, d);
@@ -198,8 +166,8 @@ __global__ __launch_bounds__(PICK_LANES) void nj_pick_kernel(const uint32_t *__r
   __syncthreads();
   if (t == 0) {
     for (uint32_t w = 1; w < PICK_LANES / 64; ++w) take_min(bk, bi, s_k[w], s_i[w]);
-    hg_nj_join out{NJ_NONE, NJ_NONE, 0, 0};  // (never written with c >= 2 live names: a pair exists)
-    if (bi != NJ_NONE) {
+    hg_nj_join out{DENSE_NONE, DENSE_NONE, 0, 0};  // (never written with c >= 2 live names: a pair exists)
+    if (bi != DENSE_NONE) {
       const uint32_t a = bi, b = row_j[a];
       const uint32_t D = M[(size_t)a * ld + b];
       const int64_t len_a = c == 2u ? (int64_t)D : hg_nj_len_a(c, D, r[a], r[b]);
@@ -260,12 +228,7 @@ hg_status nj_begin(hg_ctx *c, size_t n, Nj &g, MatrixHold &hold) {
   g.r = static_cast<int64_t *>(c->w_nj.p);
   g.row_q = g.r + g.ld;
   g.live = reinterpret_cast<uint32_t *>(g.row_q + g.ld), g.row_j = g.live + g.ld;
-  const size_t bytes = n * g.ld * sizeof(uint32_t);
-  const hipError_t e = hipMalloc(&hold.p, bytes);
-  if (e != hipSuccess) {
-    hold.p = nullptr;
-    return hg_fail(c, HG_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + ") for the matrix of neighbour joining: " + hipGetErrorString(e));
-  }
+  if ((s = hg_matrix_alloc(c, hold, n * g.ld * sizeof(uint32_t), "neighbour joining")) != HG_OK) return s;
   g.M = static_cast<uint32_t *>(hold.p);
   hg_timed tm(c, HG_T_DIST);
   hipLaunchKernelGGL(nj_init_kernel, dim3(grid_for(c, g.ld)), dim3(256), 0, c->stream, g.live, g.row_j, (uint32_t)n, (uint32_t)g.ld);
@@ -275,22 +238,16 @@ hg_status nj_begin(hg_ctx *c, size_t n, Nj &g, MatrixHold &hold) {
 
 // rows [r0, r0 + rows) from a block of ANI values (nj_fill_kernel)
 hg_status nj_fill(hg_ctx *c, const Nj &g, const float *blk, size_t pitch, size_t c0, size_t r0, size_t rows, size_t n) {
-  hg_timed tm(c, HG_T_DIST);
-  const dim3 grid((unsigned)std::min<size_t>((g.ld + 255) / 256, 64), (unsigned)std::min<size_t>(rows, 16384));
-  hipLaunchKernelGGL(nj_fill_kernel, grid, dim3(256), 0, c->stream, blk, pitch, (uint32_t)c0, (uint32_t)r0, (uint32_t)rows, (uint32_t)n, g.ld,
-                     g.M);
-  HG_HIP(c, hipGetLastError());
-  return HG_OK;
+  return hg_matrix_fill<uint32_t>(c, nj_fill_kernel, g.M, g.ld, blk, pitch, c0, r0, rows, n);
 }
 
 // the filled upper triangle -> mirror, r(), n - 2 rounds and the last join, all queued; final on return
 hg_status nj_resolve(hg_ctx *c, Nj &g, size_t n, hg_nj_join *d_joins, size_t *n_joins) {
   const uint32_t m = (uint32_t)n;
+  const hg_status s = hg_matrix_mirror<uint32_t>(c, nj_mirror_kernel, g.M, n, g.ld);
+  if (s != HG_OK) return s;
   {
     hg_timed tm(c, HG_T_DIST);
-    const unsigned tiles = (unsigned)((n + MIRROR_TILE - 1) / MIRROR_TILE);
-    hipLaunchKernelGGL(nj_mirror_kernel, dim3(tiles, tiles), dim3(MIRROR_TILE, 8), 0, c->stream, g.M, m, g.ld);
-    HG_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(nj_rsum_kernel, dim3(m), dim3(256), 0, c->stream, g.M, g.ld, g.r);
     HG_HIP(c, hipGetLastError());
     const dim3 row_grid(m), node_grid(grid_for(c, n));
@@ -332,24 +289,14 @@ extern "C" hg_status hg_nj_dev(hg_ctx *c, const int16_t *d_hv, const int32_t *d_
   hg_status s = nj_check(c, n, n_joins, true, &done);
   if (s != HG_OK || done) return s;
   if (!d_hv || !d_norm2 || !d_joins) return hg_fail(c, HG_ERR_INVALID, "NULL argument");
-  if (hv_d == 0 || hv_d > 65536) return hg_fail(c, HG_ERR_UNSUPPORTED, "hv_d must be in 1..65536");
-  if (ksize == 0) return hg_fail(c, HG_ERR_INVALID, "ksize must be >= 1");
+  if ((s = hg_sketch_dims_check(c, hv_d, ksize)) != HG_OK) return s;
   HG_ENTER(c);
-  // the scratch block: rows [r0, r0 + rb) x columns [r0, n) of the ANI matrix, the first block being the widest
-  const size_t fit = std::max<size_t>(1, HG_SEARCH_BLOCK_BYTES / (sizeof(float) * n));
-  const size_t rb = std::min<size_t>(n, c->dbg_nj_block_rows ? (size_t)c->dbg_nj_block_rows : fit);
-  if ((s = hg_ensure(c, c->w_srch_blk, rb * n * sizeof(float))) != HG_OK) return s;
-  auto *blk = static_cast<float *>(c->w_srch_blk.p);
   Nj g{};
   MatrixHold hold;
-  if ((s = nj_begin(c, n, g, hold)) != HG_OK) return s;
-  for (size_t r0 = 0; r0 < n; r0 += rb) {
-    const size_t rows = std::min(rb, n - r0), cols = n - r0;
-    if ((s = hg_dist_full_dev(c, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, rows, d_hv + r0 * (size_t)hv_d, d_norm2 + r0, cols, hv_d, ksize,
-                              blk)) != HG_OK)
-      return s;
-    if ((s = nj_fill(c, g, blk, cols, r0, r0, rows, n)) != HG_OK) return s;
-  }
+  s = hg_matrix_row_blocks(
+      c, d_hv, d_norm2, n, hv_d, ksize, c->dbg_nj_block_rows, true, [&] { return nj_begin(c, n, g, hold); },
+      [&](const float *blk, size_t pitch, size_t c0, size_t r0, size_t rows) { return nj_fill(c, g, blk, pitch, c0, r0, rows, n); });
+  if (s != HG_OK) return s;
   return nj_resolve(c, g, n, d_joins, n_joins);
 }
 
