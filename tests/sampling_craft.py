@@ -2,7 +2,7 @@
 on the host).  Everything is generated from fixed seeds; the only hash function used is the oracle's.
 
 The decision under test is `keep h  <=>  h < threshold` (threshold = (2^64 - 1) // scaled) and the route a kept hash takes in the
-k-mer kernels (hyper-gen_amd/csrc/hg_kmer_kernels.hip): the work item's LDS list of STAGE entries, one global atomic per wave once
+k-mer kernels (hyper-gen_amd/csrc/hg_kmer_hits.h): the work item's LDS list of STAGE entries, one global atomic per wave once
 it overflows (append_hit), quarter-full flushes between tiles when dense_sampling(threshold), the per-genome hit region of
 2 * expect + 1 024 slots (hg_sketch_plan.hip) and the re-run of a genome that overflows it.
 

@@ -1,4 +1,4 @@
-"""The k-mer kernel's first t1ha2 mixup on bounded operands (HG_KS_MUL128_BOUNDED in hg_kmer_kernels.hip), in Python integers.
+"""The k-mer kernel's first t1ha2 mixup on bounded operands (HG_KS_MUL128_BOUNDED in hg_kmer_asm.h), in Python integers.
 
 The stage computes lo64 and s + hi64 of ((s + w0) mod 2^64) * P, where w0 is the k-mer's first eight bytes -- each one of
 "ACGT" -- and s is wave-uniform: the seed with P3 (k = 17..24, seeds below 2^28 only) or the length K with P4 (k = 25..32).
@@ -89,8 +89,11 @@ def test_seed_limit_has_margin_and_the_general_text_is_needed_beyond():
 
 
 def test_source_uses_the_limit_checked_here():
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hyper-gen_amd", "csrc", "hg_kmer_kernels.hip")
-    text = open(src).read()
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hyper-gen_amd", "csrc")
+    text = open(os.path.join(csrc, "hg_kmer_kernels.hip")).read()  # the translation unit: the .hip and the hg_kmer_*.h it includes
+    parts = re.findall(r'#include "(hg_kmer_\w+\.h)"', text)
+    assert parts
+    text += "".join(open(os.path.join(csrc, p)).read() for p in parts)
     m = re.search(r"FIRST_SEED_END\s*=\s*1ull\s*<<\s*(\d+)", text)
     assert m and (1 << int(m.group(1))) == SEED_END
     assert "seed < FIRST_SEED_END" in text and "first_mixup_bounded(P3, FIRST_SEED_END - 1)" in text

@@ -1,4 +1,4 @@
-"""The 128-bit products with P1 and P3 in the k-mer kernels have no carry op (hg_kmer_kernels.hip: mul128_cross_fits).  No
+"""The 128-bit products with P1 and P3 in the k-mer kernels have no carry op (hg_kmer_t1ha2.h: mul128_cross_fits).  No
 operand can set the carry that was removed -- that is arithmetic, checked by the file's static_asserts and by
 test_mul128_carry_free.py -- so what is tested here is the text itself: the asm statements of k = 17..32 (HG_KS_MUL128_NC in
 the P1 stage, in the P3 stage of k >= 25 and in the general first mixup of k <= 24; their register binding, and VCC, which the

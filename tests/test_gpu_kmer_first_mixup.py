@@ -1,4 +1,4 @@
-"""kmer_sample_shared, k = 17..32: the first t1ha2 mixup runs a text that relies on bounded operands (hg_kmer_kernels.hip,
+"""kmer_sample_shared, k = 17..32: the first t1ha2 mixup runs a text that relies on bounded operands (hg_kmer_asm.h,
 HG_KS_MUL128_BOUNDED: staged bytes are ACGT, and the wave-uniform operand -- the seed for k <= 24, K for k >= 25 -- is
 small); for k <= 24 a seed of 2^28 or more takes the general text instead.  Everything here is exact equality with the CPU
 oracle.  With threshold = 2^64 - 1 every k-mer's hash is kept, so whole hash sets are compared.

@@ -4,7 +4,7 @@ edge tile does the arithmetic per lane.  Everything here is exact equality with 
 choice between the two flips, where a wave or a tile ends with the genome, and with non-bases inside interior tiles (the
 packed form must raise the tile's "dirty" flag from the blob's bitmap alone).
 
-Geometry (GeoS in hg_kmer_kernels.hip): 256 lanes x 12 starts are staged (NB_T = 3 072 bases); k <= 21 has a 32-base code
+Geometry (GeoS in hg_kmer_shared.h): 256 lanes x 12 starts are staged (NB_T = 3 072 bases); k <= 21 has a 32-base code
 window and tiles of 254 x 12 = 3 048 starts, k = 22..32 a 48-base window and tiles of 253 x 12 = 3 036 starts (a tile then
 starts at bit 0 or bit 4 of a bitmap byte, alternating); a work item is 9 tiles."""
 import numpy as np

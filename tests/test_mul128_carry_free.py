@@ -1,5 +1,5 @@
-"""The 128-bit products of t1ha2's mixups with P1 and P3 run without a carry op (hg_kmer_kernels.hip: mul128_cross_fits,
-HG_KS_MUL128_NC and the same path of mul128_lo_hiadd).  The schoolbook product sums x0 p1 + x1 p0 + hi32(x0 p0) in 64 bits;
+"""The 128-bit products of t1ha2's mixups with P1 and P3 run without a carry op (hg_kmer_t1ha2.h: mul128_cross_fits and
+that path of mul128_lo_hiadd; hg_kmer_asm.h: HG_KS_MUL128_NC).  The schoolbook product sums x0 p1 + x1 p0 + hi32(x0 p0) in 64 bits;
 for a prime with p0 + p1 < 2^32 that sum cannot reach 2^64, whatever x is, so its carry-out is never set.
 
 Here, in Python integers: the predicate's arithmetic for P0..P6, and the six-instruction sequence restated register by
@@ -14,7 +14,15 @@ M32, M64 = 2**32 - 1, 2**64 - 1
 PRIMES = (0xEC99BF0D8372CAAB, 0x82434FE90EDCEF39, 0xD4F06DB99D67BE4B, 0xBD9CACC22C6E9571,
           0x9C06FAF4D023E3AB, 0xC060724A8424F345, 0xCB5AF53AE3AAAC31)
 P1, P2, P3 = PRIMES[1], PRIMES[2], PRIMES[3]
-SRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hyper-gen_amd", "csrc", "hg_kmer_kernels.hip")
+CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "hyper-gen_amd", "csrc")
+
+
+def unit_text():
+    """the text of the k-mer translation unit: hg_kmer_kernels.hip and the hg_kmer_*.h it includes"""
+    top = open(os.path.join(CSRC, "hg_kmer_kernels.hip")).read()
+    parts = re.findall(r'#include "(hg_kmer_\w+\.h)"', top)
+    assert parts, "hg_kmer_kernels.hip includes its hg_kmer_*.h parts"
+    return top + "".join(open(os.path.join(CSRC, p)).read() for p in parts)
 
 
 def worst_cross_sum(P):
@@ -45,7 +53,7 @@ def true_product(x, P, addend):
 
 
 def test_primes_are_the_kernels():
-    text = open(SRC).read()
+    text = unit_text()
     found = {int(i): int(v, 16) for i, v in re.findall(r"constexpr uint64_t P(\d) = (0x[0-9A-Fa-f]+)ull;", text)}
     assert found == dict(enumerate(PRIMES))
 

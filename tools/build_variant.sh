@@ -1,5 +1,6 @@
 #!/bin/bash
-# Development build of the library with extra flags for ONE translation unit (A/B switches of the kernels).
+# Development build of the library with ONE translation unit compiled apart, with extra flags if any.  The k-mer kernels
+# carry no compile-time A/B switches: the other side of an A/B is this script run in a checkout of the parent commit.
 # usage: tools/build_variant.sh <name> <file.hip> [flags...]   ->   tools/_exp_lib_<name>.so (git-ignored); run with HYPERGEN_LIB=...
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

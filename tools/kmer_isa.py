@@ -109,7 +109,7 @@ def main():
     text = [" ".join(t for _, t in b) for _, b in blocks]
     hash_blocks = [i for i, c in enumerate(cnt) if c["v_mad_u64_u32"] >= 20]
     # copies of the 12-k-mer loop: clean and dirty tiles (their main-path blocks are the same instructions), and both once
-    # more with the first mixup's general text, which seeds of 2^28 and more take (HG_KS_BOUNDED_FIRST); the main path is
+    # more with the first mixup's general text, which seeds of 2^28 and more take (HG_KS_FIRST_FULL_3); the main path is
     # the first copy with the fewest products
     assert len(hash_blocks) in (2 * M, 4 * M), "expected two or four copies of the %d-k-mer loop, found %d hash blocks" % (M, len(hash_blocks))
     copies = [hash_blocks[i:i + M] for i in range(0, len(hash_blocks), M)]

@@ -99,6 +99,7 @@ L += ["", "## the other files", "",
       "| `%s_kmer_traffic.json`, `%s_kmer_ascii_traffic.json`, `%s_dist_traffic.json` | the `roofline.traffic` figures `bench.py` reports | idem |" % (tag, tag, tag),
       "| `%s_kmer_packed_isa.*`, `%s_kmer_isa.*` | static instruction budget of `kmer_sample_shared<21, true, PACKED>` by class, per k-mer | `tools/kmer_isa.py %s [packed]` |" % (tag, tag, tag),
       # (rows of single changes name their own files, like the r06 .. r01 rows below: `tag` is the round of the full profile set)
+      "| `kmer_refactor_device_code.txt`, `r13_kmer_packed_isa.*`, `r13_kmer_isa.*` | the k-mer translation unit cut into `hg_kmer_kernels.hip` + six `hg_kmer_*.h`, settled switches out: all 194 kernels against the parent commit's, instruction text and resource figures, what had to be written how for that, and the static budgets of this tree (equal to r12's) | `hipcc --cuda-device-only -S` of `hg_kmer_kernels.hip` in both trees (method in the file), `tools/kmer_isa.py r13 [packed]` |",
       "| `r12_kmer_ab.txt`, `r12_kmer_packed_isa.*`, `r12_kmer_isa.*` | no carry op in the 128-bit products with P1 and P3 (`mul128_cross_fits`): the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32, and k = 21 with a seed of 2^28, `SQ_INSTS_VALU` at k = 21 and 32, bench line), the register table, and the static budgets | `tools/kmer_time.py [--seed]`, `tools/kmer_isa.py r12 [packed]` |",
       *(["| `r12_kernel_stats.csv`, `r12_rocprofv3_kernel_stats_full.csv`, `r12_pmc.json`, `r12_derived.md`, `r12_kmer_traffic.json`, `r12_kmer_ascii_traffic.json` | the bench command's kernel stats and counters on the sources of that change (the k-mer kernel's `roofline.valu_issue` and `roofline.traffic` in `bench.py`; no dist-only run: the dist figures stay r06's) | `tools/profile_gpu.sh r12`, `tools/derive_prof.py r12` |"] if os.path.exists(os.path.join(P, "r12_pmc.json")) else []),
       "| `r11_kmer_ab.txt`, `r11_kmer_packed_isa.*`, `r11_kmer_isa.*` | first t1ha2 mixup of `kmer_sample_shared` (k = 17..32) on bounded operands: the parent commit's library against the change's, alternated (kernel time at k = 21 in both input forms, k = 32, and k = 21 with a seed of 2^28 that takes the general text, `SQ_INSTS_VALU`, bench line), the register table, and the static budgets | `tools/kmer_time.py [--seed]`, `tools/kmer_isa.py r11 [packed]` |",
