@@ -576,6 +576,78 @@ def rec_read_text(path):
     return _read_file(lib_rec().hg_rec_read_text, lib().hg_pinned_free, "hg_rec_read_text", path)
 
 
+# ---- libhypergen_frag.so (include/hypergen_frag.h): fragment-wise ANI and aligned fraction ----
+FRAG_LIB_PATH = os.path.join(_HERE, "libhypergen_frag.so")
+FRAG_EXPORTS = [
+    "hg_frag_plan", "hg_frag_sketch_seq_dev", "hg_frag_ani_matrix_dev", "hg_frag_ani_dev", "hg_frag_ani", "hg_frag_row_chunk",
+    "hg_frag_col_tile", "hg_frag_wave", "hg_frag_fold_threads", "hg_frag_kernel_names", "hg_frag_launch_counts",
+]
+FRAG_PAIR_DTYPE = np.dtype([("sum", np.uint64), ("matched", np.uint32), ("total", np.uint32)])  # hg_frag_pair
+FRAG_BEST_DTYPE = np.dtype([("m", np.uint32), ("row", np.uint32)])  # hg_frag_best
+FRAG_NONE = 0xFFFFFFFF
+FRAG_ROWS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p)
+
+
+@functools.lru_cache(None)
+def lib_frag():
+    """The fourth companion library, loaded behind lib() like lib_aa()."""
+    lib()
+    vp, sz, u64 = C.c_void_p, C.c_size_t, C.c_uint64
+    sig = {
+        "hg_frag_plan": (C.c_int, [u64, u64, u64, vp, vp, sz, C.POINTER(sz)]),
+        "hg_frag_sketch_seq_dev": (C.c_int, [vp, vp, u64, C.POINTER(SketchParams), u64, u64, FRAG_ROWS_FN, vp, C.POINTER(sz)]),
+        "hg_frag_ani_matrix_dev": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, sz, C.c_float, vp, vp]),
+        "hg_frag_ani_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, sz, C.c_float, sz, vp, vp]),
+        "hg_frag_ani": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, sz, vp, sz, C.c_float, vp, vp]),
+        "hg_frag_row_chunk": (C.c_uint32, []),
+        "hg_frag_col_tile": (C.c_uint32, []),
+        "hg_frag_wave": (C.c_uint32, []),
+        "hg_frag_fold_threads": (C.c_uint32, []),
+        "hg_frag_kernel_names": (C.c_char_p, []),
+        "hg_frag_launch_counts": (C.c_uint32, [vp, C.c_uint32]),
+    }
+    return _load("libhypergen_frag.so", FRAG_LIB_PATH, sig, FRAG_EXPORTS)
+
+
+def frag_plan(length, window, step, cap=None):
+    """hg_frag_plan (needs no GPU): (status, n, starts, lens); without a capacity a first call sizes the arrays"""
+    n = C.c_size_t(0)
+    if cap is None:
+        st = lib_frag().hg_frag_plan(length, window, step, None, None, 0, C.byref(n))
+        if st != ERR_CAPACITY:
+            return st, int(n.value), np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        cap = int(n.value)
+    starts, lens = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+    st = lib_frag().hg_frag_plan(length, window, step, _ptr(starts) if cap else None, _ptr(lens) if cap else None, cap, C.byref(n))
+    return st, int(n.value), starts, lens
+
+
+def frag_geometry():
+    """dict of hg_frag_row_chunk, hg_frag_col_tile, hg_frag_wave and hg_frag_fold_threads"""
+    L = lib_frag()
+    return {"row_chunk": int(L.hg_frag_row_chunk()), "col_tile": int(L.hg_frag_col_tile()), "wave": int(L.hg_frag_wave()),
+            "fold_threads": int(L.hg_frag_fold_threads())}
+
+
+def frag_kernel_names():
+    """hg_frag_kernel_names: the library's kernels as rocprofv3 spells them, in launch order"""
+    return lib_frag().hg_frag_kernel_names().decode().split("\n")
+
+
+def frag_launch_counts():
+    """hg_frag_launch_counts: {kernel name: launches of this process so far}"""
+    names = frag_kernel_names()
+    counts = np.zeros(len(names), np.uint64)
+    assert lib_frag().hg_frag_launch_counts(_ptr(counts), counts.size) == len(names)
+    return dict(zip(names, (int(x) for x in counts)))
+
+
+def _frag_offsets(first):
+    """genome offsets as the uint32 array the library reads, and the number of genomes"""
+    a = np.ascontiguousarray(first, np.uint32)
+    return a, max(a.size - 1, 0)
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -799,6 +871,58 @@ class Context:
         n2 = np.concatenate(got["n2"]) if got["n2"] else np.zeros(0, np.int32)
         nh = np.concatenate(got["nh"]) if got["nh"] else np.zeros(0, np.uint32)
         return got["recs"], which, hv, n2, nh
+
+    # ---- fragment-wise ANI and aligned fraction (libhypergen_frag.so) --------------------------
+    def frag_sketch_seq_dev(self, d_seq, n_bps, params, window, step):
+        """hg_frag_sketch_seq_dev on a device pointer (int): (starts, lens, hv, norm2, nhash) of the planned windows, in order"""
+        got = {"starts": [], "lens": [], "hv": [], "n2": [], "nh": [], "next": 0}
+
+        def rows(user, starts, lens, first, m, hv, n2, nh):
+            if first != got["next"]:
+                return 1
+            got["next"] += m
+            got["starts"].append(np.frombuffer(C.string_at(starts, m * 8), np.uint64).copy())
+            got["lens"].append(np.frombuffer(C.string_at(lens, m * 8), np.uint64).copy())
+            got["hv"].append(np.frombuffer(C.string_at(hv, m * params.hv_d * 2), np.int16).reshape(m, params.hv_d).copy())
+            got["n2"].append(np.frombuffer(C.string_at(n2, m * 4), np.int32).copy())
+            got["nh"].append(np.frombuffer(C.string_at(nh, m * 4), np.uint32).copy())
+            return 0
+
+        n_windows = C.c_size_t(0)
+        self._ck(lib_frag().hg_frag_sketch_seq_dev(self._h, _ptr(d_seq), n_bps, C.byref(params), window, step, FRAG_ROWS_FN(rows), None,
+                                                   C.byref(n_windows)))
+        assert got["next"] == n_windows.value
+        return tuple(np.concatenate(got[k]) for k in ("starts", "lens", "hv", "n2", "nh"))
+
+    def frag_ani_matrix_dev(self, d_ani, R, Q, ref_first, qry_first, frag_th, d_pair, d_best=None, allow=()):
+        """hg_frag_ani_matrix_dev on device pointers (ints); the offsets are host arrays of n + 1 entries.  Returns the status."""
+        rf, n_ref = _frag_offsets(ref_first)
+        qf, n_qry = _frag_offsets(qry_first)
+        return self._ck(lib_frag().hg_frag_ani_matrix_dev(self._h, _ptr(d_ani), R, Q, _ptr(rf) if rf.size else None, n_ref,
+                                                          _ptr(qf) if qf.size else None, n_qry, frag_th, _ptr(d_pair),
+                                                          _ptr(d_best) if d_best is not None else None), allow=allow)
+
+    def frag_ani_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, ref_first, qry_first, frag_th, d_pair, d_best=None, block_rows=0,
+                     allow=()):
+        """hg_frag_ani_dev on device pointers (ints), under the ctx's ANI metric.  Returns the status."""
+        rf, n_ref = _frag_offsets(ref_first)
+        qf, n_qry = _frag_offsets(qry_first)
+        return self._ck(lib_frag().hg_frag_ani_dev(self._h, _ptr(d_ref), _ptr(d_rn), R, _ptr(d_qry), _ptr(d_qn), Q, hv_d, ksize,
+                                                   _ptr(rf) if rf.size else None, n_ref, _ptr(qf) if qf.size else None, n_qry, frag_th,
+                                                   block_rows, _ptr(d_pair), _ptr(d_best) if d_best is not None else None), allow=allow)
+
+    def frag_ani(self, ref_hv, ref_n2, qry_hv, qry_n2, ref_first, qry_first, frag_th, ksize=21, want_best=True):
+        """hg_frag_ani, host arrays in and out: (pair records [n_ref, n_qry], best records [n_ref, Q] or None)"""
+        r, q = np.ascontiguousarray(ref_hv, np.int16), np.ascontiguousarray(qry_hv, np.int16)
+        rn, qn = np.ascontiguousarray(ref_n2, np.int32), np.ascontiguousarray(qry_n2, np.int32)
+        rf, n_ref = _frag_offsets(ref_first)
+        qf, n_qry = _frag_offsets(qry_first)
+        pair = np.zeros((n_ref, n_qry), FRAG_PAIR_DTYPE)
+        best = np.zeros((n_ref, q.shape[0]), FRAG_BEST_DTYPE) if want_best else None
+        self._ck(lib_frag().hg_frag_ani(self._h, _ptr(r), _ptr(rn), r.shape[0], _ptr(q), _ptr(qn), q.shape[0], r.shape[1], ksize,
+                                        _ptr(rf) if rf.size else None, n_ref, _ptr(qf) if qf.size else None, n_qry, frag_th,
+                                        _ptr(pair), _ptr(best) if want_best else None))
+        return pair, best
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):
         r = np.ascontiguousarray(ref_hv, np.int16)

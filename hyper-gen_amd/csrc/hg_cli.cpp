@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <atomic>
 #include <bitset>
+#include <cctype>
 #include <cerrno>
 #include <chrono>
 #include <condition_variable>
@@ -33,6 +34,7 @@
 
 #include "../../include/hypergen.h"
 #include "../../include/hypergen_aa.h"
+#include "../../include/hypergen_frag.h"
 #include "../../include/hypergen_rec.h"
 #include "../../include/hypergen_tx.h"
 
@@ -91,6 +93,13 @@ struct Cli {
   bool individual = false;   // --individual (sketch): one sketch per FASTA record of every file, the files split on the device (hypergen_rec.h); parse's own too
   unsigned long long min_length = 0;  // --min_length N (sketch --individual): leave out records with fewer than N sequence bytes
   bool min_length_given = false;
+  unsigned long long fragment = 0, fragment_step = 0;  // --fragment W [--fragment_step S] (sketch): one sketch per window of W bases every S [W] bases of every file (hypergen_frag.h); parse's own too
+  bool fragment_given = false, fragment_step_given = false;
+  bool fragments = false;            // --fragments (dist): fragment-wise ANI and aligned fraction per pair of genomes (hypergen_frag.h); parse's own, like the three below
+  float fragment_ani = 90.0f;        // --fragment_ani T (dist --fragments): a fragment counts as matched from this ANI of its best window on
+  unsigned long long min_fragments = 1;  // --min_fragments N (dist --fragments): pairs with fewer matched fragments are not written
+  std::string fragment_hits;         // --fragment_hits FILE (dist --fragments): one line per matched (reference genome, query fragment)
+  bool fragment_ani_given = false, min_fragments_given = false, fragment_hits_given = false;
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
@@ -325,7 +334,24 @@ void print_dist_help() {
               "         inside doubled; the tree is unrooted, its top level has three children; branch lengths are substitutions\n"
               "         per site, 1 - ANI / 100, with eight decimals, and may be negative, as neighbour joining leaves them\n"
               "         (nothing is clamped).  -o is what it is without --newick.  It needs --ani_metric mash or\n"
-              "         max_containment and does not go with --pairs or --shards.\n");
+              "         max_containment and does not go with --pairs or --shards.\n"
+              "dist --fragments [--fragment_ani T] [--min_fragments N] [--fragment_hits FILE]: the ANI over the shared part of two\n"
+              "         genomes and how much of them is shared, as FastANI, skani and GTDB's species rule (ANI >= 95 and aligned\n"
+              "         fraction >= 0.5) report them.  -r and -q are sketch files written with sketch --fragment: consecutive\n"
+              "         records whose names differ only in a final :start-end are the fragments of one genome, a record without\n"
+              "         that suffix is a genome of one fragment, and a genome whose records are not consecutive is an error.\n"
+              "         Every query fragment keeps its best window in every reference genome; it is matched when that ANI is at\n"
+              "         least --fragment_ani T [90].  At the default -d 4096 the best of a genome's unrelated windows reads as an\n"
+              "         ANI near 87 whatever -s is: fragment hits below about 88 are noise, keep T above that.  --ani_metric is\n"
+              "         containment unless it is given: the share of the fragment's hashes found in the window.  One line per\n"
+              "         (reference genome, query genome) with at least --min_fragments N [1] matched fragments and a genome ANI of\n"
+              "         at least -a, ordered by query, then reference, in file order: reference, query, ANI, matched fragments,\n"
+              "         all fragments of the query.  The ANI is the mean of the matched fragments' bests, every one counted as\n"
+              "         dist prints it, in thousandths; the aligned fraction is matched / all.  With -r and -q naming one file\n"
+              "         every ordered pair is written, a genome with itself too.  --fragment_hits FILE writes one line per matched\n"
+              "         (reference genome, query fragment), ordered by query fragment, then reference genome: name of the\n"
+              "         fragment, name of its best window, ANI.  It runs on the first visible GPU, block by block (no matrix is\n"
+              "         held), and does not go with --pairs, --columns, --newick or --shards.\n");
 }
 
 // `hyper-gen sketch --help`: the general help with a paragraph on --alphabet behind it
@@ -366,7 +392,16 @@ void print_sketch_help() {
               "         blank, without the file's path; files go in the order sketch reads them, records in file order.  Names\n"
               "         that repeat are kept, a record without an identifier and sequence in front of the first header are\n"
               "         errors.  --min_length N [0] leaves out the records with fewer than N sequence bytes; it needs --individual.\n"
-              "         It does not go with --alphabet protein, with --translate or with --shards.\n");
+              "         It does not go with --alphabet protein, with --translate or with --shards.\n"
+              "sketch --fragment W [--fragment_step S]: one sketch per window of W bases of every file's merged sequence, a window\n"
+              "         starting every S bases [W]: the fragments that dist --fragments compares, as FastANI and skani cut them.\n"
+              "         W and S are multiples of 4, S is at most W and W at least -k.  A sequence of up to W bases is one window;\n"
+              "         a last window shorter than W / 2 is dropped, which cannot happen with S up to W / 2.  Cut the query side\n"
+              "         with --fragment L and the reference side with --fragment 2L --fragment_step L: every colinear stretch of L\n"
+              "         bases then lies whole inside one reference window.  The name of a record is file:start-end, 1-based and\n"
+              "         inclusive, in the merged sequence; everything else in it is what sketch writes.  Every file goes to the\n"
+              "         first visible GPU once and its windows are sketched from that one copy.  It does not go with\n"
+              "         --individual, with --alphabet protein, with --translate or with --shards.\n");
 }
 
 // what --translate and --alphabet protein (`opt`; its input is `input`) have in common: neither goes with --min_count or
@@ -437,6 +472,33 @@ Cli parse(int argc, char **argv) {
       c.min_length_given = true;
       continue;
     }
+    if (a.flag == "--fragments") {  // dist's own switch, no value
+      c.fragments = true;
+      continue;
+    }
+    // sketch's --fragment / --fragment_step and the three that belong to dist --fragments, read like rows of the table
+    static const char *const own[] = {"fragment", "fragment_step", "fragment_ani", "min_fragments", "fragment_hits"};
+    size_t own_k = 0;
+    for (; own_k < 5; ++own_k)
+      if (a.flag == std::string("--") + own[own_k] || a.flag.rfind(std::string("--") + own[own_k] + "=", 0) == 0) break;
+    if (own_k < 5) {
+      a.name = own[own_k];
+      const size_t nl = std::strlen(a.name) + 2;
+      if (a.flag.size() > nl) a.val = a.flag.substr(nl + 1);
+      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
+      else a.val = argv[++i];
+      a.flag = std::string("--") + a.name;
+      if (own_k == 0) c.fragment = a.uint(~0ull), c.fragment_given = true;
+      else if (own_k == 1) c.fragment_step = a.uint(~0ull), c.fragment_step_given = true;
+      else if (own_k == 2) {
+        char *end = nullptr;
+        c.fragment_ani = std::strtof(a.val.c_str(), &end);
+        if (a.val.empty() || *end || !(c.fragment_ani >= 0.0f && c.fragment_ani <= 100.0f)) a.bad(" (an ANI, 0 to 100)");
+        c.fragment_ani_given = true;
+      } else if (own_k == 3) c.min_fragments = a.uint(0xFFFFFFFFull, 1), c.min_fragments_given = true;
+      else c.fragment_hits = a.file(), c.fragment_hits_given = true;
+      continue;
+    }
     const Option *o = nullptr;
     bool have_val = false;
     if (a.flag.rfind("--", 0) == 0) {
@@ -477,6 +539,16 @@ Cli parse(int argc, char **argv) {
     die("--individual is not supported by " + c.mode + ": it splits the FASTA files sketch reads into their records");
   if (c.min_length_given && c.mode_bit != SKETCH)
     die("--min_length is not supported by " + c.mode + ": it belongs to sketch --individual");
+  if ((c.fragment_given || c.fragment_step_given) && c.mode_bit != SKETCH)
+    die(std::string(c.fragment_given ? "--fragment" : "--fragment_step") + " is not supported by " + c.mode + ": it cuts the sequences sketch reads into windows");
+  if (c.fragments && c.mode_bit != DIST)
+    die("--fragments is not supported by " + c.mode + ": it makes dist compare genomes fragment by fragment");
+  const std::pair<bool, const char *> of_fragments[] = {{c.fragment_ani_given, "--fragment_ani"}, {c.min_fragments_given, "--min_fragments"},
+                                                        {c.fragment_hits_given, "--fragment_hits"}};
+  for (const auto &o : of_fragments) {
+    if (o.first && c.mode_bit != DIST) die(std::string(o.second) + " is not supported by " + c.mode + ": it belongs to dist --fragments");
+    if (o.first && !c.fragments) die(std::string(o.second) + " needs --fragments: without it dist compares whole sketches");
+  }
   // what an option needs of the others
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
@@ -516,6 +588,26 @@ Cli parse(int argc, char **argv) {
   }
   if (c.min_length_given && !c.individual) die("--min_length needs --individual: without it sketch makes one sketch per file, whatever its length");
   if (c.protein) amino_acid_mode(c, "--alphabet protein", "protein");  // (Mash's protein default for k)
+  if (c.fragment_step_given && !c.fragment_given) die("--fragment_step needs --fragment: without it sketch makes one sketch per file");
+  if (c.fragment_given) {
+    if (c.individual) die("--fragment is not supported with --individual: the windows are cut from a file's merged sequence, not from its records");
+    if (c.protein) die("--fragment is not supported with --alphabet protein: protein input is sketched one file at a time");
+    if (c.translate) die("--fragment is not supported with --translate: translated input is sketched one file at a time");
+    if (c.shards) die("--shards is not supported with --fragment: the windows are sketched on the first visible GPU");
+    if (!c.fragment_step_given) c.fragment_step = c.fragment;
+    if (c.fragment == 0 || c.fragment % 4) die("invalid value '" + std::to_string(c.fragment) + "' for '--fragment': a window is a multiple of 4 bases, at least 4");
+    if (c.fragment_step == 0 || c.fragment_step % 4)
+      die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step is a multiple of 4 bases, at least 4");
+    if (c.fragment_step > c.fragment) die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step above the window would leave bases out");
+    if (c.fragment < c.ksize) die("invalid value '" + std::to_string(c.fragment) + "' for '--fragment': a window shorter than -k holds no k-mer");
+  }
+  if (c.fragments) {
+    if (given(c, "pairs")) die("--pairs is not supported with --fragments: every pair of genomes is compared");
+    if (given(c, "columns")) die("--columns is not supported with --fragments: a line carries the fragment ANI, the matched and the total fragments");
+    if (given(c, "newick")) die("--newick is not supported with --fragments: the tree is drawn from whole sketches");
+    if (c.shards) die("--shards is not supported with --fragments: it runs on the first visible GPU");
+    if (!given(c, "ani_metric")) c.ani_metric = HG_ANI_CONTAINMENT;  // the share of a fragment found in its best window
+  }
   return c;
 }
 
@@ -617,6 +709,7 @@ void finish_sketch(const Cli &c, double t0, const std::string &head, const char 
 
 int run_sketch_batches(const Cli &c, const std::vector<std::string> &files);
 int run_sketch_individual(const Cli &c, const std::vector<std::string> &files);
+int run_sketch_fragments(const Cli &c, const std::vector<std::string> &files);
 
 int run_sketch(const Cli &c) {
   if (c.path == "1" && c.out.empty()) die("the following required arguments were not provided: --path --out");
@@ -624,6 +717,7 @@ int run_sketch(const Cli &c) {
   if (c.protein) return run_sketch_batches(c, fasta_files(c.path, {"*.faa"}));
   if (c.translate) return run_sketch_batches(c, fasta_files(c.path));
   if (c.individual) return run_sketch_individual(c, fasta_files(c.path));
+  if (c.fragment_given) return run_sketch_fragments(c, fasta_files(c.path));
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -890,6 +984,51 @@ int run_sketch_individual(const Cli &c, const std::vector<std::string> &files) {
   char note[128] = "";
   if (n < n_total) std::snprintf(note, sizeof note, "%zu records shorter than %llu were left out", n_total - n, c.min_length);
   finish_sketch(c, t0, "Sketching " + std::to_string(n) + " records of " + std::to_string(files.size()) + " files", "records", rows.out, note);
+  hg_ctx_destroy(ctx);
+  return 0;
+}
+
+// sketch --fragment W [--fragment_step S]: every file's merged sequence goes to the first visible GPU once (the reader and
+// the parameters are run_sketch's), hg_frag_sketch_seq_dev sketches its windows from that one copy in sub-batches, and the
+// rows come back through take_windows, which packs them.  A record's file_str is file:start-end, 1-based and inclusive.
+struct FragmentRows {
+  const std::string *file;
+  SketchRecords out;
+};
+int take_windows(void *user, const uint64_t *starts, const uint64_t *lens, size_t, size_t m, const int16_t *hv, const int32_t *n2, const uint32_t *) {
+  FragmentRows &o = *static_cast<FragmentRows *>(user);
+  const Cli &c = o.out.c;
+  for (size_t k = 0; k < m; ++k)
+    o.out.put(o.out.recs.size(), hv + k * c.hv_d, n2[k], *o.file + ":" + std::to_string(starts[k] + 1) + "-" + std::to_string(starts[k] + lens[k]),
+              c.canonical);
+  return 0;
+}
+
+int run_sketch_fragments(const Cli &c, const std::vector<std::string> &files) {
+  logline("INFO", "Start sketching...");
+  const double t0 = now_s();
+  const hg_sketch_params p = sketch_params(c, false);  // (run_sketch's reading of -C and -D)
+  const uint32_t read_mode = c.device == "gpu" ? HG_READ_MERGE : HG_READ_NEEDLETAIL;
+  if (hg_device_count() <= 0) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+  hg_ctx *ctx = nullptr;
+  if (hg_ctx_create(0, &ctx) != HG_OK) die(std::string("no MI355X device: ") + hg_last_error(nullptr));
+
+  FragmentRows rows{nullptr, SketchRecords(c)};
+  uint8_t *seq = nullptr;
+  size_t cap = 0;
+  for (const std::string &file : files) {
+    size_t n = 0;
+    if (hg_read_fastx_pinned(file.c_str(), read_mode, &seq, &cap, &n) != HG_OK) die("Opening .fna files failed: " + file);
+    DevBuf<uint8_t> d_seq(ctx, ((n + 3) & ~(size_t)3) + 64);  // (the 32 readable bytes behind the genome, and room for a whole last dword)
+    if (n) d_seq.upload(seq, n);
+    rows.file = &file;
+    size_t n_windows = 0;
+    const hg_status ss = hg_frag_sketch_seq_dev(ctx, d_seq.get(), n, &p, c.fragment, c.fragment_step, take_windows, &rows, &n_windows);
+    if (ss != HG_OK) die(file + ": " + hg_status_str(ss) + " (" + hg_last_error(ctx) + ")");
+    debugf("%s: %zu bases, %zu windows", file.c_str(), n, n_windows);
+  }
+  hg_pinned_free(seq);
+  finish_sketch(c, t0, "Sketching " + std::to_string(rows.out.recs.size()) + " windows of " + std::to_string(files.size()) + " files", "windows", rows.out);
   hg_ctx_destroy(ctx);
   return 0;
 }
@@ -1221,9 +1360,123 @@ struct Session {
   const Loaded &Q() const { return two ? Q2 : R; }  // the query side: the one file against itself without a second
 };
 
+// The genomes of a sketch file written with sketch --fragment: consecutive records whose names differ only in a final
+// :<digits>-<digits>.  A record without that suffix is a genome of one fragment; a genome whose name reappears behind
+// another one is fatal.
+struct Genomes {
+  std::vector<uint32_t> first;  // n + 1 record offsets
+  std::vector<std::string> name;
+  size_t n() const { return name.size(); }
+};
+std::string genome_of(const char *record) {
+  const std::string s = record;
+  size_t e = s.size(), d = e;
+  while (d && std::isdigit((unsigned char)s[d - 1])) --d;
+  if (d == e || !d || s[d - 1] != '-') return s;
+  size_t b = d - 1;
+  while (b && std::isdigit((unsigned char)s[b - 1])) --b;
+  if (b == d - 1 || b < 2 || s[b - 1] != ':') return s;  // (a name that is nothing but the suffix stays whole)
+  return s.substr(0, b - 1);
+}
+Genomes genomes_of(const Loaded &L, const std::string &path) {
+  Genomes G;
+  std::map<std::string, bool> seen;
+  for (size_t i = 0; i < L.n; ++i) {
+    const char *record = hg_sketch_file_get(L.f, i)->file_str;
+    std::string g = genome_of(record);
+    if (!G.name.empty() && g == G.name.back()) continue;
+    if (!seen.emplace(g, true).second)
+      die(path + ": genome '" + g + "' reappears at record '" + record + "' behind another genome: the fragments of a genome must be consecutive");
+    G.first.push_back((uint32_t)i), G.name.push_back(std::move(g));
+  }
+  G.first.push_back((uint32_t)L.n);
+  return G;
+}
+
+void dump_text(const std::string &path, const std::string &text, const char *failed) {
+  FILE *f = std::fopen(path.c_str(), "wb");
+  const bool bad = !f || std::fwrite(text.data(), 1, text.size(), f) != text.size();
+  if ((f && std::fclose(f) != 0) || bad) die(failed);
+}
+std::string milli_str(uint64_t v) {  // thousandths with exactly three decimals
+  char buf[32];
+  std::snprintf(buf, sizeof buf, "%llu.%03llu", (unsigned long long)(v / 1000), (unsigned long long)(v % 1000));
+  return buf;
+}
+uint64_t milli_of(float ani) {  // the integer dist prints for an ANI (put_ani), which is the library's m
+  if (!(ani >= 0.0f)) ani = 0.0f;
+  if (ani > 100.0f) ani = 100.0f;
+  return (uint64_t)__builtin_rint((double)ani * 1000.0);
+}
+
+// dist --fragments: the sketches of -r are reference windows, those of -q query fragments; hg_frag_ani_dev reduces the
+// (windows x fragments) matrix, block by block on the first visible GPU, to one record per pair of genomes -- and with
+// --fragment_hits to every fragment's best window per reference genome.  Everything printed is an integer of thousandths.
+int run_dist_fragments(const Cli &c) {
+  const double t0 = now_s();
+  const bool sym = c.path_r == c.path_q;
+  Session s(1, c.ani_metric, c.path_r, sym ? nullptr : &c.path_q);
+  const Loaded &R = s.R, &Q = s.Q();
+  const Genomes gr = genomes_of(R, c.path_r), gq = sym ? gr : genomes_of(Q, c.path_q);
+  to_devices(s.multi, R, s.dR);
+  if (!sym) to_devices(s.multi, Q, s.dQ);
+  const DevSet &dq = sym ? s.dR : s.dQ;
+  logline("INFO", "Computing fragment ANI..");
+  hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+  const size_t n_ref = gr.n(), n_qry = gq.n();
+  const bool want_hits = c.fragment_hits_given;
+  std::vector<hg_frag_pair> pair(n_ref * n_qry);
+  std::vector<hg_frag_best> best(want_hits ? n_ref * Q.n : 0);
+  {
+    DevBuf<hg_frag_pair> d_pair(ctx, pair.size());
+    DevBuf<hg_frag_best> d_best(ctx);
+    if (want_hits) d_best.alloc(best.size());
+    ck(ctx, hg_frag_ani_dev(ctx, s.dR.hv[0], s.dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize, gr.first.data(), n_ref,
+                            gq.first.data(), n_qry, c.fragment_ani, 0, d_pair.get(), want_hits ? d_best.get() : nullptr), "fragment ANI");
+    d_pair.download(pair.data(), pair.size());
+    if (want_hits) d_best.download(best.data(), best.size());
+  }
+  const uint64_t a_milli = milli_of(c.ani_th), m_th = milli_of(c.fragment_ani);
+  std::string text;
+  size_t lines = 0;
+  for (size_t h = 0; h < n_qry; ++h)
+    for (size_t g = 0; g < n_ref; ++g) {
+      const hg_frag_pair &p = pair[g * n_qry + h];
+      if (!p.matched || p.matched < c.min_fragments) continue;
+      const uint64_t ani = (2 * p.sum + p.matched) / (2ull * p.matched);
+      if (ani < a_milli) continue;
+      text += gr.name[g] + "\t" + gq.name[h] + "\t" + milli_str(ani) + "\t" + std::to_string(p.matched) + "\t" + std::to_string(p.total) + "\n";
+      ++lines;
+    }
+  dump_text(c.out, text, "Dump ANI file failed!");
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "Output %zu of %zu genome pairs with at least %llu fragments at %.1f and ANI above %.1f to file %s", lines,
+                n_ref * n_qry, c.min_fragments, c.fragment_ani, c.ani_th, c.out.c_str());
+  logline("INFO", buf);
+  if (want_hits) {
+    text.clear();
+    size_t hits = 0;
+    for (size_t q = 0; q < Q.n; ++q)
+      for (size_t g = 0; g < n_ref; ++g) {
+        const hg_frag_best &b = best[g * Q.n + q];
+        if (b.row == HG_FRAG_NONE || b.m < m_th) continue;
+        text += std::string(hg_sketch_file_get(Q.f, q)->file_str) + "\t" + hg_sketch_file_get(R.f, b.row)->file_str + "\t" + milli_str(b.m) + "\n";
+        ++hits;
+      }
+    dump_text(c.fragment_hits, text, "Dump fragment hits file failed!");
+    std::snprintf(buf, sizeof buf, "Output %zu fragment hits to file %s", hits, c.fragment_hits.c_str());
+    logline("INFO", buf);
+  }
+  std::snprintf(buf, sizeof buf, "Computed fragment ANIs for %zu ref genomes (%zu windows) and %zu query genomes (%zu fragments) took %.3fs", n_ref,
+                R.n, n_qry, Q.n, now_s() - t0);
+  logline("INFO", buf);
+  return 0;
+}
+
 int run_dist(const Cli &c) {
   if (c.path_r == "1" || c.path_q == "1" || c.out.empty())
     die("the following required arguments were not provided: --path_r --path_q --out");
+  if (c.fragments) return run_dist_fragments(c);
   const double t0 = now_s();
   const bool sym = c.path_r == c.path_q;  // src/dist.rs:13
   // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
