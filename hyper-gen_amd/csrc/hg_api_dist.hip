@@ -119,7 +119,9 @@ static hg_status dist_block_once(hg_ctx *c, const int16_t *d_ref_hv, const int32
   // all): statistics-driven schedule
   if (mark == 0u && (spec_cover == -2 || (spec_cover >= 0 && (int)verdict > spec_cover))) {
     c->misc_zeroed = nullptr;
+    const uint32_t skip = c->i8_skip;  // (the rerun is part of this call: it takes nothing off the countdown)
     if ((s = hg_run_dist(c, a)) != HG_OK) return s;
+    c->i8_skip = skip;
     if ((s = hg_publish_words(c, d_count, HG_RES_WORDS, &h_res, HG_RES_WORDS)) != HG_OK) return s;
     c->misc_zeroed = d_count;
   }

@@ -15,7 +15,9 @@
 // run behind them;
 // the tree resolution [5], [6] = roots that selected an edge in the odd / even rounds, [7] = edges of the forest being
 // written, and counts its rounds in [4] too.
-// All are zero between calls: the call that reads them back clears them behind the copy (hg_publish_words).
+// The call that reads them back clears them behind the copy (hg_publish_words), but no entry point may count on finding
+// them zero: an incremental clustering dropped behind hg_cluster_add_hits_dev leaves [1] raised.  Every scheme's init kernel
+// clears the words it uses, and hg_cluster_stats*, which has none, clears its two in front of its first kernel.
 enum : uint32_t {
   HG_CLU_COUNT = 0,
   HG_CLU_ERR = 1,

@@ -209,6 +209,10 @@ hg_status stats_begin(hg_ctx *c, size_t n, const uint32_t *d_cluster, size_t n_c
   if ((s = hg_ensure(c, c->w_cstats, acc_bytes + (d_node ? 0 : n * sizeof(hg_node_stat)) + 64)) != HG_OK) return s;
   g.acc = static_cast<Acc *>(c->w_cstats.p);
   g.node = d_node ? d_node : reinterpret_cast<hg_node_stat *>(static_cast<char *>(c->w_cstats.p) + acc_bytes);
+  // The check kernel only raises the error word, so it has to find it clear, and "zero between calls" does not hold: an
+  // incremental clustering may be dropped behind hg_cluster_add_hits_dev, which leaves the word raised by a hit with an
+  // index >= n.  Cleared here in stream order, not inside the kernel: other lanes of the same launch raise the word.
+  HG_HIP(c, hipMemsetAsync(g.res, 0, 2 * sizeof(uint32_t), c->stream));
   hg_timed tm(c, HG_T_DIST);
   hipLaunchKernelGGL(cluster_stats_check_kernel, dim3(grid_for(c, std::max(n, n_clusters))), dim3(256), 0, c->stream, d_cluster, (uint32_t)n,
                      (uint32_t)n_clusters, g.acc, g.res);
