@@ -88,18 +88,15 @@ struct Cli {
   unsigned long long seed = 123, scaled = 1500, hv_d = 4096;
   float quant_scale = 1.0f, ani_th = 85.0f;  // (cluster's default threshold is 95.0, the other subcommands' 85.0)
   bool protein = false;      // --alphabet dna|protein (sketch): protein = amino-acid k-mers of the *.faa files of -p (hypergen_aa.h)
-  bool alphabet_given = false;  // (taken by parse itself: the option table's size is pinned by tests/test_nj_surface.py)
-  bool translate = false;    // --translate (sketch): amino-acid k-mers of the six reading frames of the nucleotide files (hypergen_tx.h); parse's own too
-  bool individual = false;   // --individual (sketch): one sketch per FASTA record of every file, the files split on the device (hypergen_rec.h); parse's own too
+  // (three switches have no field: --translate (sketch): amino-acid k-mers of the six reading frames of the nucleotide files
+  // (hypergen_tx.h); --individual (sketch): one sketch per FASTA record of every file, the files split on the device
+  // (hypergen_rec.h); --fragments (dist): fragment-wise ANI and aligned fraction per pair of genomes (hypergen_frag.h) --
+  // given(c, "translate") and so on is all there is to know of them)
   unsigned long long min_length = 0;  // --min_length N (sketch --individual): leave out records with fewer than N sequence bytes
-  bool min_length_given = false;
-  unsigned long long fragment = 0, fragment_step = 0;  // --fragment W [--fragment_step S] (sketch): one sketch per window of W bases every S [W] bases of every file (hypergen_frag.h); parse's own too
-  bool fragment_given = false, fragment_step_given = false;
-  bool fragments = false;            // --fragments (dist): fragment-wise ANI and aligned fraction per pair of genomes (hypergen_frag.h); parse's own, like the three below
+  unsigned long long fragment = 0, fragment_step = 0;  // --fragment W [--fragment_step S] (sketch): one sketch per window of W bases every S [W] bases of every file (hypergen_frag.h)
   float fragment_ani = 90.0f;        // --fragment_ani T (dist --fragments): a fragment counts as matched from this ANI of its best window on
   unsigned long long min_fragments = 1;  // --min_fragments N (dist --fragments): pairs with fewer matched fragments are not written
   std::string fragment_hits;         // --fragment_hits FILE (dist --fragments): one line per matched (reference genome, query fragment)
-  bool fragment_ani_given = false, min_fragments_given = false, fragment_hits_given = false;
   unsigned min_count = 1;    // --min_count N (sketch): keep a sampled k-mer only if it occurs at least N times (hg_sketch_params.min_count)
   SearchPath search_path = SearchPath::automatic;  // --search_path auto|hits|topk (search; testing aid)
   int ani_metric = HG_ANI_MASH;  // --ani_metric mash|containment|max_containment (dist / search / cluster; hg_ctx_set_ani_metric)
@@ -113,7 +110,7 @@ struct Cli {
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
   std::string newick_out;         // --newick <file> (dist on one file): the neighbour-joining tree of all its sketches
-  std::bitset<32> given;          // which options the command line carried, by row of `options`
+  std::bitset<64> given;          // which options the command line carried, by row of `options`
 };
 
 // One option of the command line as it was typed, and the ways its value is read
@@ -126,6 +123,10 @@ struct Arg {
     const unsigned long long v = std::strtoull(val.c_str(), &e, 10);
     if (val.empty() || *e || v > max || v < min) die("invalid value '" + val + "' for '" + flag + "'");
     return v;
+  }
+  // the same, a bad value reported under the option's own name, "--thread", however the flag was typed
+  unsigned long long named_uint(unsigned long long max, unsigned long long min = 0) const {
+    return Arg{std::string("--") + name, val, name}.uint(max, min);
   }
   // the place of the value in a fixed list; the error names the list: " (a | b | c)"
   size_t choice(std::initializer_list<const char *> names, bool list_them = true) const {
@@ -173,10 +174,10 @@ void take_columns(Cli &c, const Arg &a) {
   }
 }
 
-// Every option: long name, short letter (0: none), how its value is taken, the subcommands that accept it, why the others do
-// not ("--name is not supported by <mode>: <why>") and why it does not go with --shards (nullptr: it does).  A subcommand that
-// merely ignores an option accepts it, as the reference's one flat argument struct does (src/utils.rs:42-162).  The restricted
-// rows stand in the order their faults are reported in.
+// Every option: long name, short letter (0: none), how its value is taken (nullptr: a switch, it has none), the subcommands that
+// accept it, why the others do not ("--name is not supported by <mode>: <why>") and why it does not go with --shards (nullptr:
+// it does).  A subcommand that merely ignores an option accepts it, as the reference's one flat argument struct does
+// (src/utils.rs:42-162).  The restricted rows stand in the order their faults are reported in.
 struct Option {
   const char *name;
   char letter;
@@ -227,9 +228,26 @@ const Option options[] = {
      "the filter needs the k-mer counts, which a sketch no longer has"},
     // (testing aid: the several-GPU path on fewer GPUs)
     {"shards", 'G', [](Cli &c, const Arg &a) { c.shards = (unsigned)a.uint(64); }, SKETCH | DIST | SEARCH, "it runs on the first visible GPU"},
+    // (sketch's other inputs and dist --fragments; their numbers are reported under the option's name: named_uint)
+    {"alphabet", 0, [](Cli &c, const Arg &a) { c.protein = a.choice({"dna", "protein"}) == 1; }, SKETCH,
+     "it names the alphabet of the sequences sketch reads"},
+    {"translate", 0, nullptr, SKETCH, "it translates the nucleotide sequences sketch reads"},
+    {"individual", 0, nullptr, SKETCH, "it splits the FASTA files sketch reads into their records"},
+    {"min_length", 0, [](Cli &c, const Arg &a) { c.min_length = a.named_uint(~0ull); }, SKETCH, "it belongs to sketch --individual"},
+    {"fragment", 0, [](Cli &c, const Arg &a) { c.fragment = a.named_uint(~0ull); }, SKETCH, "it cuts the sequences sketch reads into windows"},
+    {"fragment_step", 0, [](Cli &c, const Arg &a) { c.fragment_step = a.named_uint(~0ull); }, SKETCH,
+     "it cuts the sequences sketch reads into windows"},
+    {"fragments", 0, nullptr, DIST, "it makes dist compare genomes fragment by fragment"},
+    {"fragment_ani", 0, [](Cli &c, const Arg &a) {
+       char *end = nullptr;
+       c.fragment_ani = std::strtof(a.val.c_str(), &end);
+       if (a.val.empty() || *end || !(c.fragment_ani >= 0.0f && c.fragment_ani <= 100.0f)) a.bad(" (an ANI, 0 to 100)");
+     }, DIST, "it belongs to dist --fragments"},
+    {"min_fragments", 0, [](Cli &c, const Arg &a) { c.min_fragments = a.named_uint(0xFFFFFFFFull, 1); }, DIST, "it belongs to dist --fragments"},
+    {"fragment_hits", 0, [](Cli &c, const Arg &a) { c.fragment_hits = a.file(); }, DIST, "it belongs to dist --fragments"},
 };
 const size_t N_OPTIONS = sizeof options / sizeof options[0];
-static_assert(N_OPTIONS <= 32, "Cli::given has 32 bits");
+static_assert(N_OPTIONS <= decltype(Cli::given)().size(), "Cli::given has a bit per row");
 
 size_t option_row(const char *name) {
   for (size_t k = 0; k < N_OPTIONS; ++k)
@@ -426,78 +444,18 @@ Cli parse(int argc, char **argv) {
     std::exit(0);
   }
   static const char *const modes[] = {"sketch", "dist", "search", "cluster"};
+  unsigned k_mode = 0;
   for (unsigned k = 0; k < 4; ++k)
-    if (c.mode == modes[k]) c.mode_bit = 1u << k;
+    if (c.mode == modes[k]) c.mode_bit = 1u << (k_mode = k);
   if (!c.mode_bit) die("unknown subcommand '" + c.mode + "'");
   if (c.mode_bit != SKETCH) c.method = "fracminhash";
   if (c.mode_bit == CLUSTER) c.ani_th = 95.0f;
   for (int i = 2; i < argc; ++i) {
     Arg a{argv[i], "", nullptr};
-    if (c.mode_bit == CLUSTER && (a.flag == "--help" || a.flag == "-h")) {
-      print_cluster_help();
+    static void (*const help_of[])() = {print_sketch_help, print_dist_help, nullptr, print_cluster_help};  // by subcommand; search has none
+    if (help_of[k_mode] && (a.flag == "--help" || a.flag == "-h")) {
+      help_of[k_mode]();
       std::exit(0);
-    }
-    if (c.mode_bit == DIST && (a.flag == "--help" || a.flag == "-h")) {
-      print_dist_help();
-      std::exit(0);
-    }
-    if (c.mode_bit == SKETCH && (a.flag == "--help" || a.flag == "-h")) {
-      print_sketch_help();
-      std::exit(0);
-    }
-    if (a.flag == "--alphabet" || a.flag.rfind("--alphabet=", 0) == 0) {  // sketch's own option, read like a row of the table
-      a.name = "alphabet";
-      if (a.flag.size() > 10) a.val = a.flag.substr(11);
-      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
-      else a.val = argv[++i];
-      c.protein = a.choice({"dna", "protein"}) == 1;
-      c.alphabet_given = true;
-      continue;
-    }
-    if (a.flag == "--translate") {  // sketch's own switch, no value
-      c.translate = true;
-      continue;
-    }
-    if (a.flag == "--individual") {  // likewise
-      c.individual = true;
-      continue;
-    }
-    if (a.flag == "--min_length" || a.flag.rfind("--min_length=", 0) == 0) {  // belongs to --individual, read like a row of the table
-      a.name = "min_length";
-      if (a.flag.size() > 12) a.val = a.flag.substr(13);
-      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
-      else a.val = argv[++i];
-      a.flag = "--min_length";
-      c.min_length = a.uint(~0ull);
-      c.min_length_given = true;
-      continue;
-    }
-    if (a.flag == "--fragments") {  // dist's own switch, no value
-      c.fragments = true;
-      continue;
-    }
-    // sketch's --fragment / --fragment_step and the three that belong to dist --fragments, read like rows of the table
-    static const char *const own[] = {"fragment", "fragment_step", "fragment_ani", "min_fragments", "fragment_hits"};
-    size_t own_k = 0;
-    for (; own_k < 5; ++own_k)
-      if (a.flag == std::string("--") + own[own_k] || a.flag.rfind(std::string("--") + own[own_k] + "=", 0) == 0) break;
-    if (own_k < 5) {
-      a.name = own[own_k];
-      const size_t nl = std::strlen(a.name) + 2;
-      if (a.flag.size() > nl) a.val = a.flag.substr(nl + 1);
-      else if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
-      else a.val = argv[++i];
-      a.flag = std::string("--") + a.name;
-      if (own_k == 0) c.fragment = a.uint(~0ull), c.fragment_given = true;
-      else if (own_k == 1) c.fragment_step = a.uint(~0ull), c.fragment_step_given = true;
-      else if (own_k == 2) {
-        char *end = nullptr;
-        c.fragment_ani = std::strtof(a.val.c_str(), &end);
-        if (a.val.empty() || *end || !(c.fragment_ani >= 0.0f && c.fragment_ani <= 100.0f)) a.bad(" (an ANI, 0 to 100)");
-        c.fragment_ani_given = true;
-      } else if (own_k == 3) c.min_fragments = a.uint(0xFFFFFFFFull, 1), c.min_fragments_given = true;
-      else c.fragment_hits = a.file(), c.fragment_hits_given = true;
-      continue;
     }
     const Option *o = nullptr;
     bool have_val = false;
@@ -515,6 +473,11 @@ Cli parse(int argc, char **argv) {
     } else {
       die("unexpected argument '" + a.flag + "'");
     }
+    if (o && !o->take) {  // a switch
+      if (have_val) die("unexpected argument '" + a.flag + "'");
+      c.given.set((size_t)(o - options));
+      continue;
+    }
     if (!have_val) {
       if (i + 1 >= argc) die("a value is required for '" + a.flag + "'");
       a.val = argv[++i];
@@ -531,25 +494,10 @@ Cli parse(int argc, char **argv) {
     if (!(options[k].modes & c.mode_bit)) die(f + " is not supported by " + c.mode + ": " + options[k].why);
     if (options[k].why_shards && c.shards) die(f + " is not supported with --shards: " + options[k].why_shards);
   }
-  if (c.alphabet_given && c.mode_bit != SKETCH)
-    die("--alphabet is not supported by " + c.mode + ": it names the alphabet of the sequences sketch reads");
-  if (c.translate && c.mode_bit != SKETCH)
-    die("--translate is not supported by " + c.mode + ": it translates the nucleotide sequences sketch reads");
-  if (c.individual && c.mode_bit != SKETCH)
-    die("--individual is not supported by " + c.mode + ": it splits the FASTA files sketch reads into their records");
-  if (c.min_length_given && c.mode_bit != SKETCH)
-    die("--min_length is not supported by " + c.mode + ": it belongs to sketch --individual");
-  if ((c.fragment_given || c.fragment_step_given) && c.mode_bit != SKETCH)
-    die(std::string(c.fragment_given ? "--fragment" : "--fragment_step") + " is not supported by " + c.mode + ": it cuts the sequences sketch reads into windows");
-  if (c.fragments && c.mode_bit != DIST)
-    die("--fragments is not supported by " + c.mode + ": it makes dist compare genomes fragment by fragment");
-  const std::pair<bool, const char *> of_fragments[] = {{c.fragment_ani_given, "--fragment_ani"}, {c.min_fragments_given, "--min_fragments"},
-                                                        {c.fragment_hits_given, "--fragment_hits"}};
-  for (const auto &o : of_fragments) {
-    if (o.first && c.mode_bit != DIST) die(std::string(o.second) + " is not supported by " + c.mode + ": it belongs to dist --fragments");
-    if (o.first && !c.fragments) die(std::string(o.second) + " needs --fragments: without it dist compares whole sketches");
-  }
   // what an option needs of the others
+  const bool translate = given(c, "translate"), individual = given(c, "individual"), fragments = given(c, "fragments");
+  for (const char *of_fragments : {"fragment_ani", "min_fragments", "fragment_hits"})
+    if (given(c, of_fragments) && !fragments) die(std::string("--") + of_fragments + " needs --fragments: without it dist compares whole sketches");
   if (c.search_path == SearchPath::topk && c.top_n > HG_SEARCH_TOPK_MAX)
     die("--search_path topk takes -n up to " + std::to_string(HG_SEARCH_TOPK_MAX) + " (larger -n goes through the hit list)");
   if (given(c, "agglomerate") && given(c, "hclust"))
@@ -577,31 +525,31 @@ Cli parse(int argc, char **argv) {
   if (given(c, "newick") && c.ani_metric == HG_ANI_CONTAINMENT)
     die("--ani_metric containment is not supported with --newick: it is directional (mash | max_containment)");
   if (given(c, "newick") && given(c, "pairs")) die("--pairs is not supported with --newick: the tree needs every pair, not the listed ones");
-  if (c.translate) {
+  if (translate) {
     if (c.protein) die("--translate is not supported with --alphabet protein: protein input is not translated");
     amino_acid_mode(c, "--translate", "translated");  // (k defaults as for --alphabet protein)
   }
-  if (c.individual) {
+  if (individual) {
     if (c.protein) die("--individual is not supported with --alphabet protein: protein input is sketched one file at a time");
-    if (c.translate) die("--individual is not supported with --translate: translated input is sketched one file at a time");
+    if (translate) die("--individual is not supported with --translate: translated input is sketched one file at a time");
     if (c.shards) die("--shards is not supported with --individual: the records are sketched on the first visible GPU");
   }
-  if (c.min_length_given && !c.individual) die("--min_length needs --individual: without it sketch makes one sketch per file, whatever its length");
+  if (given(c, "min_length") && !individual) die("--min_length needs --individual: without it sketch makes one sketch per file, whatever its length");
   if (c.protein) amino_acid_mode(c, "--alphabet protein", "protein");  // (Mash's protein default for k)
-  if (c.fragment_step_given && !c.fragment_given) die("--fragment_step needs --fragment: without it sketch makes one sketch per file");
-  if (c.fragment_given) {
-    if (c.individual) die("--fragment is not supported with --individual: the windows are cut from a file's merged sequence, not from its records");
+  if (given(c, "fragment_step") && !given(c, "fragment")) die("--fragment_step needs --fragment: without it sketch makes one sketch per file");
+  if (given(c, "fragment")) {
+    if (individual) die("--fragment is not supported with --individual: the windows are cut from a file's merged sequence, not from its records");
     if (c.protein) die("--fragment is not supported with --alphabet protein: protein input is sketched one file at a time");
-    if (c.translate) die("--fragment is not supported with --translate: translated input is sketched one file at a time");
+    if (translate) die("--fragment is not supported with --translate: translated input is sketched one file at a time");
     if (c.shards) die("--shards is not supported with --fragment: the windows are sketched on the first visible GPU");
-    if (!c.fragment_step_given) c.fragment_step = c.fragment;
+    if (!given(c, "fragment_step")) c.fragment_step = c.fragment;
     if (c.fragment == 0 || c.fragment % 4) die("invalid value '" + std::to_string(c.fragment) + "' for '--fragment': a window is a multiple of 4 bases, at least 4");
     if (c.fragment_step == 0 || c.fragment_step % 4)
       die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step is a multiple of 4 bases, at least 4");
     if (c.fragment_step > c.fragment) die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step above the window would leave bases out");
     if (c.fragment < c.ksize) die("invalid value '" + std::to_string(c.fragment) + "' for '--fragment': a window shorter than -k holds no k-mer");
   }
-  if (c.fragments) {
+  if (fragments) {
     if (given(c, "pairs")) die("--pairs is not supported with --fragments: every pair of genomes is compared");
     if (given(c, "columns")) die("--columns is not supported with --fragments: a line carries the fragment ANI, the matched and the total fragments");
     if (given(c, "newick")) die("--newick is not supported with --fragments: the tree is drawn from whole sketches");
@@ -715,9 +663,9 @@ int run_sketch(const Cli &c) {
   if (c.path == "1" && c.out.empty()) die("the following required arguments were not provided: --path --out");
   if (c.out.empty()) die("the following required arguments were not provided: --out");
   if (c.protein) return run_sketch_batches(c, fasta_files(c.path, {"*.faa"}));
-  if (c.translate) return run_sketch_batches(c, fasta_files(c.path));
-  if (c.individual) return run_sketch_individual(c, fasta_files(c.path));
-  if (c.fragment_given) return run_sketch_fragments(c, fasta_files(c.path));
+  if (given(c, "translate")) return run_sketch_batches(c, fasta_files(c.path));
+  if (given(c, "individual")) return run_sketch_individual(c, fasta_files(c.path));
+  if (given(c, "fragment")) return run_sketch_fragments(c, fasta_files(c.path));
   const auto files = fasta_files(c.path);
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -857,7 +805,7 @@ void parallel(size_t n, F fn) {
 // hg_aa_sketch_batch or hg_tx_sketch_batch sketches it on the first visible GPU.  Log lines, records and payloads are
 // run_sketch's; the records carry canonical = false.
 int run_sketch_batches(const Cli &c, const std::vector<std::string> &files) {
-  const bool tx = c.translate;
+  const bool tx = given(c, "translate");
   const uint32_t read_mode = c.device == "gpu" ? HG_READ_MERGE : HG_READ_NEEDLETAIL;  // (run_sketch's choice)
   const size_t n = files.size();
   logline("INFO", "Start sketching...");
@@ -1424,7 +1372,7 @@ int run_dist_fragments(const Cli &c) {
   logline("INFO", "Computing fragment ANI..");
   hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
   const size_t n_ref = gr.n(), n_qry = gq.n();
-  const bool want_hits = c.fragment_hits_given;
+  const bool want_hits = given(c, "fragment_hits");
   std::vector<hg_frag_pair> pair(n_ref * n_qry);
   std::vector<hg_frag_best> best(want_hits ? n_ref * Q.n : 0);
   {
@@ -1476,7 +1424,7 @@ int run_dist_fragments(const Cli &c) {
 int run_dist(const Cli &c) {
   if (c.path_r == "1" || c.path_q == "1" || c.out.empty())
     die("the following required arguments were not provided: --path_r --path_q --out");
-  if (c.fragments) return run_dist_fragments(c);
+  if (given(c, "fragments")) return run_dist_fragments(c);
   const double t0 = now_s();
   const bool sym = c.path_r == c.path_q;  // src/dist.rs:13
   // (containment is directional: one file against itself runs the full comparison and writes every ordered pair i != j)
@@ -1584,9 +1532,7 @@ int run_dist(const Cli &c) {
     char *text = nullptr;
     size_t len = 0;
     if (hg_nj_newick(joins.data(), R.n, names.data(), &text, &len) != HG_OK) die("inconsistent neighbour-joining result");
-    FILE *f = std::fopen(c.newick_out.c_str(), "wb");
-    const bool bad = !f || std::fwrite(text, 1, len, f) != len;
-    if ((f && std::fclose(f) != 0) || bad) die("Dump Newick file failed!");
+    dump_text(c.newick_out, std::string(text, len), "Dump Newick file failed!");
     hg_free(text);
     std::snprintf(buf, sizeof buf, "Output neighbour-joining tree of %zu genomes to file %s", R.n, c.newick_out.c_str());
     logline("INFO", buf);
@@ -1671,10 +1617,234 @@ int run_search(const Cli &c) {
 // of a --tree line is the lowest ANI between the two merged clusters.
 // --stats <file> (hg_cluster_stats_dev): one line per cluster at -a, whatever formed the clusters -- the statistics of the
 // device arrays as they stand, in processing order under --order size, so that ties go to the sketch processed first.
+//
+// What a scheme leaves on the host: the clusters at -a, in processing order, and what only some schemes produce
+struct Cut {  // the clusters at one threshold
+  float th;
+  size_t n_cl = 0;
+  std::vector<uint32_t> rep, cl;
+};
+struct Merge {  // the absorbed name, what it went into, the merge's level and size
+  uint32_t name, into, size;
+  float level;
+};
+struct Clusters {
+  Cut at;                              // -a
+  std::vector<float> ani;              // greedy, setcover: every sketch's ANI with its representative
+  std::vector<Merge> merges;           // average, complete with --tree: the dendrogram, every child before its parent
+  std::vector<hg_ani_hit> tree;        // --tree / --levels: the edges of the single-linkage tree
+  std::vector<Cut> more;               // --levels: one further threshold each, cut from the tree
+  std::vector<hg_cluster_stat> stats;  // --stats
+};
+
+// A scheme's device calls: the sketches as they lie on the device, the arrays the clusters at -a go to, and one function per
+// scheme that fills what it produces of `r` beyond them (r.at.rep and r.at.cl are downloaded by the caller)
+struct ClusterJob {
+  const Cli &c;
+  const Loaded &L;
+  hg_ctx *ctx;
+  const int16_t *hv;
+  const int32_t *n2;
+  uint32_t *d_rep, *d_cl;
+  const float th = c.ani_th;
+
+  // --hclust average, --agglomerate: the schemes on the dense matrix
+  void dense(Clusters &r) const {
+    const bool want = given(c, "tree");
+    DevBuf<uint32_t> d_into(ctx), d_size(ctx);  // (NULL without --tree: the library then skips the dendrogram)
+    DevBuf<float> d_level(ctx);
+    if (want) d_into.alloc(L.n), d_size.alloc(L.n), d_level.alloc(L.n);
+    ck(ctx, (c.complete ? hg_cluster_complete_dev : hg_cluster_average_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep, d_cl,
+                                                                            d_into.get(), d_level.get(), d_size.get(), &r.at.n_cl),
+       "cluster");
+    if (c.complete) debugf("complete linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_complete_rounds(ctx));
+    else debugf("average linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_average_rounds(ctx));
+    if (!want) return;
+    std::vector<uint32_t> into(L.n), sz(L.n);
+    std::vector<float> level(L.n);
+    d_into.download(into.data(), L.n), d_size.download(sz.data(), L.n), d_level.download(level.data(), L.n);
+    for (size_t i = 0; i < L.n; ++i)
+      if (into[i] != i) r.merges.push_back(Merge{(uint32_t)i, into[i], sz[i], level[i]});
+    // averages, and minima, never increase towards the root: by (level descending, size ascending, into, name) children come first
+    std::sort(r.merges.begin(), r.merges.end(), [](const Merge &x, const Merge &y) {
+      if (x.level != y.level) return x.level > y.level;
+      if (x.size != y.size) return x.size < y.size;
+      if (x.into != y.into) return x.into < y.into;
+      return x.name < y.name;
+    });
+  }
+  // --linkage greedy | setcover: one representative per cluster
+  void representatives(Clusters &r) const {
+    const bool setcover = c.linkage == Linkage::setcover;
+    DevBuf<float> d_ani(ctx, L.n);
+    ck(ctx, (setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep, d_cl,
+                                                                         d_ani.get(), &r.at.n_cl), "cluster");
+    r.ani.resize(L.n);
+    d_ani.download(r.ani.data(), L.n);
+    if (setcover) debugf("set-cover resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_setcover_rounds(ctx));
+    else debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
+  }
+  // --tree, --levels: one comparison at the floor -a (hg_cluster_tree_dev); every level is a cut of the tree (the step calls of
+  // hg_cluster)
+  void tree_and_levels(Clusters &r) const {
+    DevBuf<hg_ani_hit> d_tree(ctx, std::max<size_t>(L.n, 2));
+    size_t n_edges = 0;
+    ck(ctx, hg_cluster_tree_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_tree.get(), L.n ? L.n - 1 : 0, &n_edges, d_rep, d_cl,
+                                &r.at.n_cl), "cluster");
+    debugf("tree of %zu edges in %llu rounds", n_edges, (unsigned long long)hg_ctx_cluster_tree_rounds(ctx));
+    r.tree.resize(n_edges);
+    if (n_edges) d_tree.download(r.tree.data(), n_edges);
+    DevBuf<uint32_t> d_rep2(ctx, L.n), d_cl2(ctx, L.n);  // (one pair of buffers for all levels)
+    for (const float t : c.levels) {
+      Cut v;
+      v.th = t, v.rep.resize(L.n), v.cl.resize(L.n);
+      ck(ctx, hg_cluster_init_dev(ctx, d_rep2.get(), L.n), "cluster");
+      ck(ctx, hg_cluster_add_hits_dev(ctx, d_rep2.get(), L.n, d_tree.get(), n_edges, t), "cluster");
+      ck(ctx, hg_cluster_finish_dev(ctx, d_rep2.get(), L.n, d_cl2.get(), &v.n_cl), "cluster");
+      d_rep2.download(v.rep.data(), L.n);
+      d_cl2.download(v.cl.data(), L.n);
+      r.more.push_back(std::move(v));
+    }
+  }
+  void single(Clusters &r) const {
+    ck(ctx, hg_cluster_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep, d_cl, &r.at.n_cl), "cluster");
+  }
+  // --stats: the records of the clusters at -a, from the device arrays as they stand (processing order)
+  void stats(Clusters &r) const {
+    const double ts = now_s();
+    const size_t n_cl = r.at.n_cl;
+    DevBuf<hg_cluster_stat> d_stat(ctx, std::max<size_t>(n_cl, 1));
+    ck(ctx, hg_cluster_stats_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, d_cl, n_cl, nullptr, d_stat.get()), "cluster statistics");
+    r.stats.resize(n_cl);
+    if (n_cl) d_stat.download(r.stats.data(), n_cl);
+    debugf("cluster statistics in %.1f ms", (now_s() - ts) * 1e3);
+  }
+};
+
+// Everything the writers index with, before anything is written
+void check_clusters(const Cli &c, size_t n, const Clusters &r) {
+  const bool setcover = c.linkage == Linkage::setcover;
+  bool bad = (c.hclust_average || c.complete) && given(c, "tree") && r.merges.size() != n - r.at.n_cl;
+  for (const Merge &m : r.merges) bad |= m.into > m.name;
+  // (a set-cover representative may have a larger index than its member)
+  for (size_t i = 0; i < n; ++i) bad |= r.at.cl[i] >= r.at.n_cl || (setcover ? r.at.rep[i] >= n : r.at.rep[i] > i);
+  for (const Cut &v : r.more)
+    for (size_t i = 0; i < n; ++i) bad |= v.cl[i] >= v.n_cl || v.rep[i] > i;
+  if (given(c, "tree"))
+    for (const hg_ani_hit &e : r.tree) bad |= e.ref_idx >= n || e.qry_idx >= n;
+  for (const hg_cluster_stat &x : r.stats)
+    bad |= x.size == 0 || x.medoid >= n || (x.size >= 2 && (x.within_min_a >= n || x.within_min_b >= n)) ||
+           (x.outside_idx != HG_STATS_NONE && (x.outside_member >= n || x.outside_idx >= n));
+  if (bad) die("inconsistent cluster result");
+}
+
+// "Output N genomes in M clusters (S singletons) at ANI threshold <th> to file <-o>"
+void log_cut(const Cli &c, size_t n, const Cut &v, const char *th) {
+  std::vector<uint32_t> size(v.n_cl, 0);
+  for (size_t i = 0; i < n; ++i) ++size[v.cl[i]];
+  size_t singletons = 0;
+  for (uint32_t x : size) singletons += x == 1;
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %s to file %s", n, v.n_cl, singletons, th,
+                c.out.c_str());
+  logline("INFO", buf);
+}
+
+// -o: one line per record, in file order: its name, "\t<cluster id>\t<name of the cluster's first member or representative>" for -a
+// and for each level, then the ANI with the representative where there are representatives.  perm: processing position -> record
+void write_clusters(const Cli &c, const Loaded &L, const std::vector<uint32_t> &perm, const Clusters &r) {
+  const std::vector<uint32_t> &rep = r.at.rep, &cl = r.at.cl;
+  const std::vector<Cut> &more = r.more;
+  std::vector<uint32_t> pos(L.n);  // record -> processing position
+  for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
+  write_tsv(c.out, c.threads, L.n,
+            [&](size_t i) {
+              size_t b = (size_t)L.len[i] + 12 + L.len[perm[rep[pos[i]]]] + 9;
+              for (const Cut &v : more) b += 12 + L.len[v.rep[i]];
+              return b;
+            },
+            [&](size_t i, char *w) {
+              auto put_cluster = [&](char *o, uint32_t id, size_t first) {
+                size_t b = 0;
+                o[b++] = '\t', b += put_u32(o + b, id), o[b++] = '\t';
+                return b + L.put_name(o + b, first);
+              };
+              const uint32_t k = pos[i];
+              size_t b = L.put_name(w, i);
+              b += put_cluster(w + b, cl[k], perm[rep[k]]);
+              for (const Cut &v : more) b += put_cluster(w + b, v.cl[i], v.rep[i]);
+              if (c.linkage != Linkage::single) return b + put_ani(w + b, r.ani[k]);  // "\t<ani>\n"
+              w[b++] = '\n';
+              return b;
+            },
+            "Dump cluster file failed!");
+}
+// --tree of average and complete linkage: one line per merge: file of into, file of the absorbed name, level, size
+void write_merge_tree(const Cli &c, const Loaded &L, const std::vector<Merge> &merges) {
+  write_tsv(c.tree_out, c.threads, merges.size(), [&](size_t i) { return (size_t)L.len[merges[i].into] + L.len[merges[i].name] + 22; },
+            [&](size_t i, char *w) {
+              size_t b = put_line(w, L, merges[i].into, L, merges[i].name, merges[i].level);
+              w[b - 1] = '\t';  // (put_line ends the line behind the ANI)
+              b += put_u32(w + b, merges[i].size);
+              w[b++] = '\n';
+              return b;
+            },
+            "Dump tree file failed!");
+}
+// --tree of single linkage: one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
+void write_edge_tree(const Cli &c, const Loaded &L, const std::vector<hg_ani_hit> &tree) {
+  write_tsv(c.tree_out, c.threads, tree.size(), [&](size_t i) { return (size_t)L.len[tree[i].ref_idx] + L.len[tree[i].qry_idx] + 10; },
+            [&](size_t i, char *w) { return put_line(w, L, tree[i].ref_idx, L, tree[i].qry_idx, tree[i].ani); }, "Dump tree file failed!");
+}
+// --stats: one line per cluster, in id order: id, size, medoid, mean and minimum within (and the pair that has it), the nearest
+// sketch outside (its ANI, the member, the sketch, the sketch's cluster); NA where a cluster has no such value
+void write_stats(const Cli &c, const Loaded &L, const std::vector<uint32_t> &perm, const Clusters &r) {
+  const std::vector<hg_cluster_stat> &stats = r.stats;
+  const uint32_t none = HG_STATS_NONE;
+  size_t mixed = 0;  // clusters of two or more whose nearest outside sketch is as close as their two least similar members
+  for (const hg_cluster_stat &x : stats) mixed += x.size >= 2 && x.outside_idx != none && x.outside_max >= x.within_min;
+  auto name_len = [&](uint32_t k) { return k == none ? (size_t)2 : (size_t)L.len[perm[k]]; };
+  write_tsv(c.stats_out, c.threads, stats.size(),
+            [&](size_t i) {
+              const hg_cluster_stat &x = stats[i];
+              return 80 + name_len(x.medoid) + name_len(x.within_min_a) + name_len(x.within_min_b) + name_len(x.outside_member) +
+                     name_len(x.outside_idx);
+            },
+            [&](size_t i, char *w) {
+              const hg_cluster_stat &x = stats[i];
+              size_t b = 0;
+              auto tab = [&] { w[b++] = '\t'; };
+              auto na = [&] { tab(), w[b++] = 'N', w[b++] = 'A'; };
+              auto name = [&](uint32_t k) { tab(), b += L.put_name(w + b, perm[k]); };
+              auto milli = [&](uint32_t m) {  // the thousandths as dist prints an ANI
+                tab(), b += put_u32(w + b, m / 1000), w[b++] = '.';
+                w[b++] = (char)('0' + m / 100 % 10), w[b++] = (char)('0' + m / 10 % 10), w[b++] = (char)('0' + m % 10);
+              };
+              b += put_u32(w + b, (uint32_t)i), tab(), b += put_u32(w + b, x.size), name(x.medoid);
+              if (x.size >= 2) {
+                const float mean = (float)(((double)x.within_sum / ((double)x.size * (double)(x.size - 1))) / 1000.0);
+                b += put_ani(w + b, mean) - 1;  // (without put_ani's end of line)
+                milli(x.within_min), name(x.within_min_a), name(x.within_min_b);
+              } else {
+                na(), na(), na(), na();
+              }
+              if (x.outside_idx != none) {
+                milli(x.outside_max), name(x.outside_member), name(x.outside_idx);
+                tab(), b += put_u32(w + b, r.at.cl[x.outside_idx]);
+              } else {
+                na(), na(), na(), na();
+              }
+              w[b++] = '\n';
+              return b;
+            },
+            "Dump statistics file failed!");
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "Output statistics of %zu clusters (%zu not separated) to file %s", stats.size(), mixed, c.stats_out.c_str());
+  logline("INFO", buf);
+}
+
 int run_cluster(const Cli &c) {
   if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
-  const float th = c.ani_th;
-  const bool setcover = c.linkage == Linkage::setcover, with_reps = c.linkage != Linkage::single;  // (greedy, setcover)
   const double t0 = now_s();
   Session s(1, c.ani_metric, c.path);
   const Loaded &L = s.R;
@@ -1682,218 +1852,36 @@ int run_cluster(const Cli &c) {
   for (size_t i = 0; i < L.n; ++i) perm[i] = (uint32_t)i;
   if (c.order_size) std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return L.n2[a] > L.n2[b]; });
   to_devices(s.multi, L, s.dR, false, c.order_size ? &perm : nullptr);
-  const int16_t *hv = s.dR.hv[0];
-  const int32_t *n2 = s.dR.n2[0];
   char buf[512];
-  std::snprintf(buf, sizeof buf, "Clustering %zu genomes at ANI threshold %.1f..", L.n, th);
+  std::snprintf(buf, sizeof buf, "Clustering %zu genomes at ANI threshold %.1f..", L.n, c.ani_th);
   logline("INFO", buf);
   const double tp = now_s();
   hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
   DevBuf<uint32_t> d_rep(ctx, L.n), d_cl(ctx, L.n);
-  size_t n_cl = 0;
-  std::vector<uint32_t> rep(L.n), cl(L.n);
-  std::vector<float> ani;
-  struct Level {  // --levels: one further threshold, cut from the tree
-    float th;
-    size_t n_cl = 0;
-    std::vector<uint32_t> rep, cl;
-  };
-  std::vector<Level> more;
-  std::vector<hg_ani_hit> tree;  // --tree / --levels
-  const bool dense = c.hclust_average || c.complete;  // average or complete linkage: the schemes on the dense matrix
-  struct Merge {                 // ... with --tree: the absorbed name, what it went into, the merge's level and size
-    uint32_t name, into, size;
-    float level;
-  };
-  std::vector<Merge> merges;
-  if (dense) {
-    const bool want = given(c, "tree");
-    DevBuf<uint32_t> d_into(ctx), d_size(ctx);  // (NULL without --tree: the library then skips the dendrogram)
-    DevBuf<float> d_level(ctx);
-    if (want) d_into.alloc(L.n), d_size.alloc(L.n), d_level.alloc(L.n);
-    ck(ctx, (c.complete ? hg_cluster_complete_dev : hg_cluster_average_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(),
-                                                                            d_cl.get(), d_into.get(), d_level.get(), d_size.get(), &n_cl),
-       "cluster");
-    if (c.complete) debugf("complete linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_complete_rounds(ctx));
-    else debugf("average linkage in %llu rounds", (unsigned long long)hg_ctx_cluster_average_rounds(ctx));
-    if (want) {
-      std::vector<uint32_t> into(L.n), sz(L.n);
-      std::vector<float> level(L.n);
-      d_into.download(into.data(), L.n), d_size.download(sz.data(), L.n), d_level.download(level.data(), L.n);
-      for (size_t i = 0; i < L.n; ++i) {
-        if (into[i] > i) die("inconsistent cluster result");
-        if (into[i] != i) merges.push_back(Merge{(uint32_t)i, into[i], sz[i], level[i]});
-      }
-      // averages, and minima, never increase towards the root: by (level descending, size ascending, into, name) children come first
-      std::sort(merges.begin(), merges.end(), [](const Merge &x, const Merge &y) {
-        if (x.level != y.level) return x.level > y.level;
-        if (x.size != y.size) return x.size < y.size;
-        if (x.into != y.into) return x.into < y.into;
-        return x.name < y.name;
-      });
-      if (merges.size() != L.n - n_cl) die("inconsistent cluster result");
-    }
-  } else if (with_reps) {
-    DevBuf<float> d_ani(ctx, L.n);
-    ck(ctx, (setcover ? hg_cluster_setcover_dev : hg_cluster_greedy_dev)(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(),
-                                                                         d_cl.get(), d_ani.get(), &n_cl), "cluster");
-    ani.resize(L.n);
-    d_ani.download(ani.data(), L.n);
-    if (setcover) debugf("set-cover resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_setcover_rounds(ctx));
-    else debugf("greedy resolution in %llu rounds", (unsigned long long)hg_ctx_cluster_greedy_rounds(ctx));
-  } else if (given(c, "tree") || given(c, "levels")) {
-    // one comparison at the floor -a (hg_cluster_tree_dev); every level is a cut of the tree (the step calls of hg_cluster)
-    DevBuf<hg_ani_hit> d_tree(ctx, std::max<size_t>(L.n, 2));
-    size_t n_edges = 0;
-    ck(ctx, hg_cluster_tree_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_tree.get(), L.n ? L.n - 1 : 0, &n_edges, d_rep.get(),
-                                d_cl.get(), &n_cl), "cluster");
-    debugf("tree of %zu edges in %llu rounds", n_edges, (unsigned long long)hg_ctx_cluster_tree_rounds(ctx));
-    tree.resize(n_edges);
-    if (n_edges) d_tree.download(tree.data(), n_edges);
-    DevBuf<uint32_t> d_rep2(ctx, L.n), d_cl2(ctx, L.n);  // (one pair of buffers for all levels)
-    for (const float t : c.levels) {
-      Level v;
-      v.th = t, v.rep.resize(L.n), v.cl.resize(L.n);
-      ck(ctx, hg_cluster_init_dev(ctx, d_rep2.get(), L.n), "cluster");
-      ck(ctx, hg_cluster_add_hits_dev(ctx, d_rep2.get(), L.n, d_tree.get(), n_edges, t), "cluster");
-      ck(ctx, hg_cluster_finish_dev(ctx, d_rep2.get(), L.n, d_cl2.get(), &v.n_cl), "cluster");
-      d_rep2.download(v.rep.data(), L.n);
-      d_cl2.download(v.cl.data(), L.n);
-      more.push_back(std::move(v));
-    }
-  } else {
-    ck(ctx, hg_cluster_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, th, d_rep.get(), d_cl.get(), &n_cl), "cluster");
-  }
-  d_rep.download(rep.data(), L.n);
-  d_cl.download(cl.data(), L.n);
+  const ClusterJob job{c, L, ctx, s.dR.hv[0], s.dR.n2[0], d_rep.get(), d_cl.get()};
+  const bool dense = c.hclust_average || c.complete;  // average or complete linkage
+  Clusters r;
+  r.at.th = c.ani_th, r.at.rep.resize(L.n), r.at.cl.resize(L.n);
+  if (dense) job.dense(r);
+  else if (c.linkage != Linkage::single) job.representatives(r);
+  else if (given(c, "tree") || given(c, "levels")) job.tree_and_levels(r);
+  else job.single(r);
+  d_rep.download(r.at.rep.data(), L.n);
+  d_cl.download(r.at.cl.data(), L.n);
   debugf("clusters on the host in %.1f ms", (now_s() - tp) * 1e3);
-  // --stats: the records of the clusters at -a, from the device arrays as they stand (processing order)
-  std::vector<hg_cluster_stat> stats;
-  if (given(c, "stats")) {
-    const double ts = now_s();
-    DevBuf<hg_cluster_stat> d_stat(ctx, std::max<size_t>(n_cl, 1));
-    ck(ctx, hg_cluster_stats_dev(ctx, hv, n2, L.n, (uint32_t)L.hv_d, L.ksize, d_cl.get(), n_cl, nullptr, d_stat.get()), "cluster statistics");
-    stats.resize(n_cl);
-    if (n_cl) d_stat.download(stats.data(), n_cl);
-    debugf("cluster statistics in %.1f ms", (now_s() - ts) * 1e3);
-  }
-  std::vector<uint32_t> size(n_cl, 0);
-  for (size_t i = 0; i < L.n; ++i) {
-    // (a set-cover representative may have a larger index than its member)
-    if (cl[i] >= n_cl || (setcover ? rep[i] >= L.n : rep[i] > i)) die("inconsistent cluster result");
-    ++size[cl[i]];
-  }
-  size_t singletons = 0;
-  for (uint32_t x : size) singletons += x == 1;
-  for (const Level &v : more)
-    for (size_t i = 0; i < L.n; ++i)
-      if (v.cl[i] >= v.n_cl || v.rep[i] > i) die("inconsistent cluster result");
-  // one line per record, in file order: its name, "\t<cluster id>\t<name of the cluster's first member or representative>" for -a
-  // and for each level, then the ANI with the representative where there are representatives
-  std::vector<uint32_t> pos(L.n);  // record -> processing position
-  for (size_t k = 0; k < L.n; ++k) pos[perm[k]] = (uint32_t)k;
-  write_tsv(c.out, c.threads, L.n,
-            [&](size_t i) {
-              size_t b = (size_t)L.len[i] + 12 + L.len[perm[rep[pos[i]]]] + 9;
-              for (const Level &v : more) b += 12 + L.len[v.rep[i]];
-              return b;
-            },
-            [&](size_t i, char *w) {
-              auto put_cluster = [&](char *o, uint32_t id, size_t r) {
-                size_t b = 0;
-                o[b++] = '\t', b += put_u32(o + b, id), o[b++] = '\t';
-                return b + L.put_name(o + b, r);
-              };
-              const uint32_t k = pos[i];
-              size_t b = L.put_name(w, i);
-              b += put_cluster(w + b, cl[k], perm[rep[k]]);
-              for (const Level &v : more) b += put_cluster(w + b, v.cl[i], v.rep[i]);
-              if (with_reps) return b + put_ani(w + b, ani[k]);  // "\t<ani>\n"
-              w[b++] = '\n';
-              return b;
-            },
-            "Dump cluster file failed!");
-  if (given(c, "tree") && dense) {  // one line per merge: file of into, file of the absorbed name, level, size
-    write_tsv(c.tree_out, c.threads, merges.size(), [&](size_t i) { return (size_t)L.len[merges[i].into] + L.len[merges[i].name] + 22; },
-              [&](size_t i, char *w) {
-                size_t b = put_line(w, L, merges[i].into, L, merges[i].name, merges[i].level);
-                w[b - 1] = '\t';  // (put_line ends the line behind the ANI)
-                b += put_u32(w + b, merges[i].size);
-                w[b++] = '\n';
-                return b;
-              },
-              "Dump tree file failed!");
-  } else if (given(c, "tree")) {  // one line per edge, strongest first: file of lo, file of hi, ANI as dist prints it
-    for (const hg_ani_hit &e : tree)
-      if (e.ref_idx >= L.n || e.qry_idx >= L.n) die("inconsistent cluster result");
-    write_tsv(c.tree_out, c.threads, tree.size(), [&](size_t i) { return (size_t)L.len[tree[i].ref_idx] + L.len[tree[i].qry_idx] + 10; },
-              [&](size_t i, char *w) { return put_line(w, L, tree[i].ref_idx, L, tree[i].qry_idx, tree[i].ani); }, "Dump tree file failed!");
-  }
-  std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %.1f to file %s", L.n, n_cl,
-                singletons, th, c.out.c_str());
-  logline("INFO", buf);
-  if (given(c, "stats")) {
-    // one line per cluster, in id order: id, size, medoid, mean and minimum within (and the pair that has it), the nearest
-    // sketch outside (its ANI, the member, the sketch, the sketch's cluster); NA where a cluster has no such value
-    const uint32_t none = HG_STATS_NONE;
-    size_t mixed = 0;  // clusters of two or more whose nearest outside sketch is as close as their two least similar members
-    for (const hg_cluster_stat &x : stats) {
-      const bool pairs = x.size >= 2, outside = x.outside_idx != none;
-      if (x.size == 0 || x.medoid >= L.n || (pairs && (x.within_min_a >= L.n || x.within_min_b >= L.n)) ||
-          (outside && (x.outside_member >= L.n || x.outside_idx >= L.n)))
-        die("inconsistent cluster result");
-      mixed += pairs && outside && x.outside_max >= x.within_min;
-    }
-    auto name_len = [&](uint32_t k) { return k == none ? (size_t)2 : (size_t)L.len[perm[k]]; };
-    write_tsv(c.stats_out, c.threads, stats.size(),
-              [&](size_t i) {
-                const hg_cluster_stat &x = stats[i];
-                return 80 + name_len(x.medoid) + name_len(x.within_min_a) + name_len(x.within_min_b) + name_len(x.outside_member) +
-                       name_len(x.outside_idx);
-              },
-              [&](size_t i, char *w) {
-                const hg_cluster_stat &x = stats[i];
-                size_t b = 0;
-                auto tab = [&] { w[b++] = '\t'; };
-                auto na = [&] { tab(), w[b++] = 'N', w[b++] = 'A'; };
-                auto name = [&](uint32_t k) { tab(), b += L.put_name(w + b, perm[k]); };
-                auto milli = [&](uint32_t m) {  // the thousandths as dist prints an ANI
-                  tab(), b += put_u32(w + b, m / 1000), w[b++] = '.';
-                  w[b++] = (char)('0' + m / 100 % 10), w[b++] = (char)('0' + m / 10 % 10), w[b++] = (char)('0' + m % 10);
-                };
-                b += put_u32(w + b, (uint32_t)i), tab(), b += put_u32(w + b, x.size), name(x.medoid);
-                if (x.size >= 2) {
-                  const float mean = (float)(((double)x.within_sum / ((double)x.size * (double)(x.size - 1))) / 1000.0);
-                  b += put_ani(w + b, mean) - 1;  // (without put_ani's end of line)
-                  milli(x.within_min), name(x.within_min_a), name(x.within_min_b);
-                } else {
-                  na(), na(), na(), na();
-                }
-                if (x.outside_idx != none) {
-                  milli(x.outside_max), name(x.outside_member), name(x.outside_idx);
-                  tab(), b += put_u32(w + b, cl[x.outside_idx]);
-                } else {
-                  na(), na(), na(), na();
-                }
-                w[b++] = '\n';
-                return b;
-              },
-              "Dump statistics file failed!");
-    std::snprintf(buf, sizeof buf, "Output statistics of %zu clusters (%zu not separated) to file %s", stats.size(), mixed,
-                  c.stats_out.c_str());
-    logline("INFO", buf);
-  }
-  for (const Level &v : more) {
-    std::vector<uint32_t> sz(v.n_cl, 0);
-    for (size_t i = 0; i < L.n; ++i) ++sz[v.cl[i]];
-    size_t single = 0;
-    for (uint32_t x : sz) single += x == 1;
-    char lv[32];  // (one decimal like -a's line where that is the level, else as many digits as it needs)
-    std::snprintf(lv, sizeof lv, "%.1f", (double)v.th);
-    if (std::strtof(lv, nullptr) != v.th) std::snprintf(lv, sizeof lv, "%g", (double)v.th);
-    std::snprintf(buf, sizeof buf, "Output %zu genomes in %zu clusters (%zu singletons) at ANI threshold %s to file %s", L.n, v.n_cl,
-                  single, lv, c.out.c_str());
-    logline("INFO", buf);
+  if (given(c, "stats")) job.stats(r);
+  check_clusters(c, L.n, r);
+
+  write_clusters(c, L, perm, r);
+  if (given(c, "tree")) dense ? write_merge_tree(c, L, r.merges) : write_edge_tree(c, L, r.tree);
+  std::snprintf(buf, sizeof buf, "%.1f", r.at.th);
+  log_cut(c, L.n, r.at, buf);
+  if (given(c, "stats")) write_stats(c, L, perm, r);
+  for (const Cut &v : r.more) {
+    // (one decimal like -a's line where that is the level, else as many digits as it needs)
+    std::snprintf(buf, sizeof buf, "%.1f", (double)v.th);
+    if (std::strtof(buf, nullptr) != v.th) std::snprintf(buf, sizeof buf, "%g", (double)v.th);
+    log_cut(c, L.n, v, buf);
   }
   std::snprintf(buf, sizeof buf, "Clustered %zu files took %.3fs", L.n, now_s() - t0);
   logline("INFO", buf);

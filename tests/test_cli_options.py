@@ -188,6 +188,95 @@ CASES = [
     (('cluster', '-p', 'x'), 2, 'error: the following required arguments were not provided: --path --out\n'),
     (('cluster', '-o', 'out.tsv'), 2, 'error: the following required arguments were not provided: --path --out\n'),
     (('search',), 0, ''),
+    # the ten options that parse once read by hand (--alphabet, --translate, --individual, --min_length, --fragment,
+    # --fragment_step, --fragments, --fragment_ani, --min_fragments, --fragment_hits), recorded from those readers before they
+    # became rows of the table: a bad number is reported under the option's bare name however it was typed, a switch takes no
+    # '=value', and the first fault reported is the one of the earlier row
+    (('sketch', '--individual', '--min_length=x'), 2, "error: invalid value 'x' for '--min_length'\n"),
+    (('sketch', '--fragment=x'), 2, "error: invalid value 'x' for '--fragment'\n"),
+    (('sketch', '--fragment', '8', '--fragment_step=x'), 2, "error: invalid value 'x' for '--fragment_step'\n"),
+    (('dist', '--fragments', '--min_fragments=0'), 2, "error: invalid value '0' for '--min_fragments'\n"),
+    (('dist', '--fragments', '--fragment_ani=101'), 2, "error: invalid value '101' for '--fragment_ani' (an ANI, 0 to 100)\n"),
+    (('dist', '--fragments', '--fragment_hits='), 2, "error: invalid value '' for '--fragment_hits' (a file name)\n"),
+    (('sketch', '--alphabet='), 2, "error: invalid value '' for '--alphabet' (dna | protein)\n"),
+    (('sketch', '--alphabet', 'rna'), 2, "error: invalid value 'rna' for '--alphabet' (dna | protein)\n"),
+    (('sketch', '--alphabet'), 2, "error: a value is required for '--alphabet'\n"),
+    (('sketch', '--translate=1'), 2, "error: unexpected argument '--translate=1'\n"),
+    (('sketch', '--min_length', '--individual'), 2, "error: invalid value '--individual' for '--min_length'\n"),
+    (('dist', '--alphabet', 'protein', '--search_path', 'hits'), 2, 'error: --search_path is not supported by dist: it chooses how search selects its results\n'),
+    (('dist', '--translate', '--individual'), 2, 'error: --translate is not supported by dist: it translates the nucleotide sequences sketch reads\n'),
+    (('search', '--fragment_ani', '95', '--fragment', '8'), 2, 'error: --fragment is not supported by search: it cuts the sequences sketch reads into windows\n'),
+    (('cluster', '--min_length', '5', '--alphabet', 'dna'), 2, 'error: --alphabet is not supported by cluster: it names the alphabet of the sequences sketch reads\n'),
+    (('search', '--fragments', '--tree', 't'), 2, 'error: --tree is not supported by search: it belongs to cluster --linkage single\n'),
+    (('dist', '--fragment_hits', 'h', '--min_fragments', '2'), 2, 'error: --min_fragments needs --fragments: without it dist compares whole sketches\n'),
+    (('dist', '--fragment_ani', '95', '--search_path', 'topk', '-n', '65'), 2, 'error: --search_path is not supported by dist: it chooses how search selects its results\n'),
+    (('dist', '--fragments', '--fragment_ani', '95', '--shards', '2', '--columns', 'mash'), 2, 'error: --columns is not supported with --shards: dist with --columns or --pairs runs on the first visible GPU\n'),
+    (('sketch', '--fragments', '--min_count', '0'), 2, "error: invalid value '0' for '--min_count'\n"),
+    (('sketch', '--fragment', '8', '-t', '300'), 2, "error: invalid value '300' for '-t'\n"),
+    (('sketch', '-t', '300', '--fragment', 'x'), 2, "error: invalid value '300' for '-t'\n"),
+    (('sketch', '--individual', '--fragment_step', '8'), 2, 'error: --fragment_step needs --fragment: without it sketch makes one sketch per file\n'),
+    (('sketch', '--alphabet', 'protein', '--alphabet', 'dna', '--fragment', '1000'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--translate', '--translate'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    # ... their values: missing, empty, out of range, the last one inside it
+    (('sketch', '--individual=1'), 2, "error: unexpected argument '--individual=1'\n"),
+    (('dist', '--fragments='), 2, "error: unexpected argument '--fragments='\n"),
+    (('sketch', '--translate', 'x'), 2, "error: unexpected argument 'x'\n"),
+    (('sketch', '--min_length'), 2, "error: a value is required for '--min_length'\n"),
+    (('sketch', '--min_length='), 2, "error: invalid value '' for '--min_length'\n"),
+    (('sketch', '--individual', '--min_length', '-1'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--fragment=8x'), 2, "error: invalid value '8x' for '--fragment'\n"),
+    (('sketch', '--fragment_step'), 2, "error: a value is required for '--fragment_step'\n"),
+    (('sketch', '--fragment', '18446744073709551616'), 2, "error: invalid value '18446744073709551615' for '--fragment': a window is a multiple of 4 bases, at least 4\n"),
+    (('dist', '--fragments', '--min_fragments=4294967296'), 2, "error: invalid value '4294967296' for '--min_fragments'\n"),
+    (('dist', '--fragments', '--min_fragments', '4294967295'), 2, 'error: the following required arguments were not provided: --path_r --path_q --out\n'),
+    (('dist', '--fragments', '--fragment_ani=nan'), 2, "error: invalid value 'nan' for '--fragment_ani' (an ANI, 0 to 100)\n"),
+    (('dist', '--fragments', '--fragment_ani', '-1'), 2, "error: invalid value '-1' for '--fragment_ani' (an ANI, 0 to 100)\n"),
+    (('dist', '--fragments', '--fragment_ani', '1e2'), 2, 'error: the following required arguments were not provided: --path_r --path_q --out\n'),
+    (('dist', '--fragments', '--fragment_ani='), 2, "error: invalid value '' for '--fragment_ani' (an ANI, 0 to 100)\n"),
+    (('dist', '--fragments', '--fragment_ani', '95x'), 2, "error: invalid value '95x' for '--fragment_ani' (an ANI, 0 to 100)\n"),
+    (('dist', '--fragment_ani'), 2, "error: a value is required for '--fragment_ani'\n"),
+    # ... in a subcommand that refuses them
+    (('search', '--individual'), 2, 'error: --individual is not supported by search: it splits the FASTA files sketch reads into their records\n'),
+    (('cluster', '--fragments'), 2, 'error: --fragments is not supported by cluster: it makes dist compare genomes fragment by fragment\n'),
+    (('cluster', '--translate'), 2, 'error: --translate is not supported by cluster: it translates the nucleotide sequences sketch reads\n'),
+    (('dist', '--fragment_step', '4'), 2, 'error: --fragment_step is not supported by dist: it cuts the sequences sketch reads into windows\n'),
+    (('dist', '--fragment', '8', '--fragment_step', '4'), 2, 'error: --fragment is not supported by dist: it cuts the sequences sketch reads into windows\n'),
+    (('search', '--min_fragments', '2', '--fragment_hits', 'h'), 2, 'error: --min_fragments is not supported by search: it belongs to dist --fragments\n'),
+    # ... and what they need of the others, on both sides of the edge
+    (('dist', '--fragment_hits=h'), 2, 'error: --fragment_hits needs --fragments: without it dist compares whole sketches\n'),
+    (('dist', '--fragment_ani', '95'), 2, 'error: --fragment_ani needs --fragments: without it dist compares whole sketches\n'),
+    (('dist', '--fragments', '--fragment_ani', '95', '--min_fragments', '2', '--fragment_hits', 'h'), 2, 'error: the following required arguments were not provided: --path_r --path_q --out\n'),
+    (('dist', '--fragments', '--pairs', 'f'), 2, 'error: --pairs is not supported with --fragments: every pair of genomes is compared\n'),
+    (('dist', '--fragments', '--columns', 'mash'), 2, 'error: --columns is not supported with --fragments: a line carries the fragment ANI, the matched and the total fragments\n'),
+    (('dist', '--fragments', '--newick', 't'), 2, 'error: --newick is not supported with --fragments: the tree is drawn from whole sketches\n'),
+    (('dist', '--fragments', '--shards', '2'), 2, 'error: --shards is not supported with --fragments: it runs on the first visible GPU\n'),
+    (('sketch', '--translate', '--alphabet', 'protein'), 2, 'error: --translate is not supported with --alphabet protein: protein input is not translated\n'),
+    (('sketch', '--individual', '--alphabet', 'protein'), 2, 'error: --individual is not supported with --alphabet protein: protein input is sketched one file at a time\n'),
+    (('sketch', '--individual', '--translate'), 2, 'error: --individual is not supported with --translate: translated input is sketched one file at a time\n'),
+    (('sketch', '--individual', '--shards', '2'), 2, 'error: --shards is not supported with --individual: the records are sketched on the first visible GPU\n'),
+    (('sketch', '--min_length', '5'), 2, 'error: --min_length needs --individual: without it sketch makes one sketch per file, whatever its length\n'),
+    (('sketch', '--individual', '--min_length', '5'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--individual', '--min_length=5'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--translate', '--min_count', '2'), 2, 'error: --min_count is not supported with --translate: amino-acid k-mers are sketched without the count filter\n'),
+    (('sketch', '--translate', '--shards', '2'), 2, 'error: --shards is not supported with --translate: translated input is sketched on the first visible GPU\n'),
+    (('sketch', '--alphabet', 'protein', '-k', '33'), 2, "error: invalid value '33' for '--ksize': --alphabet protein takes k-mers of 1 to 32 residues\n"),
+    (('sketch', '--translate', '-k', '33'), 2, "error: invalid value '33' for '--ksize': --translate takes k-mers of 1 to 32 residues\n"),
+    (('sketch', '--alphabet=protein', '-k', '32'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--fragment', '6'), 2, "error: invalid value '6' for '--fragment': a window is a multiple of 4 bases, at least 4\n"),
+    (('sketch', '--fragment', '0'), 2, "error: invalid value '0' for '--fragment': a window is a multiple of 4 bases, at least 4\n"),
+    (('sketch', '--fragment', '8', '--fragment_step', '12'), 2, "error: invalid value '12' for '--fragment_step': a step above the window would leave bases out\n"),
+    (('sketch', '--fragment', '8', '--fragment_step', '6'), 2, "error: invalid value '6' for '--fragment_step': a step is a multiple of 4 bases, at least 4\n"),
+    (('sketch', '--fragment', '8', '--fragment_step', '0'), 2, "error: invalid value '0' for '--fragment_step': a step is a multiple of 4 bases, at least 4\n"),
+    (('sketch', '--fragment', '8'), 2, "error: invalid value '8' for '--fragment': a window shorter than -k holds no k-mer\n"),
+    (('sketch', '--fragment', '24', '--fragment_step=8'), 2, 'error: the following required arguments were not provided: --path --out\n'),
+    (('sketch', '--fragment', '8', '--individual'), 2, "error: --fragment is not supported with --individual: the windows are cut from a file's merged sequence, not from its records\n"),
+    (('sketch', '--fragment', '8', '--alphabet', 'protein'), 2, 'error: --fragment is not supported with --alphabet protein: protein input is sketched one file at a time\n'),
+    (('sketch', '--fragment', '8', '--translate'), 2, 'error: --fragment is not supported with --translate: translated input is sketched one file at a time\n'),
+    (('sketch', '--fragment', '8', '--shards', '2'), 2, 'error: --shards is not supported with --fragment: the windows are sketched on the first visible GPU\n'),
+    # search has no help of its own: the lookup by subcommand leaves --help and -h to the table, as the three blocks did
+    (('search', '--help'), 2, "error: unexpected argument '--help'\n"),
+    (('search', '-h'), 2, "error: a value is required for '-h'\n"),
+    (('search', '-h', 'x'), 2, "error: unexpected argument '-h'\n"),
 ]
 
 HELP = (

@@ -525,3 +525,44 @@ def test_cli_tree_and_levels_end_to_end(tmp_path):
     for l in lines:
         a, b, v = l.split("\t")
         assert field[(a, b)] == v
+
+
+def test_cli_levels_without_tree(gctx, tmp_path):
+    """--levels alone: the tree is built for its cuts only and no tree file is written.  16 sketches at hv_d 1024 (a cluster of 8,
+    half of another, 4 loners); the bytes of -o are those of hg_cluster_tree and of the step calls on its edges (cut_dev), formatted
+    as test_cli_tree_and_levels_end_to_end formats them; the levels are two of the tree's own ANIs, written so that the command
+    line reads back the same float32"""
+    import bench
+    c, hg, dev = gctx
+    n, hv_d, floor = 16, 1024, 93.0
+
+    def rows(m, first):
+        return bench.clustered_hvs(m, first, dev, n=900, cluster=8).cpu().numpy()[:, :hv_d].copy()
+
+    hv = np.concatenate([rows(12, 0)] + [rows(1, 1000 + 8 * j) for j in range(4)])
+    n2 = cr.norms(hv)
+    files = ["/d/%sg%02d.fna" % ("x" * (i % 3), i) for i in range(n)]
+    recs = []
+    for i in range(n):
+        q, pk = hg.hv_pack(hv[i])
+        recs.append(dict(ksize=21, scaled=1500, canonical=True, seed=123, hv_d=hv_d, hv_quant_bits=q, hv_norm_2=int(n2[i]),
+                         file_str=files[i], hv=pk.view(np.int16)))
+    sk, out = str(tmp_path / "sixteen.sketch"), str(tmp_path / "levels.tsv")
+    hg.write_sketch_file(sk, recs)
+    tree, rep, cl, nc = c.cluster_tree(hv, n2, 21, floor)
+    assert nc == 6 and tree.size == n - nc
+    anis = np.unique(tree["ani"])
+    lo, hi = float(anis[anis.size // 2]), float(anis[-1])
+    assert floor < lo < hi
+    d_tree = to_dev(gctx, tree)
+    cuts = [(rep, cl, nc)] + [cut_dev(gctx, n, d_tree, tree.size, t) for t in (lo, hi)]
+    assert nc < cuts[1][2] < cuts[2][2] < n  # the levels tell something apart; the strongest edge reaches the last one
+    want = "".join("\t".join([files[i]] + [x for r_, c_, _ in cuts for x in (str(c_[i]), files[r_[i]])]) + "\n" for i in range(n)).encode()
+    r = cli(hg, "cluster", "-p", sk, "-o", out, "-a", "%.9g" % floor, "--levels", "%.9g,%.9g" % (lo, hi))
+    assert open(out, "rb").read() == want
+    assert sorted(os.listdir(str(tmp_path))) == ["levels.tsv", "sixteen.sketch"]
+    for (r_, c_, k), t in zip(cuts, (floor, lo, hi)):
+        name = "%.1f" % t if np.float32("%.1f" % t) == np.float32(t) else "%g" % t  # (as the log line prints a level)
+        singletons = int((np.bincount(c_) == 1).sum())
+        assert ("Output %d genomes in %d clusters (%d singletons) at ANI threshold %s to file %s" % (n, k, singletons, name, out)) in r.stdout
+    assert r.stdout.count("Output %d genomes in" % n) == 3

@@ -76,11 +76,12 @@ def test_join_record_is_24_bytes_with_the_headers_offsets(hg, tmp_path):
 
 
 # ---- the command line -----------------------------------------------------------------------------------------------
-def test_the_option_table_has_the_newick_row_and_stays_within_32():
+def test_the_option_table_has_the_newick_row_and_stays_within_the_width_of_given():
     src = open(os.path.join(ROOT, "hyper-gen_amd", "csrc", "hg_cli.cpp")).read()
     table = src[src.index("const Option options[] = {"):src.index("const size_t N_OPTIONS")]
     rows = re.findall(r"^    \{\"([a-z_]+)\", ", table, flags=re.M)
-    assert "newick" in rows and len(rows) == len(set(rows)) == 30 <= 32
+    width, = map(int, re.findall(r"std::bitset<(\d+)> given;", src))  # Cli::given, a bit per row
+    assert width == 64 and "newick" in rows and len(rows) == len(set(rows)) == 40 <= width
 
 
 NOT_DIST = "error: --newick is not supported by %s: it draws the tree of dist's comparison\n"
