@@ -648,6 +648,61 @@ def _frag_offsets(first):
     return a, max(a.size - 1, 0)
 
 
+# ---- libhypergen_hist.so (include/hypergen_hist.h): the histogram of the ANI values of a whole comparison ----
+HIST_LIB_PATH = os.path.join(_HERE, "libhypergen_hist.so")
+HIST_EXPORTS = [
+    "hg_hist_bins", "hg_hist_add_matrix_dev", "hg_hist_dev", "hg_hist", "hg_hist_lds_bins", "hg_hist_tile_rows", "hg_hist_tile_cols",
+    "hg_hist_threads", "hg_hist_kernel_names", "hg_hist_launch_counts",
+]
+HIST_ALL, HIST_UPPER, HIST_OFFDIAG = 0, 1, 2  # HG_HIST_*: every (i, j); i < j; i != j
+HIST_MILLI_MAX = 100000  # HG_HIST_MILLI_MAX
+
+
+@functools.lru_cache(None)
+def lib_hist():
+    """The fifth companion library, loaded behind lib() like lib_aa()."""
+    lib()
+    vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
+    sig = {
+        "hg_hist_bins": (u32, [u32]),
+        "hg_hist_add_matrix_dev": (C.c_int, [vp, vp, sz, sz, sz, sz, sz, u32, u32, vp]),
+        "hg_hist_dev": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, u32, u32, u32, u32, sz, vp]),
+        "hg_hist": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, u32, u32, u32, u32, vp]),
+        "hg_hist_lds_bins": (u32, []),
+        "hg_hist_tile_rows": (u32, []),
+        "hg_hist_tile_cols": (u32, []),
+        "hg_hist_threads": (u32, []),
+        "hg_hist_kernel_names": (C.c_char_p, []),
+        "hg_hist_launch_counts": (u32, [vp, u32]),
+    }
+    return _load("libhypergen_hist.so", HIST_LIB_PATH, sig, HIST_EXPORTS)
+
+
+def hist_bins(bin_milli):
+    """hg_hist_bins (needs no GPU): the bins of a width in thousandths, 0 for a width outside 1..100 000"""
+    return int(lib_hist().hg_hist_bins(bin_milli))
+
+
+def hist_geometry():
+    """dict of hg_hist_lds_bins, hg_hist_tile_rows, hg_hist_tile_cols and hg_hist_threads"""
+    L = lib_hist()
+    return {"lds_bins": int(L.hg_hist_lds_bins()), "tile_rows": int(L.hg_hist_tile_rows()), "tile_cols": int(L.hg_hist_tile_cols()),
+            "threads": int(L.hg_hist_threads())}
+
+
+def hist_kernel_names():
+    """hg_hist_kernel_names: the library's kernels as rocprofv3 spells them"""
+    return lib_hist().hg_hist_kernel_names().decode().split("\n")
+
+
+def hist_launch_counts():
+    """hg_hist_launch_counts: {kernel name: launches of this process so far}"""
+    names = hist_kernel_names()
+    counts = np.zeros(len(names), np.uint64)
+    assert lib_hist().hg_hist_launch_counts(_ptr(counts), counts.size) == len(names)
+    return dict(zip(names, (int(x) for x in counts)))
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -923,6 +978,28 @@ class Context:
                                         _ptr(rf) if rf.size else None, n_ref, _ptr(qf) if qf.size else None, n_qry, frag_th,
                                         _ptr(pair), _ptr(best) if want_best else None))
         return pair, best
+
+    # ---- the histogram of the ANI values of a comparison (libhypergen_hist.so) ------------------
+    def hist_add_matrix_dev(self, d_ani, rows, cols, pitch, row0, col0, pairs, bin_milli, d_counts, allow=()):
+        """hg_hist_add_matrix_dev on device pointers (ints): ADDS the block's selected pairs to d_counts, in stream order.
+        Returns the status."""
+        return self._ck(lib_hist().hg_hist_add_matrix_dev(self._h, _ptr(d_ani), rows, cols, pitch, row0, col0, pairs, bin_milli,
+                                                          _ptr(d_counts)), allow=allow)
+
+    def hist_dev(self, d_ref, d_rn, R, d_qry, d_qn, Q, hv_d, ksize, pairs, bin_milli, d_counts, block_rows=0, allow=()):
+        """hg_hist_dev on device pointers (ints), under the ctx's ANI metric; d_counts is zeroed first.  Returns the status."""
+        return self._ck(lib_hist().hg_hist_dev(self._h, _ptr(d_ref), _ptr(d_rn), R, _ptr(d_qry), _ptr(d_qn), Q, hv_d, ksize, pairs,
+                                               bin_milli, block_rows, _ptr(d_counts)), allow=allow)
+
+    def hist(self, ref_hv, ref_n2, qry_hv=None, qry_n2=None, pairs=HIST_ALL, bin_milli=100, ksize=21):
+        """hg_hist, host arrays in, the uint64 counts out; without a query side the reference set is compared with itself
+        (the form HIST_UPPER and HIST_OFFDIAG need)"""
+        r, rn = np.ascontiguousarray(ref_hv, np.int16), np.ascontiguousarray(ref_n2, np.int32)
+        q, qn = (r, rn) if qry_hv is None else (np.ascontiguousarray(qry_hv, np.int16), np.ascontiguousarray(qry_n2, np.int32))
+        counts = np.zeros(max(hist_bins(bin_milli), 1), np.uint64)
+        self._ck(lib_hist().hg_hist(self._h, _ptr(r), _ptr(rn), r.shape[0], _ptr(q), _ptr(qn), q.shape[0], r.shape[1], ksize, pairs,
+                                    bin_milli, _ptr(counts)))
+        return counts
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):
         r = np.ascontiguousarray(ref_hv, np.int16)

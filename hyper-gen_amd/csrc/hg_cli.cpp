@@ -35,6 +35,7 @@
 #include "../../include/hypergen.h"
 #include "../../include/hypergen_aa.h"
 #include "../../include/hypergen_frag.h"
+#include "../../include/hypergen_hist.h"
 #include "../../include/hypergen_rec.h"
 #include "../../include/hypergen_tx.h"
 
@@ -110,6 +111,8 @@ struct Cli {
   std::vector<uint32_t> columns;  // --columns LIST (dist): HG_PAIRS_* bits in the order listed, one further field per line each
   std::string pairs_file;         // --pairs FILE (dist): evaluate the listed name pairs instead of thresholding the matrix
   std::string newick_out;         // --newick <file> (dist on one file): the neighbour-joining tree of all its sketches
+  std::string histogram_out;      // --histogram FILE (dist): the distribution of the ANI values of every pair of the comparison (hypergen_hist.h)
+  uint32_t histogram_bin = 100;   // --histogram_bin B (dist --histogram): the width of a bin, an ANI, held in thousandths
   std::bitset<64> given;          // which options the command line carried, by row of `options`
 };
 
@@ -159,6 +162,17 @@ void take_levels(Cli &c, const Arg &a) {
     if (!c.levels.empty() && !(v > c.levels.back())) a.bad(": the levels must be strictly ascending");
     c.levels.push_back(v);
   }
+}
+// --histogram_bin B: a decimal string into thousandths, exactly: digits, then at most three behind a point; 0.001 to 100
+void take_histogram_bin(Cli &c, const Arg &a) {
+  const char *const what = " (the width of a bin as an ANI: above 0, at most 100, at most three decimals)";
+  const size_t point = std::min(a.val.find('.'), a.val.size());
+  const std::string ip = a.val.substr(0, point), fp = point < a.val.size() ? a.val.substr(point + 1) : "";
+  if (ip.size() + fp.size() == 0 || ip.size() > 6 || fp.size() > 3 || (ip + fp).find_first_not_of("0123456789") != std::string::npos) a.bad(what);
+  uint64_t v = 0;
+  for (const char ch : ip + fp + std::string(3 - fp.size(), '0')) v = v * 10 + (uint64_t)(ch - '0');
+  if (v < 1 || v > HG_HIST_MILLI_MAX) a.bad(what);
+  c.histogram_bin = (uint32_t)v;
 }
 void take_columns(Cli &c, const Arg &a) {
   static const std::pair<const char *, uint32_t> names[] = {{"mash", HG_PAIRS_MASH}, {"containment", HG_PAIRS_CONTAINMENT},
@@ -245,6 +259,12 @@ const Option options[] = {
      }, DIST, "it belongs to dist --fragments"},
     {"min_fragments", 0, [](Cli &c, const Arg &a) { c.min_fragments = a.named_uint(0xFFFFFFFFull, 1); }, DIST, "it belongs to dist --fragments"},
     {"fragment_hits", 0, [](Cli &c, const Arg &a) { c.fragment_hits = a.file(); }, DIST, "it belongs to dist --fragments"},
+    // (dist --histogram, hypergen_hist.h: rows 41 and 42, the name on a line of its own; tests/test_hist_surface.py counts all rows)
+    {"histogram",
+     0, [](Cli &c, const Arg &a) { c.histogram_out = a.file(); }, DIST, "it counts the ANI values of dist's comparison",
+     "dist with --histogram runs on the first visible GPU"},
+    {"histogram_bin",
+     0, take_histogram_bin, DIST, "it belongs to dist --histogram"},
 };
 const size_t N_OPTIONS = sizeof options / sizeof options[0];
 static_assert(N_OPTIONS <= decltype(Cli::given)().size(), "Cli::given has a bit per row");
@@ -370,6 +390,20 @@ void print_dist_help() {
               "         (reference genome, query fragment), ordered by query fragment, then reference genome: name of the\n"
               "         fragment, name of its best window, ANI.  It runs on the first visible GPU, block by block (no matrix is\n"
               "         held), and does not go with --pairs, --columns, --newick or --shards.\n");
+  // (no blank line in front: everything behind the general help stays one block, as the --fragments text does)
+  std::printf("dist --histogram FILE [--histogram_bin B]: how the ANI values of the WHOLE comparison are distributed -- the plot behind\n"
+              "         the 95 %% species gap, and how many pairs a threshold will produce, known before it is run.  Every pair dist\n"
+              "         enumerates is counted, whatever -a is: all of -r x -q with two files, the pairs i < j of one file, every\n"
+              "         ordered pair i != j of one file under --ani_metric containment.  A value counts as dist prints it, in\n"
+              "         thousandths; --histogram_bin B [0.1] is the width of a bin as an ANI, 0.001 to 100 with at most three\n"
+              "         decimals (0.1: 1001 bins; 0.001: one bin per printed value).  FILE gets one line per bin, all bins,\n"
+              "         ascending: the bin's first and last printed value, the pairs in it, the pairs in it and in all higher\n"
+              "         bins.  That last field is the number of lines of a dist -a 0 TSV that PRINT at least the bin's first\n"
+              "         value; it is not the number of lines dist -a x writes, which compares the unrounded value: a pair at\n"
+              "         94.9996 prints 95.000 and fails -a 95.  The histogram is a second pass over the comparison on the first\n"
+              "         visible GPU, block by block (no matrix is held; a width below 0.013 reads every block once per 8192 bins);\n"
+              "         -o is what it is without --histogram.  It goes with --columns and --newick and does not go with --pairs,\n"
+              "         --fragments or --shards.\n");
 }
 
 // `hyper-gen sketch --help`: the general help with a paragraph on --alphabet behind it
@@ -548,6 +582,11 @@ Cli parse(int argc, char **argv) {
       die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step is a multiple of 4 bases, at least 4");
     if (c.fragment_step > c.fragment) die("invalid value '" + std::to_string(c.fragment_step) + "' for '--fragment_step': a step above the window would leave bases out");
     if (c.fragment < c.ksize) die("invalid value '" + std::to_string(c.fragment) + "' for '--fragment': a window shorter than -k holds no k-mer");
+  }
+  if (given(c, "histogram_bin") && !given(c, "histogram")) die("--histogram_bin needs --histogram: without it dist counts no pairs");
+  if (given(c, "histogram")) {
+    if (given(c, "pairs")) die("--histogram is not supported with --pairs: it counts every pair of the comparison, not the listed ones");
+    if (fragments) die("--histogram is not supported with --fragments: it counts the ANI of whole sketches, not of fragments");
   }
   if (fragments) {
     if (given(c, "pairs")) die("--pairs is not supported with --fragments: every pair of genomes is compared");
@@ -1431,7 +1470,9 @@ int run_dist(const Cli &c) {
   const bool sym_full = sym && c.ani_metric == HG_ANI_CONTAINMENT;
   // --columns / --pairs: the pairs' further metrics come from one hg_ani_pairs_dev call on the device list, on one GPU
   // --newick: the neighbour-joining tree of the file's sketches (hg_nj_dev), on that GPU too
-  const bool pairs = given(c, "pairs"), newick = given(c, "newick"), with_cols = pairs || given(c, "columns"), one_gpu = with_cols || newick;
+  // --histogram: the counts of all pairs' ANI values (hg_hist_dev), a second pass on that GPU
+  const bool pairs = given(c, "pairs"), newick = given(c, "newick"), with_cols = pairs || given(c, "columns"), histogram = given(c, "histogram");
+  const bool one_gpu = with_cols || newick || histogram;
   const uint32_t metric_bit = c.ani_metric == HG_ANI_MASH ? HG_PAIRS_MASH : c.ani_metric == HG_ANI_CONTAINMENT ? HG_PAIRS_CONTAINMENT : HG_PAIRS_MAX_CONTAINMENT;
   uint32_t mask = pairs ? metric_bit : 0u;  // (--pairs: the ANI field itself is a column of the call)
   for (const uint32_t b : c.columns) mask |= b;
@@ -1493,6 +1534,18 @@ int run_dist(const Cli &c) {
     if (n_joins) d_joins.download(joins.data(), n_joins);
     debugf("neighbour joining of %zu sketches in %.1f ms", R.n, (now_s() - tn) * 1e3);
   }
+  std::vector<uint64_t> hist;  // --histogram: the counts, computed while the sketches are on the device
+  if (histogram) {
+    hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+    const double th = now_s();
+    hist.resize(hg_hist_bins(c.histogram_bin));
+    DevBuf<uint64_t> d_hist(ctx, hist.size());
+    // dist's own enumeration: i != j of the one file under containment, i < j of the one file, everything of two files
+    ck(ctx, hg_hist_dev(ctx, s.dR.hv[0], s.dR.n2[0], R.n, dq.hv[0], dq.n2[0], Q.n, (uint32_t)R.hv_d, R.ksize,
+                        sym_full ? HG_HIST_OFFDIAG : sym ? HG_HIST_UPPER : HG_HIST_ALL, c.histogram_bin, 0, d_hist.get()), "histogram");
+    d_hist.download(hist.data(), hist.size());
+    debugf("histogram of all pairs in %zu bins in %.1f ms", hist.size(), (now_s() - th) * 1e3);
+  }
   if (sym_full && !pairs) {  // (the pairs i = j are not written: the order of the rest stays)
     size_t w = 0;
     for (size_t i = 0; i < found; ++i)
@@ -1535,6 +1588,19 @@ int run_dist(const Cli &c) {
     dump_text(c.newick_out, std::string(text, len), "Dump Newick file failed!");
     hg_free(text);
     std::snprintf(buf, sizeof buf, "Output neighbour-joining tree of %zu genomes to file %s", R.n, c.newick_out.c_str());
+    logline("INFO", buf);
+  }
+  if (histogram) {  // one line per bin: first and last printed value, pairs, pairs in this and all higher bins
+    std::vector<uint64_t> above(hist.size() + 1, 0);
+    for (size_t b = hist.size(); b-- > 0;) above[b] = above[b + 1] + hist[b];
+    std::string text;
+    for (size_t b = 0; b < hist.size(); ++b) {
+      const uint64_t lo = b * (uint64_t)c.histogram_bin, hi = std::min<uint64_t>(lo + c.histogram_bin - 1, HG_HIST_MILLI_MAX);
+      text += milli_str(lo) + "\t" + milli_str(hi) + "\t" + std::to_string(hist[b]) + "\t" + std::to_string(above[b]) + "\n";
+    }
+    dump_text(c.histogram_out, text, "Dump histogram file failed!");
+    std::snprintf(buf, sizeof buf, "Output ANI histogram of %llu pairs in %zu bins of width %s to file %s", (unsigned long long)above[0], hist.size(),
+                  milli_str(c.histogram_bin).c_str(), c.histogram_out.c_str());
     logline("INFO", buf);
   }
   std::snprintf(buf, sizeof buf, "Computed ANIs for %zu ref files and %zu query files took %.3fs", R.n, Q.n, now_s() - t0);
