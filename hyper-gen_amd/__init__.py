@@ -703,6 +703,67 @@ def hist_launch_counts():
     return dict(zip(names, (int(x) for x in counts)))
 
 
+# ---- libhypergen_tri.so (include/hypergen_tri.h): the ANI matrix of all pairs of one set as fixed-width text ----
+TRI_LIB_PATH = os.path.join(_HERE, "libhypergen_tri.so")
+TRI_EXPORTS = [
+    "hg_tri_text_bytes", "hg_tri_field_offset", "hg_tri_format_dev", "hg_tri_dev", "hg_tri_stream_dev", "hg_tri", "hg_tri_tile_rows",
+    "hg_tri_tile_cols", "hg_tri_threads", "hg_tri_kernel_names", "hg_tri_launch_counts",
+]
+TRI_LOWER, TRI_FULL = 0, 1  # HG_TRI_*: the fields j < i of row i; all of them
+TRI_FIELD_BYTES = 8  # HG_TRI_FIELD_BYTES
+TRI_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t)  # hg_tri_sink
+
+
+@functools.lru_cache(None)
+def lib_tri():
+    """The sixth companion library, loaded behind lib() like lib_aa()."""
+    lib()
+    vp, sz, u32, u64 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64
+    sig = {
+        "hg_tri_text_bytes": (u64, [u32, u64, u64, u64]),
+        "hg_tri_field_offset": (u64, [u32, u64, u64, u64, u64]),
+        "hg_tri_format_dev": (C.c_int, [vp, vp, sz, sz, sz, sz, u32, vp]),
+        "hg_tri_dev": (C.c_int, [vp, vp, vp, sz, u32, u32, u32, sz, vp]),
+        "hg_tri_stream_dev": (C.c_int, [vp, vp, vp, sz, u32, u32, u32, sz, TRI_SINK, vp]),
+        "hg_tri": (C.c_int, [vp, vp, vp, sz, u32, u32, u32, vp]),
+        "hg_tri_tile_rows": (u32, []),
+        "hg_tri_tile_cols": (u32, []),
+        "hg_tri_threads": (u32, []),
+        "hg_tri_kernel_names": (C.c_char_p, []),
+        "hg_tri_launch_counts": (u32, [vp, u32]),
+    }
+    return _load("libhypergen_tri.so", TRI_LIB_PATH, sig, TRI_EXPORTS)
+
+
+def tri_text_bytes(layout, row0, rows, cols):
+    """hg_tri_text_bytes (needs no GPU): the bytes of the field text of the rows [row0, row0 + rows)"""
+    return int(lib_tri().hg_tri_text_bytes(layout, row0, rows, cols))
+
+
+def tri_field_offset(layout, row0, i, j, cols):
+    """hg_tri_field_offset (needs no GPU): where the field of the pair (i, j) starts in the field text of a block at row0"""
+    return int(lib_tri().hg_tri_field_offset(layout, row0, i, j, cols))
+
+
+def tri_geometry():
+    """dict of hg_tri_tile_rows, hg_tri_tile_cols and hg_tri_threads"""
+    L = lib_tri()
+    return {"tile_rows": int(L.hg_tri_tile_rows()), "tile_cols": int(L.hg_tri_tile_cols()), "threads": int(L.hg_tri_threads())}
+
+
+def tri_kernel_names():
+    """hg_tri_kernel_names: the library's kernels as rocprofv3 spells them"""
+    return lib_tri().hg_tri_kernel_names().decode().split("\n")
+
+
+def tri_launch_counts():
+    """hg_tri_launch_counts: {kernel name: launches of this process so far}"""
+    names = tri_kernel_names()
+    counts = np.zeros(len(names), np.uint64)
+    assert lib_tri().hg_tri_launch_counts(_ptr(counts), counts.size) == len(names)
+    return dict(zip(names, (int(x) for x in counts)))
+
+
 def dist_tile_order(tiles_m, tiles_n, tile_rows=256, tile_cols=320, diagonal_first=False, symmetric=False, ref_off=0, qry_off=0):
     """hg_dist_tile_order: the slot -> tile table of a launch as a uint32 array (tm | tn << 16, 0xFFFFFFFF = no tile)"""
     n = C.c_size_t(0)
@@ -1000,6 +1061,32 @@ class Context:
         self._ck(lib_hist().hg_hist(self._h, _ptr(r), _ptr(rn), r.shape[0], _ptr(q), _ptr(qn), q.shape[0], r.shape[1], ksize, pairs,
                                     bin_milli, _ptr(counts)))
         return counts
+
+    # ---- the ANI matrix of all pairs as fixed-width text (libhypergen_tri.so) ------------------------
+    def tri_format_dev(self, d_ani, rows, cols, pitch, row0, layout, d_text, allow=()):
+        """hg_tri_format_dev on device pointers (ints): the fields of one block into d_text, in stream order.  Returns the status."""
+        return self._ck(lib_tri().hg_tri_format_dev(self._h, _ptr(d_ani), rows, cols, pitch, row0, layout, _ptr(d_text)), allow=allow)
+
+    def tri_dev(self, d_hv, d_n2, n, hv_d, ksize, layout, d_text, block_rows=0, allow=()):
+        """hg_tri_dev on device pointers (ints), under the ctx's ANI metric: the whole field text into d_text.  Returns the status."""
+        return self._ck(lib_tri().hg_tri_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, layout, block_rows, _ptr(d_text)), allow=allow)
+
+    def tri_stream_dev(self, d_hv, d_n2, n, hv_d, ksize, layout, sink, block_rows=0, allow=()):
+        """hg_tri_stream_dev on device pointers (ints): sink(text: bytes, row0, rows) is called per block on this thread and
+        ends the call (HG_ERR_IO) by returning anything but None or 0.  Returns the status."""
+        def c_sink(_user, text, nbytes, row0, rows):
+            return int(sink(C.string_at(text, nbytes) if nbytes else b"", int(row0), int(rows)) or 0)
+
+        return self._ck(lib_tri().hg_tri_stream_dev(self._h, _ptr(d_hv), _ptr(d_n2), n, hv_d, ksize, layout, block_rows, TRI_SINK(c_sink), None),
+                        allow=allow)
+
+    def tri(self, hv, n2, layout=TRI_LOWER, ksize=21):
+        """hg_tri, host arrays in, the field text of all pairs of the set out (bytes)"""
+        h, hn = np.ascontiguousarray(hv, np.int16), np.ascontiguousarray(n2, np.int32)
+        n = h.shape[0]
+        text = np.zeros(max(tri_text_bytes(layout, 0, n, n), 1), np.uint8)
+        self._ck(lib_tri().hg_tri(self._h, _ptr(h), _ptr(hn), n, h.shape[1], ksize, layout, _ptr(text)))
+        return text[: tri_text_bytes(layout, 0, n, n)].tobytes()
 
     def dist_full(self, ref_hv, ref_n2, qry_hv, qry_n2, ksize=21):
         r = np.ascontiguousarray(ref_hv, np.int16)

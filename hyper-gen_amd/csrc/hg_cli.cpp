@@ -10,6 +10,7 @@
 #include <sched.h>
 #include <unistd.h>
 #include <sys/stat.h>
+#include <sys/uio.h>
 
 #include <algorithm>
 #include <atomic>
@@ -37,6 +38,7 @@
 #include "../../include/hypergen_frag.h"
 #include "../../include/hypergen_hist.h"
 #include "../../include/hypergen_rec.h"
+#include "../../include/hypergen_tri.h"
 #include "../../include/hypergen_tx.h"
 
 namespace {
@@ -77,7 +79,7 @@ void debugf(const char *fmt, ...) {
 
 enum class Linkage { single, greedy, setcover };
 enum class SearchPath { automatic, hits, topk };  // automatic: topk whenever top_n <= HG_SEARCH_TOPK_MAX, else the hit list
-enum : unsigned { SKETCH = 1, DIST = 2, SEARCH = 4, CLUSTER = 8, ANY = 15 };  // subcommands, as bits of Option::modes
+enum : unsigned { SKETCH = 1, DIST = 2, SEARCH = 4, CLUSTER = 8, TRIANGLE = 16, ANY = 31 };  // subcommands, as bits of Option::modes
 
 struct Cli {
   std::string mode, path = "1", path_r = "1", path_q = "1", out, method = "t1ha2", device = "cpu";
@@ -456,6 +458,25 @@ void print_sketch_help() {
               "         --individual, with --alphabet protein, with --translate or with --shards.\n");
 }
 
+// `hyper-gen triangle --help`: the general help (which does not list the subcommand: its text is pinned) with a paragraph on
+// the matrix file behind it
+void print_triangle_help() {
+  print_help();
+  std::printf("hyper-gen triangle -p {sketch_file} -o {output_matrix} [-t N] [--ani_metric mash|max_containment|containment]: the ANI of\n"
+              "         all pairs of the file's n sketches as a PHYLIP-like matrix of fixed-width text, formatted on the first\n"
+              "         visible GPU block by block while the host writes the block before.  The first line is n; then one line per\n"
+              "         sketch: its name as dist writes it, a tab, and the row's fields.  A field is 8 bytes: the ANI as dist\n"
+              "         prints it, right-aligned in 7 characters (\"  0.000\", \" 95.123\", \"100.000\"), then a tab, or a newline\n"
+              "         behind the row's last field.  --ani_metric mash [default] and max_containment write the lower triangle: row\n"
+              "         i carries the fields j < i, row 0 its name alone, and the fields of row i start 8 * i * (i - 1) / 2 bytes\n"
+              "         into the field text.  --ani_metric containment is directional and writes the square: row i carries all n\n"
+              "         fields, the diagonal included, starting 8 * i * n bytes into the field text.  In the file the field (i, j)\n"
+              "         lies at the length of the first line, plus the lengths of the names of rows 0..i and one byte each, plus\n"
+              "         the start of row i in the field text, plus 8 * j: a reader can seek to any pair.  Every field equals the third\n"
+              "         column of the same file's dist -a 0 line for that pair, so the matrix can be reproduced from dist -a 0.\n"
+              "         -a is accepted and ignored: every pair is written.  -t threads [16] write a block's rows.\n");
+}
+
 // what --translate and --alphabet protein (`opt`; its input is `input`) have in common: neither goes with --min_count or
 // --shards, k defaults to 9 and is at most 32
 void amino_acid_mode(Cli &c, const std::string &opt, const std::string &input) {
@@ -477,16 +498,16 @@ Cli parse(int argc, char **argv) {
     print_help();
     std::exit(0);
   }
-  static const char *const modes[] = {"sketch", "dist", "search", "cluster"};
+  static const char *const modes[] = {"sketch", "dist", "search", "cluster", "triangle"};
   unsigned k_mode = 0;
-  for (unsigned k = 0; k < 4; ++k)
+  for (unsigned k = 0; k < 5; ++k)
     if (c.mode == modes[k]) c.mode_bit = 1u << (k_mode = k);
   if (!c.mode_bit) die("unknown subcommand '" + c.mode + "'");
   if (c.mode_bit != SKETCH) c.method = "fracminhash";
   if (c.mode_bit == CLUSTER) c.ani_th = 95.0f;
   for (int i = 2; i < argc; ++i) {
     Arg a{argv[i], "", nullptr};
-    static void (*const help_of[])() = {print_sketch_help, print_dist_help, nullptr, print_cluster_help};  // by subcommand; search has none
+    static void (*const help_of[])() = {print_sketch_help, print_dist_help, nullptr, print_cluster_help, print_triangle_help};  // by subcommand; search has none
     if (help_of[k_mode] && (a.flag == "--help" || a.flag == "-h")) {
       help_of[k_mode]();
       std::exit(0);
@@ -1953,6 +1974,85 @@ int run_cluster(const Cli &c) {
   logline("INFO", buf);
   return 0;
 }
+
+// triangle: the ANI of all pairs of one file as fixed-width text (hypergen_tri.h).  Every byte of the file has a closed-form
+// place -- "n\n", then per row the name, a separator and the row's fields -- so a block that hg_tri_stream_dev hands over goes
+// straight to its rows' offsets, its rows dealt to -t threads, while the device computes and formats the next block.
+struct TriangleFile {
+  const Loaded &L;
+  int fd;
+  uint32_t layout;
+  unsigned threads;
+  size_t head;                   // bytes of the first line
+  std::vector<uint64_t> name_at;  // bytes of the names and their separators in front of row i
+  std::atomic<bool> bad{false};
+  bool write_all(const char *p, size_t left, uint64_t off) {
+    while (left) {
+      const ssize_t w = ::pwrite(fd, p, left, (off_t)off);
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) return false;
+      p += w, off += (size_t)w, left -= (size_t)w;
+    }
+    return true;
+  }
+  // row i: its name, '\t' (a row without fields: '\n') and `bytes` of fields
+  bool write_row(size_t i, const char *fields, size_t bytes) {
+    std::string name(L.len[i] + 1, bytes ? '\t' : '\n');
+    L.put_name(&name[0], i);
+    const uint64_t off = head + name_at[i] + hg_tri_field_offset(layout, 0, i, 0, L.n);
+    struct iovec iov[2] = {{&name[0], name.size()}, {const_cast<char *>(fields), bytes}};
+    ssize_t w;
+    do w = ::pwritev(fd, iov, bytes ? 2 : 1, (off_t)off);
+    while (w < 0 && errno == EINTR);
+    if (w < 0) return false;
+    if ((size_t)w == name.size() + bytes) return true;
+    // a short write: the rest piece by piece
+    const size_t done = (size_t)w;
+    if (done < name.size() && !write_all(name.data() + done, name.size() - done, off + done)) return false;
+    const size_t of_fields = done > name.size() ? done - name.size() : 0;
+    return write_all(fields + of_fields, bytes - of_fields, off + name.size() + of_fields);
+  }
+  static int sink(void *user, const char *text, size_t, size_t row0, size_t rows) {
+    TriangleFile &f = *static_cast<TriangleFile *>(user);
+    const size_t T = std::max<size_t>(1, std::min<size_t>(f.threads, rows));
+    parallel(T, [&](size_t t) {
+      for (size_t i = row0 + rows * t / T, hi = row0 + rows * (t + 1) / T; i < hi && !f.bad; ++i)
+        if (!f.write_row(i, text + hg_tri_field_offset(f.layout, row0, i, 0, f.L.n), (size_t)hg_tri_text_bytes(f.layout, i, 1, f.L.n))) f.bad = true;
+    });
+    return f.bad ? 1 : 0;
+  }
+};
+
+int run_triangle(const Cli &c) {
+  if (c.path == "1" || c.out.empty()) die("the following required arguments were not provided: --path --out");
+  const double t0 = now_s();
+  const uint32_t layout = c.ani_metric == HG_ANI_CONTAINMENT ? HG_TRI_FULL : HG_TRI_LOWER;  // (the directional metric: every ordered pair)
+  Session s(1, c.ani_metric, c.path);
+  const Loaded &L = s.R;
+  to_devices(s.multi, L, s.dR);
+  logline("INFO", "Computing ANI..");
+  const double tp = now_s();
+  hg_ctx *ctx = hg_multi_ctx(s.multi, 0);
+  const char *const failed = "Dump matrix file failed!";
+  const int fd = ::open(c.out.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
+  if (fd < 0) die(failed);
+  const std::string first = std::to_string(L.n) + "\n";
+  TriangleFile f{L, fd, layout, c.threads ? c.threads : 1u, first.size(), std::vector<uint64_t>(L.n + 1, 0)};
+  for (size_t i = 0; i < L.n; ++i) f.name_at[i + 1] = f.name_at[i] + L.len[i] + 1;
+  if (!f.write_all(first.data(), first.size(), 0)) die(failed);
+  const hg_status st = hg_tri_stream_dev(ctx, s.dR.hv[0], s.dR.n2[0], L.n, (uint32_t)L.hv_d, L.ksize, layout, 0, TriangleFile::sink, &f);
+  if (f.bad || st == HG_ERR_IO) die(failed);
+  ck(ctx, st, "triangle");
+  if (::close(fd) != 0) die(failed);
+  const uint64_t size = f.head + f.name_at[L.n] + hg_tri_text_bytes(layout, 0, L.n, L.n);
+  debugf("matrix of %.1f MB computed, formatted and written in %.1f ms", size / 1e6, (now_s() - tp) * 1e3);
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "Output ANI matrix of %zu sketches (%s) to file %s", L.n, layout == HG_TRI_LOWER ? "lower triangle" : "square", c.out.c_str());
+  logline("INFO", buf);
+  std::snprintf(buf, sizeof buf, "Computed ANI matrix of %zu files took %.3fs", L.n, now_s() - t0);
+  logline("INFO", buf);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -1962,5 +2062,6 @@ int main(int argc, char **argv) {
   if (c.mode_bit == SKETCH) return run_sketch(c);
   if (c.mode_bit == DIST) return run_dist(c);
   if (c.mode_bit == CLUSTER) return run_cluster(c);
+  if (c.mode_bit == TRIANGLE) return run_triangle(c);
   return run_search(c);
 }
